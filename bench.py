@@ -1,8 +1,12 @@
 #!/usr/bin/env python
 """ASD training-step benchmark (BASELINE.json metric: ASD train steps/sec, 64x64 render, SD-2.1 guidance).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what the headline figure does not need: the
+roofline legs of the dominant kernels and the CPU baseline.  --dump-outputs DIR writes what the last timed step left a caller
+(dump_outputs below).
 
 One "step" = StableDreamer.train_one_step on the asd_sd_nerf configuration (configs[1] of BASELINE.json):
 random camera -> HIP render (march, prune, field, composite) -> VAE encode 512^2 -> SD-2.1 UNet x5 (CFG +
@@ -626,6 +630,50 @@ def cpu_baseline(system, batch, seed: int):
             "step_seconds": round(total, 2), "step_seconds_all": [round(t, 2) for t in totals], "cpu_model": cpu_model, "host_threads_available": os.cpu_count(), "phases_s": {k: round(v, 3) for k, v in tm.items()}}
 
 
+DUMP_BUDGET_BYTES = 64 << 20      # --dump-outputs: at most 64 MB in all
+DUMP_SAMPLE = 1 << 20             # elements kept of a larger tensor: a fixed, seeded sample of its flattened entries
+DUMP_SEED = 0
+DUMP_RENDER_KEYS = ("comp_rgb", "opacity")
+
+
+def capture_render_outputs(system):
+    """--dump-outputs: a forward hook on the system that keeps references (no copy, no sync) to the image and opacity each training step
+    renders; after the timed steps the dict holds those of the last one"""
+    kept = {}
+
+    def hook(module, inputs, out):
+        kept.update({k: out[k] for k in DUMP_RENDER_KEYS if torch.is_tensor(out.get(k))})
+
+    system.register_forward_hook(hook)
+    return kept
+
+
+def dump_outputs(out_dir, loss, rendered):
+    """--dump-outputs DIR: what the last timed step computed, as DIR/<name>.npy in float32 — the loss train_one_step returns (loss.npy)
+    and the image and opacity the step rendered on its way there (render.comp_rgb.npy, render.opacity.npy).  The trained state (parameters,
+    gradients, Adam moments) is not written: it carries every step's float-atomic rounding (GroupNorm statistics, hash-grid gradient
+    scatter) through Adam's normalised updates and is not reproducible run to run, while these per-step outputs are, within rounding.
+    A tensor of more than DUMP_SAMPLE elements would be written as the entries at DUMP_SAMPLE sorted indices drawn without replacement
+    by numpy.random.default_rng(DUMP_SEED).  Returns the file names."""
+    import numpy as np
+
+    arrays = {"loss": loss.detach().reshape(1)}
+    arrays.update({"render." + k: t.detach() for k, t in rendered.items()})
+    os.makedirs(out_dir, exist_ok=True)
+    total, names = 0, []
+    for name, t in arrays.items():
+        if t.numel() == 0:
+            continue
+        a = t.reshape(-1).float().cpu().numpy()
+        if a.size > DUMP_SAMPLE:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_SAMPLE, replace=False))]
+        total += a.nbytes
+        assert total <= DUMP_BUDGET_BYTES, f"--dump-outputs: more than {DUMP_BUDGET_BYTES >> 20} MB at {name}"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        names.append(name)
+    return names
+
+
 def dist_evidence(world, rank, local_rank, dev, ex):
     """What a multi-GPU line must carry so that it proves itself: the world size as an all-reduce of ones sees it (RCCL, not the
     environment), every rank's device, the bytes one gradient exchange moves per rank and how the exchange is cut (launch.py:233-240:
@@ -660,8 +708,11 @@ def main():
     ap.add_argument("--backend", default=os.environ.get("ASD_BACKEND", "hip"), choices=["hip", "eager"])
     ap.add_argument("--workload", default="asd_sd_nerf", choices=["asd_sd_nerf", "asd_mv_nerf", "asd_sd_hyper_ingp", "asd_sd_3dconv_net", "asd_mv_triplane"],
                     help="asd_sd_nerf = BASELINE configs[1] (the headline metric); asd_mv_nerf = SURVEY C3 (MVDream, 4 views), secondary")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true", help="same-box A/B runs (tools/r6_ab_env.sh): the step line only, no roofline legs")
+    ap.add_argument("--full", action="store_true", help="also the measurements the headline figure does not need: roofline legs and CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the loss, parameters, gradients and buffers of the last step as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: no roofline legs")
     ap.add_argument("--render", type=int, default=0, help="secondary workloads only: render size override (e.g. 256 for BASELINE's wording of configs[4])")
     ap.add_argument("--phases", action="store_true", help="also report per-phase milliseconds (adds syncs; untimed extra steps)")
     args = ap.parse_args()
@@ -700,6 +751,7 @@ def main():
 
     for _ in range(args.warmup):
         step()
+    rendered = capture_render_outputs(system) if args.dump_outputs and rank == 0 else None
     trace_mark()                                      # outside the timed region: opens it in a kernel trace (tools/db_steps.py)
     torch.cuda.synchronize()
     if world > 1:
@@ -724,6 +776,8 @@ def main():
 
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     pct = lambda q: round(step_ms[min(len(step_ms) - 1, int(q * len(step_ms)))], 3)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, rendered)
     ex = system.gradient_exchange() if hasattr(system, "gradient_exchange") else None
     allreduce_ms = round(ex.exposed_ms(), 3) if ex is not None else None
     evidence = dist_evidence(world, rank, local_rank, dev, ex)
@@ -803,28 +857,27 @@ def main():
             out.pop("kept_samples_last_step", None)
         if phases:
             out["phases_ms"] = phases
-        # `roofline` = the kernel rocprofv3 ranks first for this step (profiles/: see DOMINANT above); the other families follow
-        if args.no_roofline:
-            print(json.dumps(out), flush=True)
-            return
-        lines = {"gemm": roofline_gemm_kernel(), "vae_conv": roofline_conv_kernel("vae512"), "unet_conv": roofline_conv_kernel("unet64")}
-        if args.workload == "asd_sd_nerf":
-            lines["pp_conv"] = roofline_pp_kernel()
-            lines["gemm256"] = roofline_gemm256_kernel()
-        if args.workload in ("asd_sd_nerf", "asd_mv_nerf"):
-            lines["field_bwd"] = roofline_field_bwd(system, batch, reps=5)
-            lines["renderer"] = roofline_field_kernel(system, batch)
-        if args.workload == "asd_sd_3dconv_net":
-            lines["conv3d"] = roofline_conv3d()
-        dom = DOMINANT if DOMINANT in lines and lines[DOMINANT] is not None else ("conv3d" if "conv3d" in lines else "gemm")
-        out["roofline"] = lines.pop(dom)
-        out["roofline"]["rank_source"] = (DOMINANT_SOURCE if dom == DOMINANT else
-                                          "profiles/r04_c4_3dconv_step_breakdown.txt (generator unchanged in round 5): its convolution kernels lead this workload's step" if dom == "conv3d"
-                                          else "secondary workload: most frequent GEMM of the diffusion prior")
-        for k, v in lines.items():
-            out["roofline_" + k] = v
-        if world == 1 and not args.no_cpu_baseline and args.workload == "asd_sd_nerf":
-            out["cpu_baseline"] = cpu_baseline(system, batch, seed=10)
+        # --full only: `roofline` = the kernel rocprofv3 ranks first for this step (profiles/: see DOMINANT above); the other families follow,
+        # then the CPU baseline.  --no-roofline drops both, --no-cpu-baseline the latter.
+        if args.full and not args.no_roofline:
+            lines = {"gemm": roofline_gemm_kernel(), "vae_conv": roofline_conv_kernel("vae512"), "unet_conv": roofline_conv_kernel("unet64")}
+            if args.workload == "asd_sd_nerf":
+                lines["pp_conv"] = roofline_pp_kernel()
+                lines["gemm256"] = roofline_gemm256_kernel()
+            if args.workload in ("asd_sd_nerf", "asd_mv_nerf"):
+                lines["field_bwd"] = roofline_field_bwd(system, batch, reps=5)
+                lines["renderer"] = roofline_field_kernel(system, batch)
+            if args.workload == "asd_sd_3dconv_net":
+                lines["conv3d"] = roofline_conv3d()
+            dom = DOMINANT if DOMINANT in lines and lines[DOMINANT] is not None else ("conv3d" if "conv3d" in lines else "gemm")
+            out["roofline"] = lines.pop(dom)
+            out["roofline"]["rank_source"] = (DOMINANT_SOURCE if dom == DOMINANT else
+                                              "profiles/r04_c4_3dconv_step_breakdown.txt (generator unchanged in round 5): its convolution kernels lead this workload's step" if dom == "conv3d"
+                                              else "secondary workload: most frequent GEMM of the diffusion prior")
+            for k, v in lines.items():
+                out["roofline_" + k] = v
+            if world == 1 and not args.no_cpu_baseline and args.workload == "asd_sd_nerf":
+                out["cpu_baseline"] = cpu_baseline(system, batch, seed=10)
         print(json.dumps(out), flush=True)
     if world > 1:
         torch.distributed.barrier()
@@ -845,6 +898,7 @@ def main_stub(args, rank, world):
     asd_dist.broadcast_parameters(system)
     for _ in range(args.warmup):
         system.train_one_step(data.collate())
+    rendered = capture_render_outputs(system) if args.dump_outputs and rank == 0 else None
     if world > 1:
         torch.distributed.barrier()
     t0 = time.perf_counter()
@@ -857,6 +911,8 @@ def main_stub(args, rank, world):
         tmax = torch.tensor([dt], dtype=torch.float64)
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, rendered)
     ex = system.gradient_exchange()
     evidence = dist_evidence(world, rank, int(os.environ.get("LOCAL_RANK", "0")), torch.device("cpu"), ex)
     digest = torch.cat([p.detach().reshape(-1)[:64] for p in system.renderer.parameters()]).double().sum()

@@ -366,3 +366,36 @@ def test_bench_two_ranks_under_torchrun_prints_one_json_line():
     # the line proves its own world: size as an all-reduce of ones saw it, one record per rank, the bytes one exchange moves
     assert out["rccl_ranks"] == 2 and [r_["rank"] for r_ in out["ranks"]] == [0, 1] and out["collective_backend"] == "gloo"
     assert out["allreduce_units"] == 2 and out["allreduce_bytes"] > 0
+
+
+def test_bench_dump_outputs_writes_the_last_step_and_repeats(tmp_path):
+    """bench.py --dump-outputs DIR on the CPU stand-in (ASD_BENCH_STUB=1, one rank): --steps sets the timed steps, the line carries
+    ms_per_step, DIR receives the last step's loss, rendered image and opacity as non-empty float32 .npy files within 64 MB, and a
+    second run with the same arguments writes the same arrays."""
+    import json
+    import subprocess
+
+    import numpy as np
+
+    env = dict(os.environ, ASD_BENCH_STUB="1", OMP_NUM_THREADS="1")
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=240)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+        files = sorted(os.listdir(d))
+        assert files == ["loss.npy", "render.comp_rgb.npy", "render.opacity.npy"], files
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype == np.float32 and a.size > 0 for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["render.comp_rgb.npy"].shape == (8 * 8 * 3,) and arrays["render.opacity.npy"].shape == (8 * 8,)
+        assert float(arrays["loss.npy"][0]) == pytest.approx(out["loss"], rel=1e-6)
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][f], dumps[1][f], err_msg=f)

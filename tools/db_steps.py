@@ -13,7 +13,7 @@ short = lambda n: re.sub(r"\(.*", "", n.replace("void ", "").replace("(anonymous
 marker = sys.argv[sys.argv.index("--marker") + 1] if "--marker" in sys.argv else "march_kernel"
 starts = [i for i, r in enumerate(rows) if marker in r[2]]
 starts = [s for k, s in enumerate(starts) if k == 0 or s - starts[k - 1] > 50]
-# bench.py: the steps are followed by roofline micro-benchmarks that also march; use --skip-last S to stay inside the timed region
+# bench.py --full: the steps are followed by roofline micro-benchmarks that also march; use --skip-last S to stay inside the timed region
 skip = int(sys.argv[sys.argv.index("--skip-last") + 1]) if "--skip-last" in sys.argv else 0
 bracket = [i for i, r in enumerate(rows) if "asd_trace_mark_kernel" in r[2]]
 if len(bracket) >= 2 and "--skip-last" not in sys.argv:

@@ -14,7 +14,7 @@ PY
 done
 for name in default nagg12; do
   lib=""; [ $name != default ] && lib=$PWD/$V/libasd_hip_$name.so
-  ASD_HIP_LIB=$lib python bench.py --no-cpu-baseline > $OUT/c2_${name}.json 2>> $OUT/err.log
+  ASD_HIP_LIB=$lib python bench.py --full --no-cpu-baseline > $OUT/c2_${name}.json 2>> $OUT/err.log
   python - <<PY
 import json; d=json.load(open("$OUT/c2_${name}.json")); print("c2", "$name", d["value"], d["ms_per_step"], d["roofline"]["avg_launch_ms"])
 PY

@@ -4,8 +4,8 @@ O=gpurun_out/${1:-r5_final}; mkdir -p $O
 R=$PWD
 (timeout 1200 python -m pytest tests -m gpu -q > $O/gputests.log 2>&1; echo EXIT $? >> $O/gputests.log); tail -3 $O/gputests.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -i smoke
-python bench.py > $O/bench.json 2> $O/bench.err; cut -c1-200 $O/bench.json
-(cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/prof_kt && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kt -o kt -- python $R/bench.py --no-cpu-baseline > $R/$O/bench_under_trace.json 2> /tmp/kt.err; for f in $(find /tmp/prof_kt -name "*kernel_stats.csv"); do cp $f $R/$O/kernel_stats.csv; done)
+python bench.py --full > $O/bench.json 2> $O/bench.err; cut -c1-200 $O/bench.json
+(cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/prof_kt && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kt -o kt -- python $R/bench.py --full --no-cpu-baseline > $R/$O/bench_under_trace.json 2> /tmp/kt.err; for f in $(find /tmp/prof_kt -name "*kernel_stats.csv"); do cp $f $R/$O/kernel_stats.csv; done)
 head -5 $O/kernel_stats.csv | cut -c1-150
 bash tools/step_breakdown.sh ${1:-r5_final}_brk > /dev/null 2>&1; head -3 gpurun_out/${1:-r5_final}_brk/step_breakdown.txt
 bash tools/r5_pmc.sh ${1:-r5_final}_pmc FETCH_SIZE WRITE_SIZE > $O/pmc_stdout.txt 2>&1; tail -4 $O/pmc_stdout.txt
