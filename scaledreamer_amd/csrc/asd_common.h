@@ -111,6 +111,20 @@ __device__ __forceinline__ float asd_softplus(float x) { return x > 20.f ? x : l
 __device__ __forceinline__ float asd_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 __device__ __forceinline__ float asd_clampf(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// ---- SiLU of the diffusion side (nn_ops.hip, gemm_tile.h, gemm.hip) — NOT the renderer's: asd_sigmoid above keeps its IEEE division,
+// its results are compared bit for bit with the CPU oracle.  The library is built without fast-math, so `1.f / (1.f + __expf(-z))`
+// is a correctly rounded division: v_div_scale x2, v_rcp, four or five v_fma, v_div_fmas, v_div_fixup — ~10 VALU per element on
+// top of the exponential, in kernels that should be waiting for HBM.  Here: one v_exp_f32, one add, one v_rcp_f32
+// (1 ulp) in front of an fp16 store.  Saturation: z -> -inf gives exp2 = +inf, rcp(inf) = 0: silu = -0, silu' = 0;
+// z -> +inf gives exp2 = 0, sigmoid = 1: silu = z, silu' = 1; sigmoid stays inside [0, 1] for every finite z, so nothing is NaN.
+#define ASD_NEG_LOG2E (-1.4426950408889634f)
+__device__ __forceinline__ float asd_sigmoid_exp2(float t) { return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(t)); }   // t = -log2(e) * z
+__device__ __forceinline__ float asd_sigmoid_fast(float z) { return asd_sigmoid_exp2(ASD_NEG_LOG2E * z); }
+__device__ __forceinline__ float asd_silu_fast(float z) { return z * asd_sigmoid_fast(z); }
+// silu'(z) = s * (1 + z * (1 - s)) = s + z * (s - s * s) with s = sigmoid(z): two FMAs
+__device__ __forceinline__ float asd_silu_grad_s(float z, float s) { return fmaf(z, fmaf(-s, s, s), s); }
+__device__ __forceinline__ float asd_silu_grad_fast(float z) { return asd_silu_grad_s(z, asd_sigmoid_fast(z)); }
+
 // ---- hash grid ---------------------------------------------------------------------------------
 // Table index of integer corner (cx,cy,cz).  Branch-free so that the 8 gathers of a level stay in one
 // basic block: both the dense and the hashed index are formed and selected with a scalar condition.

@@ -835,7 +835,7 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const asd_gemm_arg
     }
     if (p.act == 1) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = v[r] / (1.f + __expf(-v[r]));
+        for (int r = 0; r < 4; ++r) v[r] = asd_silu_fast(v[r]);
     }
     if (p.residual) {
         const half4 b = *(const half4*)((const half_t*)p.residual + (size_t)m * p.ldr + n);
@@ -893,7 +893,7 @@ __global__ __launch_bounds__(256) void splitk_epilogue_gn_kernel(const asd_gemm_
         }
         if (p.act == 1) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) w[r] = w[r] / (1.f + __expf(-w[r]));
+            for (int r = 0; r < 4; ++r) w[r] = asd_silu_fast(w[r]);
         }
         if (p.residual) {
             const half4 b = *(const half4*)((const half_t*)p.residual + (size_t)m * p.ldr + n);
@@ -925,7 +925,7 @@ __global__ __launch_bounds__(256) void splitk_epilogue_gn_kernel(const asd_gemm_
 // (>= rows * (cg / 4) / 1024), four slabs in flight per trip.
 #define GNA_THREADS 1024
 template <int NV>
-__global__ __launch_bounds__(GNA_THREADS) void splitk_epilogue_gnapply_kernel(const asd_gemm_args p, int splits) {
+__global__ __launch_bounds__(GNA_THREADS) void splitk_epilogue_gnapply_kernel(const asd_gemm_args p, int splits, float inv_cnt /* 1 / (rows x cg), divided on the host */) {
     __shared__ float red[2 * (GNA_THREADS / 64)];
     const int cg = p.gn_cg, g4 = cg >> 2, rows = p.gn_rows;
     const int b = blockIdx.x >> 5, g = blockIdx.x & 31;
@@ -979,7 +979,7 @@ __global__ __launch_bounds__(GNA_THREADS) void splitk_epilogue_gnapply_kernel(co
         for (int r = 0; r < 4; ++r) w[r] += (float)rbias[i][r];
         if (p.act == 1) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) w[r] = w[r] / (1.f + __expf(-w[r]));
+            for (int r = 0; r < 4; ++r) w[r] = asd_silu_fast(w[r]);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) w[r] += (float)resid[i][r];
@@ -1002,7 +1002,6 @@ __global__ __launch_bounds__(GNA_THREADS) void splitk_epilogue_gnapply_kernel(co
 #pragma unroll
     for (int w = 0; w < GNA_THREADS / 64; ++w) { sum += red[2 * w]; sq += red[2 * w + 1]; }
     if (p.gn_apply_stats && tid == 0) { p.gn_apply_stats[b * 64 + g * 2] = sum; p.gn_apply_stats[b * 64 + g * 2 + 1] = sq; }
-    const float inv_cnt = 1.f / ((float)rows * (float)cg);
     const float mean = sum * inv_cnt;
     const float var = fmaxf(sq * inv_cnt - mean * mean, 0.f);
     const float rstd = rsqrtf(var + p.gn_apply_eps);
@@ -1016,7 +1015,7 @@ __global__ __launch_bounds__(GNA_THREADS) void splitk_epilogue_gnapply_kernel(co
         for (int r = 0; r < 4; ++r) {
             const float sa = rstd * (float)gm[r];
             float f = fmaf(v[i][r], sa, (float)bt[r] - mean * sa);
-            if (p.gn_apply_silu) f = f / (1.f + __expf(-f));
+            if (p.gn_apply_silu) f = asd_silu_fast(f);
             o[r] = (half_t)f;
         }
         *(half4*)((half_t*)p.gn_apply_y + (size_t)m * p.N + n) = o;
@@ -1042,9 +1041,10 @@ static void asd_launch_splitk_epilogue(const asd_gemm_args* a, hipStream_t s) {
     const int nv = a->gn_apply_y ? asd_gemm_gn_apply_nv(a) : 0;
     if (nv > 0) {
         const dim3 grid((a->M / a->gn_rows) * 32);
-        if (nv == 1) hipLaunchKernelGGL(splitk_epilogue_gnapply_kernel<1>, grid, dim3(GNA_THREADS), 0, s, *a, a->split_k);
-        else if (nv == 3) hipLaunchKernelGGL(splitk_epilogue_gnapply_kernel<3>, grid, dim3(GNA_THREADS), 0, s, *a, a->split_k);
-        else hipLaunchKernelGGL(splitk_epilogue_gnapply_kernel<ASD_GNAPPLY_MAX_NV>, grid, dim3(GNA_THREADS), 0, s, *a, a->split_k);
+        const float inv_cnt = 1.f / ((float)a->gn_rows * (float)a->gn_cg);
+        if (nv == 1) hipLaunchKernelGGL(splitk_epilogue_gnapply_kernel<1>, grid, dim3(GNA_THREADS), 0, s, *a, a->split_k, inv_cnt);
+        else if (nv == 3) hipLaunchKernelGGL(splitk_epilogue_gnapply_kernel<3>, grid, dim3(GNA_THREADS), 0, s, *a, a->split_k, inv_cnt);
+        else hipLaunchKernelGGL(splitk_epilogue_gnapply_kernel<ASD_GNAPPLY_MAX_NV>, grid, dim3(GNA_THREADS), 0, s, *a, a->split_k, inv_cnt);
         return;
     }
     const size_t total4 = (size_t)a->M * a->N / 4;

@@ -80,10 +80,7 @@ __device__ __forceinline__ void gn_tile_begin(float* lds64) {
 }
 // adds the statistics terms of the 4 stored values o (row m, channels n..n+3) to the lane's column sums: forward {v, v^2}, or — when
 // p.gn_bwd_x is set — the GroupNorm input-gradient reductions {g, g * xhat} with g = dy * silu'(z) * gamma (o is dy)
-__device__ __forceinline__ float silu_grad_f(float z) {
-    const float sg = 1.f / (1.f + __expf(-z));
-    return sg * (1.f + z * (1.f - sg));
-}
+__device__ __forceinline__ float silu_grad_f(float z) { return asd_silu_grad_fast(z); }   // no IEEE division: asd_common.h
 struct GnCol {                 // per-column constants of the backward form, formed once per column fragment (the tile lies in ONE batch element)
     float mean[4], rstd[4], gm[4], bt[4];
 };
@@ -170,7 +167,7 @@ __device__ __forceinline__ floatx4 gemm_store4(const asd_gemm_args& p, floatx4 v
     }
     if (p.act == 1) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = v[r] / (1.f + __expf(-v[r]));
+        for (int r = 0; r < 4; ++r) v[r] = asd_silu_fast(v[r]);
     }
     if (p.residual) {
         const half4 b = *(const half4*)((const half_t*)p.residual + (size_t)m * p.ldr + n);
@@ -209,7 +206,7 @@ __device__ __forceinline__ void gemm_store8(const asd_gemm_args& p, floatx4& lo,
     }
     if (p.act == 1) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = v[k] / (1.f + __expf(-v[k]));
+        for (int k = 0; k < 8; ++k) v[k] = asd_silu_fast(v[k]);
     }
     if (p.residual) {
         const half8 b = *(const half8*)((const half_t*)p.residual + (size_t)m * p.ldr + n);

@@ -128,6 +128,11 @@ void launch_gemm(Run& r, asd_gemm_args& g, Act* gn_out = nullptr, bool gn_bwd_fo
     // default since round 3: on the ping-pong kernel the epilogue's silu'(z) over the whole tile is not hidden behind another block's
     // main loop — the VAE's eleven dgrad launches grew by 22-53 us each (0.39 ms per step) for 0.33 ms of statistics passes saved; same-box
     // A/B 15.58 vs 15.64 ms per step (gpurun_out/gnb).  ASD_GN_BWD_EPILOGUE=1 switches it back on.
+    // Re-decided when silu' lost its IEEE division (asd_silu_grad_fast: ~10 VALU instead of ~25 per element): still OFF.
+    // Same box, four alternating runs of 300 steps: stand-alone statistics passes 13.748 / 13.700 / 13.698 / 13.690 ms per step, reductions in
+    // the dgrad epilogue 13.894 / 13.874 / 13.881 / 13.888 ms (+0.175 ms, every pair the same sign; the parent commit on that box 13.92 ms).
+    // The statistics passes got cheaper by the same change (statistics + apply at 512^2 x 128: 83 -> 70 us), the un-hidden epilogue
+    // arithmetic of the eleven ping-pong launches (x reload, two FMAs, v_exp, v_rcp per output and the tile reduction) did not become free.
     static const bool gn_bwd_epilogue = getenv("ASD_GN_BWD_EPILOGUE") && getenv("ASD_GN_BWD_EPILOGUE")[0] == '1';
     if (gn_bwd_form && !gn_bwd_epilogue) { gn_out = nullptr; g.gn_bwd_x = nullptr; g.gn_bwd_fstats = nullptr; g.gn_bwd_gamma = nullptr; g.gn_bwd_beta = nullptr; }
     static const bool gn_fused_apply = !(getenv("ASD_GN_FUSED_APPLY") && getenv("ASD_GN_FUSED_APPLY")[0] == '0');          // A/B switch (tools)

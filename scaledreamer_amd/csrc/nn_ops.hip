@@ -1,13 +1,17 @@
 // nn_ops.hip — bandwidth-bound layers of the SD-2.1 UNet on NHWC fp16 tensors (gfx950): GroupNorm(+SiLU),
 // LayerNorm, GEGLU, SiLU, sinusoidal timestep embedding, channel concat.  All kernels move 16 B per lane
-// (8 halfs), keep statistics in fp32 (GroupNorm32, diffusionmodules/util.py:229-231) and are HBM-bound:
-// algorithmic bytes = 2 B read + 2 B written per element (GroupNorm reads x twice: stats + apply).
+// (8 halfs) and keep statistics in fp32 (GroupNorm32, diffusionmodules/util.py:229-231); algorithmic bytes = 2 B read + 2 B
+// written per element (GroupNorm reads x twice: stats + apply).  They are MEANT to be HBM-bound; the GroupNorm(+SiLU) passes only
+// are so since their SiLU stopped dividing: built without fast-math, `v / (1.f + __expf(-v))` is an IEEE-rounded division and the
+// VALU time of the passes over the VAE's 67 MB tensors was as long as their memory time (tools/isa_mix.py and
+// tests/test_isa_divides_cpu.py keep it from coming back).  The small UNet launches (5-10 us) are latency-bound either way.
 #include "asd_common.h"
+#include <type_traits>
 
 typedef _Float16 half_t;
 typedef half_t half8 __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ float silu_f(float v) { return v / (1.f + __expf(-v)); }
+__device__ __forceinline__ float silu_f(float v) { return asd_silu_fast(v); }   // v_exp + v_rcp, no IEEE division (asd_common.h)
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
 
 // ---- GroupNorm statistics: grid (batch, chunks); block 256.  A thread owns a fixed 8-channel slot (two when
@@ -110,17 +114,19 @@ __device__ __forceinline__ void gn_reduce_partials(const float* __restrict__ par
 // Apply: same thread -> channel-slot ownership as the statistics kernel (grid (batch, chunks)): the per-channel scale and
 // shift  y = x * a + b  (a = rstd * gamma, b = beta - mean * a) are formed ONCE per thread, the row loop is one 16-byte
 // load, 8 FMAs (+ SiLU) and one 16-byte store — the first version recomputed group index, mean and rsqrt per element and
-// was VALU-bound at a quarter of the HBM rate.
+// was VALU-bound at a quarter of the HBM rate.  SILU is a template parameter (no branch in the element loop) and the exponent's
+// argument has its own folded pair:  -log2(e) * z = x * ta + tb,  so an element is cvt, 2 FMA, v_exp, add, v_rcp, mul, cvt.
+// inv_cnt = 1 / (hw * channels per group) is divided on the host.
+template <bool SILU>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const half_t* __restrict__ x1, int c1, const half_t* __restrict__ x2,
                                                        int c2, int hw, int rows_per_block, const half_t* __restrict__ gamma,
-                                                       const half_t* __restrict__ beta, float eps, int silu,
+                                                       const half_t* __restrict__ beta, float eps, float inv_cnt,
                                                        const float* __restrict__ partials, int n_chunks,
                                                        float* __restrict__ stats_out, half_t* __restrict__ y) {
     __shared__ float st[64];
     __shared__ float scratch[4][64];
     const int C = c1 + c2, slots = C / 8, cg = C / 32;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const float inv_cnt = 1.f / ((float)hw * (float)cg);
     const int r0 = blockIdx.y * rows_per_block, r1 = min(hw, r0 + rows_per_block);
     const int rows_in_flight = slots >= 256 ? 1 : 256 / slots;
     const int rsub = slots >= 256 ? 0 : tid / slots;
@@ -149,7 +155,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const half_t* __restrict_
         const int c = slot * 8;
         half8 gv = gpre, bv = bpre;
         if (j == 1) { gv = *(const half8*)(gamma + c); bv = *(const half8*)(beta + c); }
-        float sa[8], sb[8];
+        float sa[8], sb[8], ta[8], tb[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int g = (c + k) / cg;
@@ -157,6 +163,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const half_t* __restrict_
             const float var = fmaxf(st[g * 2 + 1] * inv_cnt - mean * mean, 0.f);
             sa[k] = rsqrtf(var + eps) * (float)gv[k];
             sb[k] = (float)bv[k] - mean * sa[k];
+            ta[k] = ASD_NEG_LOG2E * sa[k]; tb[k] = ASD_NEG_LOG2E * sb[k];
         }
         const half_t* base = c < c1 ? x1 + (size_t)b * hw * c1 + c : x2 + (size_t)b * hw * c2 + (c - c1);
         const size_t rstride = c < c1 ? c1 : c2;
@@ -165,8 +172,9 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const half_t* __restrict_
             half8 o;
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                float f = fmaf((float)v[k], sa[k], sb[k]);
-                if (silu) f = silu_f(f);
+                const float xf = (float)v[k];
+                float f = fmaf(xf, sa[k], sb[k]);
+                if (SILU) f *= asd_sigmoid_exp2(fmaf(xf, ta[k], tb[k]));
                 o[k] = (half_t)f;
             }
             *(half8*)(ybase + (size_t)r * C) = o;
@@ -177,14 +185,18 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const half_t* __restrict_
             for (int u = 0; u < GN_UNR; ++u) emit(pre[u], r + u * rows_in_flight);
             r += GN_UNR * rows_in_flight;
         }
-        for (; r + (GN_UNR - 1) * rows_in_flight < r1; r += GN_UNR * rows_in_flight) {
-            half8 v[GN_UNR];
+        auto trips = [&](auto uc) __attribute__((always_inline)) {      // U rows in flight per thread
+            constexpr int U = decltype(uc)::value;
+            for (; r + (U - 1) * rows_in_flight < r1; r += U * rows_in_flight) {
+                half8 v[U];
 #pragma unroll
-            for (int u = 0; u < GN_UNR; ++u) v[u] = *(const half8*)(base + (size_t)(r + u * rows_in_flight) * rstride);
+                for (int u = 0; u < U; ++u) v[u] = *(const half8*)(base + (size_t)(r + u * rows_in_flight) * rstride);
 #pragma unroll
-            for (int u = 0; u < GN_UNR; ++u) emit(v[u], r + u * rows_in_flight);
-        }
-        for (; r < r1; r += rows_in_flight) emit(*(const half8*)(base + (size_t)r * rstride), r);
+                for (int u = 0; u < U; ++u) emit(v[u], r + u * rows_in_flight);
+            }
+        };
+        trips(std::integral_constant<int, GN_UNR>{});     // (eight rows per trip on the large tensors measured the same: 43.0 vs 42.7 us)
+        trips(std::integral_constant<int, 1>{});
     }
 }
 
@@ -194,25 +206,35 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const half_t* __restrict_
 // pass 1 accumulates sum(g) and sum(g*xh) per (batch, group) exactly like the forward statistics kernel,
 // pass 2 applies the formula.  x is re-read instead of saving xh/z (bandwidth is cheaper than HBM capacity
 // is scarce here? no: 288 GB — but x must be kept for the convolution-free recompute anyway).
-__device__ __forceinline__ float silu_grad(float z) {
-    const float sg = 1.f / (1.f + __expf(-z));
-    return sg * (1.f + z * (1.f - sg));
-}
+__device__ __forceinline__ float silu_grad(float z) { return asd_silu_grad_fast(z); }   // v_exp + v_rcp + 2 FMA (asd_common.h)
+
+#ifndef GN_BWD_UNR
+#define GN_BWD_UNR 4  // rows in flight per thread in the two backward passes (two or three 16-B loads each): once the arithmetic was
+                      // light, bytes in flight per CU were what held the large tensors back (2 -> 4 rows: 83 -> 70 us for the pair at 512^2 x 128)
+#endif
+#ifndef GN_BWD_WIDE_NT
+#define GN_BWD_WIDE_NT 512  // threads per block of the backward statistics pass on the large tensors
+#endif
 
 // NT threads per block: 256, or 512 for the large tensors — the grid is capped at 256 blocks (every apply block sums all their
 // partials), and with four waves per CU the silu' arithmetic of a wave was not hidden behind anybody's loads: 2.6 TB/s on the VAE's
 // 512^2 x 128 tensors.  Eight waves per CU: 51 -> 34.5 us there, 28 -> 20 us at 256^2 x 256 (sixteen: 36.5 / 23 us, 128 registers, spills)
-template <int NT>
+// — all of that with the IEEE-division silu' (45 VALU per element pair, 113 registers).  With the present loop (26 per pair) and four
+// rows in flight: 178 registers, still one 512-thread block per CU (the grid is 256 blocks); 1024-thread blocks measured slower again
+// (pair 70 -> 86 us at 512^2 x 128).  DESIGN.md 4.15.
+// SILU is a template parameter; the per-channel constants are folded once per thread so that xh is ONE FMA of x (rstd, -mean * rstd)
+// and z one more; -log2(e) * z is then a multiply — a second folded pair (x * A + B) is the same instruction count and 16 more
+// registers per thread in a kernel that wants waves.
+template <int NT, bool SILU>
 __global__ __launch_bounds__(NT) void gn_bwd_stats_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy, int C,
                                                            int hw, int rows_per_block, const half_t* __restrict__ gamma,
-                                                           const half_t* __restrict__ beta, float eps, int silu,
+                                                           const half_t* __restrict__ beta, float eps, float inv_cnt,
                                                            const float* __restrict__ fstats, float* __restrict__ bstats) {
     __shared__ float gsum[32], gsq[32];
     const int slots = C / 8, cg = C / 32;
     const int b = blockIdx.x, tid = threadIdx.x;
     if (tid < 32) { gsum[tid] = 0.f; gsq[tid] = 0.f; }
     __syncthreads();
-    const float inv_cnt = 1.f / ((float)hw * (float)cg);
     const int r0 = blockIdx.y * rows_per_block, r1 = min(hw, r0 + rows_per_block);
     const int rows_in_flight = slots >= NT ? 1 : NT / slots;
     const int rsub = slots >= NT ? 0 : tid / slots;
@@ -222,41 +244,44 @@ __global__ __launch_bounds__(NT) void gn_bwd_stats_kernel(const half_t* __restri
         const int slot = slot0 + j * NT;
         if (slot >= slots || rsub >= rows_in_flight || (j == 1 && slots <= NT)) continue;
         const int c = slot * 8;
-        float mean[8], rstd[8], gm[8], bt[8], s[8], q[8];
+        float rstd[8], nmr[8], gm[8], bt[8], s[8], q[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int g = (c + k) / cg;
-            mean[k] = fstats[(b * 32 + g) * 2] * inv_cnt;
-            rstd[k] = rsqrtf(fmaxf(fstats[(b * 32 + g) * 2 + 1] * inv_cnt - mean[k] * mean[k], 0.f) + eps);
+            const float mean = fstats[(b * 32 + g) * 2] * inv_cnt;
+            rstd[k] = rsqrtf(fmaxf(fstats[(b * 32 + g) * 2 + 1] * inv_cnt - mean * mean, 0.f) + eps);
+            nmr[k] = -mean * rstd[k];
             gm[k] = (float)gamma[c + k]; bt[k] = (float)beta[c + k];
             s[k] = 0.f; q[k] = 0.f;
         }
-        int r = r0 + rsub;
-        for (; r + rows_in_flight < r1; r += 2 * rows_in_flight) {   // two rows (4 loads) in flight per thread
-            const size_t off0 = ((size_t)b * hw + r) * C + c, off1 = off0 + (size_t)rows_in_flight * C;
-            const half8 xv0 = *(const half8*)(x + off0), dv0 = *(const half8*)(dy + off0);
-            const half8 xv1 = *(const half8*)(x + off1), dv1 = *(const half8*)(dy + off1);
+        auto accum = [&](const half8& xv, const half8& dv) __attribute__((always_inline)) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                const float xh0 = ((float)xv0[k] - mean[k]) * rstd[k], xh1 = ((float)xv1[k] - mean[k]) * rstd[k];
-                float g0 = (float)dv0[k] * gm[k], g1 = (float)dv1[k] * gm[k];
-                if (silu) { g0 *= silu_grad(fmaf(xh0, gm[k], bt[k])); g1 *= silu_grad(fmaf(xh1, gm[k], bt[k])); }
-                s[k] += g0 + g1;
-                q[k] = fmaf(g0, xh0, fmaf(g1, xh1, q[k]));
-            }
-        }
-        for (; r < r1; r += rows_in_flight) {
-            const size_t off = ((size_t)b * hw + r) * C + c;
-            const half8 xv = *(const half8*)(x + off), dv = *(const half8*)(dy + off);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const float xh = ((float)xv[k] - mean[k]) * rstd[k];
+                const float xh = fmaf((float)xv[k], rstd[k], nmr[k]);
                 float g = (float)dv[k] * gm[k];
-                if (silu) g *= silu_grad(fmaf(xh, gm[k], bt[k]));
+                if (SILU) g *= silu_grad(fmaf(xh, gm[k], bt[k]));
                 s[k] += g;
                 q[k] = fmaf(g, xh, q[k]);
             }
-        }
+        };
+        int r = r0 + rsub;
+        // U rows per trip, all 2 U loads requested before the first is consumed: GN_BWD_UNR rows while they last, then pairs, then single rows
+        auto trips = [&](auto uc) __attribute__((always_inline)) {
+            constexpr int U = decltype(uc)::value;
+            for (; r + (U - 1) * rows_in_flight < r1; r += U * rows_in_flight) {
+                half8 xv[U], dv[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const size_t off = ((size_t)b * hw + r + u * rows_in_flight) * C + c;
+                    xv[u] = *(const half8*)(x + off); dv[u] = *(const half8*)(dy + off);
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) accum(xv[u], dv[u]);
+            }
+        };
+        trips(std::integral_constant<int, GN_BWD_UNR>{});
+        if (GN_BWD_UNR > 2) trips(std::integral_constant<int, 2>{});
+        trips(std::integral_constant<int, 1>{});
         int g = c / cg;
         float ss = 0.f, qq = 0.f;
 #pragma unroll
@@ -276,9 +301,14 @@ __global__ __launch_bounds__(NT) void gn_bwd_stats_kernel(const half_t* __restri
     }
 }
 
+// dx = rstd * (g - m1 - xh * m2), g = dy * gamma * silu'(z), with everything per-channel folded once per thread:
+//   dx = (dy * G) * silu'(z) + (xh * c2 + c1),   G = gamma * rstd, c1 = -m1 * rstd, c2 = -m2 * rstd
+// — per element cvt x, cvt dy, FMA (xh), FMA (z), the silu' of asd_common.h, one multiply and two FMAs; the other consumer's gradient
+// (ADD, a template parameter like SILU) is added in fp32 before the one rounding to fp16.
+template <bool SILU, bool ADD>
 __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const half_t* __restrict__ x, const half_t* __restrict__ dy, int C,
                                                            int hw, int rows_per_block, const half_t* __restrict__ gamma,
-                                                           const half_t* __restrict__ beta, float eps, int silu,
+                                                           const half_t* __restrict__ beta, float eps, float inv_cnt,
                                                            const float* __restrict__ fstats, const float* __restrict__ bpartials,
                                                            int n_chunks, const half_t* __restrict__ dx_add,
                                                            half_t* __restrict__ dx) {
@@ -286,7 +316,6 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const half_t* __restr
     __shared__ float scratch[4][64];
     const int slots = C / 8, cg = C / 32;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const float inv_cnt = 1.f / ((float)hw * (float)cg);
     const int r0 = blockIdx.y * rows_per_block, r1 = min(hw, r0 + rows_per_block);
     const int rows_in_flight = slots >= 256 ? 1 : 256 / slots;
     const int rsub = slots >= 256 ? 0 : tid / slots;
@@ -302,7 +331,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const half_t* __restr
         for (int u = 0; u < 2; ++u) {
             const size_t off = ((size_t)b * hw + rA + u * rows_in_flight) * C + cA;
             px[u] = *(const half8*)(x + off); pd[u] = *(const half8*)(dy + off);
-            if (dx_add) pa[u] = *(const half8*)(dx_add + off);
+            if (ADD) pa[u] = *(const half8*)(dx_add + off);
         }
     }
     gn_reduce_partials(bpartials, b, n_chunks, st, scratch);
@@ -313,27 +342,26 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const half_t* __restr
         const int c = slot * 8;
         half8 gv = gpre, bv = bpre;
         if (j == 1) { gv = *(const half8*)(gamma + c); bv = *(const half8*)(beta + c); }
-        float mean[8], rstd[8], gm[8], bt[8], m1[8], m2[8];
+        float rstd[8], nmr[8], gm[8], bt[8], G[8], c1[8], c2[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int g = (c + k) / cg;
-            mean[k] = fstats[(b * 32 + g) * 2] * inv_cnt;
-            rstd[k] = rsqrtf(fmaxf(fstats[(b * 32 + g) * 2 + 1] * inv_cnt - mean[k] * mean[k], 0.f) + eps);
+            const float mean = fstats[(b * 32 + g) * 2] * inv_cnt;
+            rstd[k] = rsqrtf(fmaxf(fstats[(b * 32 + g) * 2 + 1] * inv_cnt - mean * mean, 0.f) + eps);
+            nmr[k] = -mean * rstd[k];
             gm[k] = (float)gv[k]; bt[k] = (float)bv[k];
-            m1[k] = st[g * 2] * inv_cnt; m2[k] = st[g * 2 + 1] * inv_cnt;
+            G[k] = gm[k] * rstd[k];
+            c1[k] = -(st[g * 2] * inv_cnt) * rstd[k]; c2[k] = -(st[g * 2 + 1] * inv_cnt) * rstd[k];
         }
         auto emit = [&](const half8& xv, const half8& dv, const half8& av, int r) __attribute__((always_inline)) {
             half8 o;
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                const float xh = ((float)xv[k] - mean[k]) * rstd[k];
-                float gg = (float)dv[k] * gm[k];
-                if (silu) gg *= silu_grad(fmaf(xh, gm[k], bt[k]));
-                o[k] = (half_t)(rstd[k] * (gg - m1[k] - xh * m2[k]));
-            }
-            if (dx_add) {   // the gradient of the block's other consumer (ResnetBlock shortcut) is accumulated here
-#pragma unroll
-                for (int k = 0; k < 8; ++k) o[k] = (half_t)((float)o[k] + (float)av[k]);
+                const float xh = fmaf((float)xv[k], rstd[k], nmr[k]);
+                const float lin = fmaf(xh, c2[k], c1[k]);
+                float f = SILU ? fmaf((float)dv[k] * G[k], silu_grad(fmaf(xh, gm[k], bt[k])), lin) : fmaf((float)dv[k], G[k], lin);
+                if (ADD) f += (float)av[k];   // the gradient of the block's other consumer (ResnetBlock shortcut) is accumulated here
+                o[k] = (half_t)f;
             }
             *(half8*)(dx + ((size_t)b * hw + r) * C + c) = o;
         };
@@ -343,21 +371,23 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const half_t* __restr
             emit(px[1], pd[1], pa[1], r + rows_in_flight);
             r += 2 * rows_in_flight;
         }
-        for (; r + rows_in_flight < r1; r += 2 * rows_in_flight) {   // two rows (4-6 loads) in flight per thread
-            const size_t off0 = ((size_t)b * hw + r) * C + c, off1 = off0 + (size_t)rows_in_flight * C;
-            const half8 xv0 = *(const half8*)(x + off0), dv0 = *(const half8*)(dy + off0);
-            const half8 xv1 = *(const half8*)(x + off1), dv1 = *(const half8*)(dy + off1);
-            half8 av0 = {}, av1 = {};
-            if (dx_add) { av0 = *(const half8*)(dx_add + off0); av1 = *(const half8*)(dx_add + off1); }
-            emit(xv0, dv0, av0, r);
-            emit(xv1, dv1, av1, r + rows_in_flight);
-        }
-        for (; r < r1; r += rows_in_flight) {
-            const size_t off = ((size_t)b * hw + r) * C + c;
-            half8 av = {};
-            if (dx_add) av = *(const half8*)(dx_add + off);
-            emit(*(const half8*)(x + off), *(const half8*)(dy + off), av, r);
-        }
+        auto trips = [&](auto uc) __attribute__((always_inline)) {      // U rows (2-3 loads each) in flight per thread
+            constexpr int U = decltype(uc)::value;
+            for (; r + (U - 1) * rows_in_flight < r1; r += U * rows_in_flight) {
+                half8 xv[U], dv[U], av[U] = {};
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const size_t off = ((size_t)b * hw + r + u * rows_in_flight) * C + c;
+                    xv[u] = *(const half8*)(x + off); dv[u] = *(const half8*)(dy + off);
+                    if (ADD) av[u] = *(const half8*)(dx_add + off);
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) emit(xv[u], dv[u], av[u], r + u * rows_in_flight);
+            }
+        };
+        trips(std::integral_constant<int, GN_BWD_UNR>{});
+        if (GN_BWD_UNR > 2) trips(std::integral_constant<int, 2>{});
+        trips(std::integral_constant<int, 1>{});
     }
 }
 
@@ -620,6 +650,48 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const uint4* __restric
     for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < row16; q += (size_t)gridDim.x * 256) d[q] = s[q];
 }
 
+// the launches of the three GroupNorm passes: `silu` / `dx_add` choose the template instance, 1 / (hw * channels per group) is divided here
+static void gn_launch_apply(dim3 grid, hipStream_t s, const void* x1, int c1, const void* x2, int c2, int hw, int rows_per_block,
+                            const void* gamma, const void* beta, float eps, int silu, const float* partials, int n_chunks, float* stats,
+                            void* y) {
+    const float inv_cnt = 1.f / ((float)hw * (float)((c1 + c2) / 32));
+#define GN_APPLY_ARGS (const half_t*)x1, c1, (const half_t*)x2, c2, hw, rows_per_block, (const half_t*)gamma, (const half_t*)beta, eps, inv_cnt, \
+                      partials, n_chunks, stats, (half_t*)y
+    if (silu) hipLaunchKernelGGL(gn_apply_kernel<true>, grid, dim3(256), 0, s, GN_APPLY_ARGS);
+    else hipLaunchKernelGGL(gn_apply_kernel<false>, grid, dim3(256), 0, s, GN_APPLY_ARGS);
+#undef GN_APPLY_ARGS
+}
+
+static void gn_launch_bwd_stats(bool wide, dim3 grid, hipStream_t s, const void* x, const void* dy, int c, int hw, int rows_per_block,
+                                const void* gamma, const void* beta, float eps, int silu, const float* fstats, float* bstats) {
+    const float inv_cnt = 1.f / ((float)hw * (float)(c / 32));
+#define GN_BWD_STATS_ARGS (const half_t*)x, (const half_t*)dy, c, hw, rows_per_block, (const half_t*)gamma, (const half_t*)beta, eps, inv_cnt, fstats, bstats
+    if (wide) {
+        if (silu) hipLaunchKernelGGL((gn_bwd_stats_kernel<GN_BWD_WIDE_NT, true>), grid, dim3(GN_BWD_WIDE_NT), 0, s, GN_BWD_STATS_ARGS);
+        else hipLaunchKernelGGL((gn_bwd_stats_kernel<GN_BWD_WIDE_NT, false>), grid, dim3(GN_BWD_WIDE_NT), 0, s, GN_BWD_STATS_ARGS);
+    } else {
+        if (silu) hipLaunchKernelGGL((gn_bwd_stats_kernel<256, true>), grid, dim3(256), 0, s, GN_BWD_STATS_ARGS);
+        else hipLaunchKernelGGL((gn_bwd_stats_kernel<256, false>), grid, dim3(256), 0, s, GN_BWD_STATS_ARGS);
+    }
+#undef GN_BWD_STATS_ARGS
+}
+
+static void gn_launch_bwd_apply(dim3 grid, hipStream_t s, const void* x, const void* dy, int c, int hw, int rows_per_block, const void* gamma,
+                                const void* beta, float eps, int silu, const float* fstats, const float* bpartials, int n_chunks,
+                                const void* dx_add, void* dx) {
+    const float inv_cnt = 1.f / ((float)hw * (float)(c / 32));
+#define GN_BWD_APPLY_ARGS (const half_t*)x, (const half_t*)dy, c, hw, rows_per_block, (const half_t*)gamma, (const half_t*)beta, eps, inv_cnt, fstats, \
+                          bpartials, n_chunks, (const half_t*)dx_add, (half_t*)dx
+    if (silu) {
+        if (dx_add) hipLaunchKernelGGL((gn_bwd_apply_kernel<true, true>), grid, dim3(256), 0, s, GN_BWD_APPLY_ARGS);
+        else hipLaunchKernelGGL((gn_bwd_apply_kernel<true, false>), grid, dim3(256), 0, s, GN_BWD_APPLY_ARGS);
+    } else {
+        if (dx_add) hipLaunchKernelGGL((gn_bwd_apply_kernel<false, true>), grid, dim3(256), 0, s, GN_BWD_APPLY_ARGS);
+        else hipLaunchKernelGGL((gn_bwd_apply_kernel<false, false>), grid, dim3(256), 0, s, GN_BWD_APPLY_ARGS);
+    }
+#undef GN_BWD_APPLY_ARGS
+}
+
 extern "C" {
 
 int asd_gather_rows_f16(const void* src, const int32_t* idx_dev, int32_t n_out, int64_t row_halfs, void* dst, void* stream) {
@@ -651,9 +723,7 @@ int asd_groupnorm_f16(const void* x1, int32_t c1, const void* x2, int32_t c2, in
     const int chunks_s = chunks > cap_s ? cap_s : chunks, chunks_a = gn_apply_chunks(hw, C, batch);
     hipLaunchKernelGGL(gn_stats_kernel, dim3(batch, chunks_s), dim3(256), 0, s, (const half_t*)x1, c1, (const half_t*)x2, c2, hw,
                        asd_div_up(hw, chunks_s), partials);
-    hipLaunchKernelGGL(gn_apply_kernel, dim3(batch, chunks_a), dim3(256), 0, s, (const half_t*)x1, c1, (const half_t*)x2, c2, hw,
-                       asd_div_up(hw, chunks_a), (const half_t*)gamma, (const half_t*)beta, eps, silu, partials, chunks_s, stats,
-                       (half_t*)y);
+    gn_launch_apply(dim3(batch, chunks_a), s, x1, c1, x2, c2, hw, asd_div_up(hw, chunks_a), gamma, beta, eps, silu, partials, chunks_s, stats, y);
     ASD_LAUNCH_CHECK();
     return ASD_OK;
 }
@@ -676,8 +746,7 @@ int asd_groupnorm_apply_f16(const void* x, int32_t c, int32_t batch, int32_t hw,
         part = tmp;
         n = slices;
     }
-    hipLaunchKernelGGL(gn_apply_kernel, dim3(batch, chunks_a), dim3(256), 0, s, (const half_t*)x, c, (const half_t*)nullptr, 0, hw,
-                       asd_div_up(hw, chunks_a), (const half_t*)gamma, (const half_t*)beta, eps, silu, part, n, stats, (half_t*)y);
+    gn_launch_apply(dim3(batch, chunks_a), s, x, c, nullptr, 0, hw, asd_div_up(hw, chunks_a), gamma, beta, eps, silu, part, n, stats, y);
     ASD_LAUNCH_CHECK();
     return ASD_OK;
 }
@@ -694,15 +763,10 @@ int asd_groupnorm_bwd_f16(const void* x, const void* dy, int32_t c, int32_t batc
     // (apply blocks) x (statistics chunks) small — with 515 x 1280 blocks the prologue read 2.6x the tensor itself
     const int cap_s = asd_div_up(256, batch), cap_a = asd_div_up(GN_CAP_A, batch);
     const int chunks_s = chunks > cap_s ? cap_s : chunks, chunks_a = chunks > cap_a ? cap_a : chunks;
-    if ((size_t)asd_div_up(hw, chunks_s) * c >= 32768 && c % 8 == 0 && 512 % (c / 8) == 0)      // >= 64 KB of each tensor per block
-        hipLaunchKernelGGL(gn_bwd_stats_kernel<512>, dim3(batch, chunks_s), dim3(512), 0, s, (const half_t*)x, (const half_t*)dy, c, hw,
-                           asd_div_up(hw, chunks_s), (const half_t*)gamma, (const half_t*)beta, eps, silu, fwd_stats, bwd_stats);
-    else
-        hipLaunchKernelGGL(gn_bwd_stats_kernel<256>, dim3(batch, chunks_s), dim3(256), 0, s, (const half_t*)x, (const half_t*)dy, c, hw,
-                           asd_div_up(hw, chunks_s), (const half_t*)gamma, (const half_t*)beta, eps, silu, fwd_stats, bwd_stats);
-    hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(batch, chunks_a), dim3(256), 0, s, (const half_t*)x, (const half_t*)dy, c, hw,
-                       asd_div_up(hw, chunks_a), (const half_t*)gamma, (const half_t*)beta, eps, silu, fwd_stats, bwd_stats, chunks_s,
-                       (const half_t*)dx_add, (half_t*)dx);
+    const bool wide = (size_t)asd_div_up(hw, chunks_s) * c >= 32768 && c % 8 == 0 && GN_BWD_WIDE_NT % (c / 8) == 0;      // >= 64 KB of each tensor per block
+    gn_launch_bwd_stats(wide, dim3(batch, chunks_s), s, x, dy, c, hw, asd_div_up(hw, chunks_s), gamma, beta, eps, silu, fwd_stats, bwd_stats);
+    gn_launch_bwd_apply(dim3(batch, chunks_a), s, x, dy, c, hw, asd_div_up(hw, chunks_a), gamma, beta, eps, silu, fwd_stats, bwd_stats, chunks_s,
+                        dx_add, dx);
     ASD_LAUNCH_CHECK();
     return ASD_OK;
 }
@@ -725,9 +789,7 @@ int asd_groupnorm_bwd_apply_f16(const void* x, const void* dy, int32_t c, int32_
         part = scratch;
         n = slices;
     }
-    hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(batch, chunks_a), dim3(256), 0, s, (const half_t*)x, (const half_t*)dy, c, hw,
-                       asd_div_up(hw, chunks_a), (const half_t*)gamma, (const half_t*)beta, eps, silu, fwd_stats, part, n,
-                       (const half_t*)dx_add, (half_t*)dx);
+    gn_launch_bwd_apply(dim3(batch, chunks_a), s, x, dy, c, hw, asd_div_up(hw, chunks_a), gamma, beta, eps, silu, fwd_stats, part, n, dx_add, dx);
     ASD_LAUNCH_CHECK();
     return ASD_OK;
 }
