@@ -28,6 +28,13 @@ void asd_set_error(const char* fmt, ...);
 
 static inline int asd_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// hands out the regions of one float workspace: offsets in floats from its start, every region on a 256-byte boundary (the alignment of
+// asd_render_layout_init); `o` is the total so far.  A size query and the pass that carves the workspace run the SAME sequence of take() calls.
+struct asd_ws_cursor {
+    int64_t o = 0;
+    int64_t take(int64_t floats) { const int64_t at = o; o += (floats + 63) & ~(int64_t)63; return at; }
+};
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) must be issued once per kernel AND device (a process may drive several GPUs): one bit
 // per device in a per-call-site mask; the call is idempotent, so two threads racing here both set it and nothing is lost
 #include <atomic>

@@ -307,8 +307,8 @@ __global__ __launch_bounds__(256, 4) void field_fwd_kernel(const asd_grid_meta m
 #endif
 #define WG_TILE 64     // rows per LDS tile
 
-// PRE: the MLP half already ran on the matrix pipe (csrc/field_mfma.hip: asd_field_bwd_mlp_mfma wrote DA, the second-layer weight gradients and
-// the encoding gradients denc_pre[n][2 L]); this kernel then only scatters — no finite-difference rows in that form.
+// PRE: the MLP half already ran on the matrix pipe (csrc/field_mfma.hip: asd_field_bwd_mlp_mfma left the weight gradients and the encoding
+// gradients denc_pre[n][2 L]); this kernel then only scatters — no finite-difference rows in that form, and da_out is not touched.
 template <int L, int H, int C, int ENC = 0, bool PRE = false>
 __global__ __launch_bounds__(256, ASD_FIELD_BWD_BLOCKS) void field_bwd_sample_kernel(
     const asd_grid_meta m, const asd_field_cfg c, const float* __restrict__ grid, const float* __restrict__ w1d,
@@ -834,8 +834,8 @@ __global__ __launch_bounds__(256) void envmap_bwd_kernel(const asd_grid_meta m, 
 }
 
 int asd_field_bwd_mlp_mfma(const asd_field_cfg* cfg, const float* w1d, const float* w2d, const float* w1f, const float* w2f, const float* enc, const float* sigma,
-                           int32_t n, const int32_t* n_dev, const float* d_sigma, const float* d_features, float* da_out, float* denc_out, float* dw2d, float* dw2f,
-                           float* dw1_slabs, hipStream_t s);      // field_mfma.hip
+                           int32_t n, const int32_t* n_dev, const float* d_sigma, const float* d_features, float* denc_out, float* dw2d, float* dw2f,
+                           float* dw1_slabs, int blocks, hipStream_t s);      // field_mfma.hip
 int asd_field_bwd_mlp_mfma_blocks(int32_t n);
 
 // ---------------------------------------------------------------------------------------------------
@@ -957,18 +957,49 @@ int asd_field_fwd(const asd_grid_meta* meta, const asd_field_cfg* cfg, const flo
     return ASD_OK;
 }
 
+// The workspace of asd_field_bwd and asd_voxfield_bwd, in floats from its start: the size queries return `total`, the passes take every pointer
+// from here.  Every region starts on a 256-byte boundary; -1: not part of this configuration.
+struct field_bwd_layout {
+    bool mfma;          // hash grid, 3 feature dims, no normal gradient: MLP half + first-layer weight gradients on the matrix pipe (field_mfma.hip)
+    int n_slabs;        // slabs reserved = blocks of the launch that writes them
+    int64_t da;         // [rows][128] hidden-layer gradients, field_bwd_sample_kernel<PRE = false> -> field_wgrad_kernel; not with mfma: its MLP kernel has
+                        // no such argument and field_bwd_sample_kernel<PRE = true> skips the block that forms them
+    int64_t enc_fd;     // [3 n][32] encodings of the finite-difference points (normal gradient only)
+    int64_t slabs;      // [n_slabs][128][32] first-layer weight-gradient partial sums (field_wgrad_kernel | field_bwd_mlp_mfma_kernel)
+    int64_t priv;       // hash grid: per-XCD copies of the gradient of the ASD_FIELD_NPRIV coarsest levels
+    int64_t pg_g, pg_pos, pg_ws;    // hash grid, paged scatter of the fine levels (field_paged.h): gradients [rows][2 ASD_PG_NF_PAD], positions [rows][3], items
+    int64_t denc;       // mfma: [n][32] encoding gradients between the MLP pass and the scatter | voxel: [rows][32] feature-gradient rows
+    int64_t pts;        // voxel: [rows][3] the rows' positions for asd_voxel_sample_bwd_rows
+    int64_t total;
+};
+static int field_wgrad_chunks(int64_t rows) { return (int)((rows + WG_ROWS - 1) / WG_ROWS); }      // blocks of field_wgrad_kernel
+static bool field_paged_on() {      // ASD_FIELD_PAGED=0: the transposed-lane atomics of asd_scatter_runs for every level, the A/B partner
+    static const bool on = !(getenv("ASD_FIELD_PAGED") && atoi(getenv("ASD_FIELD_PAGED")) == 0);
+    return on;
+}
+static field_bwd_layout field_bwd_layout_init(const asd_field_cfg* cfg, int64_t n, int with_normal, bool voxel) {
+    field_bwd_layout L;
+    asd_ws_cursor w;
+    const int64_t rows = n * (with_normal ? 4 : 1);
+    const bool paged = !voxel && field_paged_on();
+    L.mfma = !voxel && !with_normal && cfg->n_feature_dims == 3;
+    L.n_slabs = L.mfma ? asd_field_bwd_mlp_mfma_blocks((int32_t)n) : field_wgrad_chunks(rows);
+    L.da = L.mfma ? -1 : w.take(rows * 128);
+    L.enc_fd = with_normal ? w.take(3 * n * 32) : -1;
+    L.slabs = w.take((int64_t)L.n_slabs * 128 * 32);
+    L.priv = !voxel && ASD_FIELD_NPRIV > 0 ? w.take((int64_t)ASD_PRIV_COPIES * ASD_FIELD_PRIV_CAP) : -1;
+    L.pg_g = paged ? w.take(rows * (2 * ASD_PG_NF_PAD)) : -1;
+    L.pg_pos = paged ? w.take(rows * 3) : -1;
+    L.pg_ws = paged ? w.take(asd_paged_workspace_floats(rows)) : -1;
+    L.denc = L.mfma ? w.take(n * 32) : voxel ? w.take(rows * 32) : -1;
+    L.pts = voxel ? w.take(rows * 3) : -1;
+    L.total = w.o;
+    return L;
+}
+
 int asd_field_bwd_workspace(const asd_field_cfg* cfg, int32_t n, int32_t with_normal, int64_t* n_floats) {
     ASD_CHECK_ARG(cfg && n_floats && n >= 0, "bad argument");
-    const int64_t rows = (int64_t)n * (with_normal ? 4 : 1);
-    int64_t chunks = (rows + WG_ROWS - 1) / WG_ROWS;
-    if (!with_normal && chunks < 4 * 512) chunks = 4 * 512;      // the matrix-pipe MLP pass leaves one weight-gradient slab per wave (field_mfma.hip)
-    // DA [rows, 128] + finite-difference encodings [3n, 32] + wgrad slabs [chunks, 128*32]
-    //   + the per-XCD copies of the gradient of the ASD_FIELD_NPRIV coarsest levels (ASD_FIELD_PRIV_CAP floats each)
-    //   + the paged scatter of the fine levels (field_paged.h): their feature gradients [rows, 20], positions [rows, 3], item lists
-    *n_floats = rows * 128 + (with_normal ? (int64_t)3 * n * 32 : 0) + chunks * 128 * 32 + 64 +
-                (ASD_FIELD_NPRIV > 0 ? (int64_t)ASD_PRIV_COPIES * ASD_FIELD_PRIV_CAP : 0) +
-                rows * (2 * ASD_PG_NF_PAD + 3) + asd_paged_workspace_floats(rows) +
-                (with_normal ? 0 : rows * 32);       // encoding gradients between the matrix-pipe MLP pass and the scatter (field_mfma.hip)
+    *n_floats = field_bwd_layout_init(cfg, n, with_normal, false).total;
     return ASD_OK;
 }
 
@@ -988,13 +1019,9 @@ int asd_field_bwd(const asd_grid_meta* meta, const asd_field_cfg* cfg, const flo
     hipStream_t s = (hipStream_t)stream;
     const int with_normal = d_normal != nullptr || d_fd_grad != nullptr;
     const int64_t rows = (int64_t)n * (with_normal ? 4 : 1);
-    int chunks = (int)((rows + WG_ROWS - 1) / WG_ROWS);
-    const int wg_chunks = chunks;                                   // slabs field_wgrad_kernel writes
-    if (!with_normal && chunks < 4 * 512) chunks = 4 * 512;         // (the layout of asd_field_bwd_workspace)
-    float* da = workspace;
-    float* enc_fd = with_normal ? da + rows * 128 : nullptr;
-    float* slabs = da + rows * 128 + (with_normal ? (int64_t)3 * n * 32 : 0);
-    float* priv = slabs + (int64_t)chunks * 128 * 32 + 64;
+    const field_bwd_layout L = field_bwd_layout_init(cfg, n, with_normal, false);
+    auto at = [&](int64_t off) { return off < 0 ? (float*)nullptr : workspace + off; };
+    float *const da = at(L.da), *const enc_fd = at(L.enc_fd), *const slabs = at(L.slabs), *priv = at(L.priv);
     uint32_t priv_stride = ASD_FIELD_NPRIV > 0 ? 2u * meta->offset[ASD_FIELD_NPRIV] : 0u;   // floats per copy
     if (priv_stride > (uint32_t)ASD_FIELD_PRIV_CAP) priv_stride = 0;    // a grid with larger coarse levels: straight into the table
     if (priv_stride > 0) {
@@ -1006,36 +1033,32 @@ int asd_field_bwd(const asd_grid_meta* meta, const asd_field_cfg* cfg, const flo
         priv = d_grid_params;
     }
     // the levels >= ASD_FIELD_NAGG (hashed: neighbouring samples share no entry) through the paged scatter — no global atomics
-    // (ASD_FIELD_PAGED=0: the transposed-lane atomics of asd_scatter_runs, the A/B partner)
     static_assert(16 - ASD_FIELD_NAGG == ASD_PG_NF, "field_paged.h is sized for the levels >= ASD_FIELD_NAGG of the 16-level grid");
-    static const int paged_on = getenv("ASD_FIELD_PAGED") ? atoi(getenv("ASD_FIELD_PAGED")) : 1;
     asd_paged_plan plan;
-    const bool paged = paged_on && asd_paged_plan_init(meta, ASD_FIELD_NAGG, &plan);
-    float* pg_g = slabs + (int64_t)chunks * 128 * 32 + 64 + (ASD_FIELD_NPRIV > 0 ? (int64_t)ASD_PRIV_COPIES * ASD_FIELD_PRIV_CAP : 0);
-    float* pg_pos = pg_g + rows * (2 * ASD_PG_NF_PAD);
-    float* pg_ws = pg_pos + rows * 3;
+    const bool paged = field_paged_on() && asd_paged_plan_init(meta, ASD_FIELD_NAGG, &plan);
+    float *const pg_g = paged ? at(L.pg_g) : nullptr, *const pg_pos = paged ? at(L.pg_pos) : nullptr;
     const dim3 grid(asd_div_up(n, 256)), block(256);
+    // slabs of the first-layer weight gradient: one per block of the launch that writes them, and slab_reduce_kernel sums that many
+    const int n_slabs = L.mfma ? asd_field_bwd_mlp_mfma_blocks(n) : field_wgrad_chunks(rows);
+    ASD_CHECK_ARG(n_slabs <= L.n_slabs, "more weight-gradient slabs than the workspace reserves");
     ASD_PROBE_START(s);
-    // the MLP half on the matrix pipe (field_mfma.hip) where there are no finite-difference rows: the headline renderer (lambda_orient = 0)
-    static const int mfma_on = getenv("ASD_FIELD_MFMA") ? atoi(getenv("ASD_FIELD_MFMA")) : 2;     // 0: the vector-pipe form (A/B partner, tools/)
-    const bool mfma = mfma_on && !with_normal && cfg->n_feature_dims == 3;
-    // ... and the first-layer weight gradient in the same pass (=2: no DA rows, no field_wgrad_kernel; 1: DA + field_wgrad_kernel, the A/B partner)
-    const bool mfma_wg = mfma && mfma_on >= 2;
-    if (mfma) {
-        float* denc = pg_ws + asd_paged_workspace_floats(rows);
-        const int rc = asd_field_bwd_mlp_mfma(cfg, w1_density, w2_density, w1_feature, w2_feature, enc_save, sigma, n, n_dev, d_sigma, d_features, da, denc,
-                                              dw2_density, dw2_feature, mfma_wg ? slabs : nullptr, s);
+    if (L.mfma) {
+        // the MLP half and the first-layer weight gradient on the matrix pipe (field_mfma.hip) where there are no finite-difference rows: the
+        // headline renderer (lambda_orient = 0); the sample kernel then only scatters
+        float* const denc = at(L.denc);
+        const int rc = asd_field_bwd_mlp_mfma(cfg, w1_density, w2_density, w1_feature, w2_feature, enc_save, sigma, n, n_dev, d_sigma, d_features, denc,
+                                              dw2_density, dw2_feature, slabs, n_slabs, s);
         if (rc != ASD_OK) return rc;
         hipLaunchKernelGGL((field_bwd_sample_kernel<16, 64, 3, 0, true>), grid, block, 0, s, *meta, *cfg, grid_params, w1_density, w2_density,
                            w1_feature, w2_feature, points, enc_save, sigma, n, n_dev, d_sigma, d_features, d_normal, d_fd_grad,
                            d_grid_params, da, enc_fd, dw2_density, dw2_feature, priv, priv_stride, (float*)nullptr, (float*)nullptr,
-                           paged ? pg_g : (float*)nullptr, paged ? pg_pos : (float*)nullptr, (const float*)denc);
+                           pg_g, pg_pos, (const float*)denc);
     } else {
 #define ASD_FIELD_BWD_LAUNCH(C_)                                                                                                     \
     hipLaunchKernelGGL((field_bwd_sample_kernel<16, 64, C_>), grid, block, 0, s, *meta, *cfg, grid_params, w1_density, w2_density,  \
                        w1_feature, w2_feature, points, enc_save, sigma, n, n_dev, d_sigma, d_features, d_normal, d_fd_grad,        \
                        d_grid_params, da, enc_fd, dw2_density, dw2_feature, priv, priv_stride, (float*)nullptr, (float*)nullptr,   \
-                       paged ? pg_g : (float*)nullptr, paged ? pg_pos : (float*)nullptr)
+                       pg_g, pg_pos)
     if (cfg->n_feature_dims == 3) ASD_FIELD_BWD_LAUNCH(3); else ASD_FIELD_BWD_LAUNCH(0);
 #undef ASD_FIELD_BWD_LAUNCH
     }
@@ -1043,14 +1066,14 @@ int asd_field_bwd(const asd_grid_meta* meta, const asd_field_cfg* cfg, const flo
         hipLaunchKernelGGL(asd_priv_reduce_kernel, dim3(asd_div_up(priv_stride / 4, 256)), block, 0, s, priv, priv_stride, priv_stride,
                            d_grid_params);
     if (paged) {
-        const int rc = asd_paged_scatter(meta, &plan, pg_pos, pg_g, n, with_normal ? 4 : 1, n_dev, d_grid_params, pg_ws, s);
+        const int rc = asd_paged_scatter(meta, &plan, pg_pos, pg_g, n, with_normal ? 4 : 1, n_dev, d_grid_params, at(L.pg_ws), s);
         if (rc != ASD_OK) return rc;
     }
     ASD_PROBE_STOP(s);
-    int n_slabs = wg_chunks;
-    const int* live = (n_dev && rows == (int64_t)n) ? n_dev : nullptr;      // every slab row is a centre row: dead chunks are skipped
-    if (mfma_wg) { n_slabs = asd_field_bwd_mlp_mfma_blocks(n); live = nullptr; }      // one slab per block of the MLP pass, all of them written
-    else hipLaunchKernelGGL((field_wgrad_kernel<128, 32>), dim3(wg_chunks), block, 0, s, da, enc_save, enc_fd, n, (int)rows, n_dev, n, slabs);
+    // the matrix-pipe pass has written every block's slab; of field_wgrad_kernel's, with a device-side count and centre rows only, the slabs of
+    // dead chunks are neither written nor summed
+    const int* live = (!L.mfma && n_dev && rows == (int64_t)n) ? n_dev : nullptr;
+    if (!L.mfma) hipLaunchKernelGGL((field_wgrad_kernel<128, 32>), dim3(n_slabs), block, 0, s, da, enc_save, enc_fd, n, (int)rows, n_dev, n, slabs);
     // slab layout [h < 64: density | h >= 64: feature][k]; both halves are contiguous H*32 blocks
     hipLaunchKernelGGL(slab_reduce_kernel, dim3(asd_div_up(64 * 32, 32)), dim3(1024), 0, s, slabs, n_slabs, 128 * 32, 64 * 32,
                        dw1_density, live, WG_ROWS);
@@ -1094,11 +1117,7 @@ int asd_voxfield_fwd(const float* voxel_cl, int32_t D, int32_t H, int32_t W, int
 
 int asd_voxfield_bwd_workspace(const asd_field_cfg* cfg, int32_t n, int32_t with_normal, int64_t* n_floats) {
     ASD_CHECK_ARG(cfg && n_floats && n >= 0, "bad argument");
-    const int64_t rows = (int64_t)n * (with_normal ? 4 : 1);
-    int64_t chunks = (rows + WG_ROWS - 1) / WG_ROWS;
-    if (!with_normal && chunks < 4 * 512) chunks = 4 * 512;      // the matrix-pipe MLP pass leaves one weight-gradient slab per wave (field_mfma.hip)
-    // DA [rows, 128] + finite-difference encodings [3n, 32] + wgrad slabs + feature-gradient rows [rows, 32] + their positions [rows, 3]
-    *n_floats = rows * 128 + (with_normal ? (int64_t)3 * n * 32 : 0) + chunks * 128 * 32 + 64 + rows * 32 + rows * 3 + 16;
+    *n_floats = field_bwd_layout_init(cfg, n, with_normal, true).total;
     return ASD_OK;
 }
 
@@ -1114,14 +1133,11 @@ int asd_voxfield_bwd(const float* voxel_cl, int32_t D, int32_t H, int32_t W, int
     hipStream_t s = (hipStream_t)stream;
     const int with_normal = d_normal != nullptr || d_fd_grad != nullptr;
     const int64_t rows = (int64_t)n * (with_normal ? 4 : 1);
-    int chunks = (int)((rows + WG_ROWS - 1) / WG_ROWS);
-    const int wg_chunks = chunks;                                   // slabs field_wgrad_kernel writes
-    if (!with_normal && chunks < 4 * 512) chunks = 4 * 512;         // (the layout of asd_field_bwd_workspace)
-    float* da = workspace;
-    float* enc_fd = with_normal ? da + rows * 128 : nullptr;
-    float* slabs = da + rows * 128 + (with_normal ? (int64_t)3 * n * 32 : 0);
-    float* denc = slabs + (int64_t)chunks * 128 * 32 + 64;
-    float* pts = denc + rows * 32;
+    const field_bwd_layout L = field_bwd_layout_init(cfg, n, with_normal, true);
+    float *const da = workspace + L.da, *const enc_fd = with_normal ? workspace + L.enc_fd : nullptr, *const slabs = workspace + L.slabs;
+    float *const denc = workspace + L.denc, *const pts = workspace + L.pts;
+    const int n_slabs = field_wgrad_chunks(rows);       // blocks of field_wgrad_kernel = slabs slab_reduce_kernel sums
+    ASD_CHECK_ARG(n_slabs <= L.n_slabs, "more weight-gradient slabs than the workspace reserves");
     const asd_grid_meta m = vox_meta(D, H, W);
     const dim3 grid(asd_div_up(n, 256)), block(256);
 #define ASD_VOXFIELD_BWD_LAUNCH(C_)                                                                                                        \
@@ -1130,13 +1146,12 @@ int asd_voxfield_bwd(const float* voxel_cl, int32_t D, int32_t H, int32_t W, int
                        dw2_sdf, dw2_feature, (float*)nullptr, 0u, denc, pts)
     if (cfg->n_feature_dims == 3) ASD_VOXFIELD_BWD_LAUNCH(3); else ASD_VOXFIELD_BWD_LAUNCH(0);
 #undef ASD_VOXFIELD_BWD_LAUNCH
-    static const int run = getenv("ASD_VOX_RUN") ? atoi(getenv("ASD_VOX_RUN")) : 128;
-    const int rc = asd_voxel_sample_bwd_rows(denc, D, H, W, C, pts, (int32_t)rows, d_voxel_cl, run, stream);     // += (atomics), amortized.hip
+    const int rc = asd_voxel_sample_bwd_rows(denc, D, H, W, C, pts, (int32_t)rows, d_voxel_cl, 128, stream);     // += (atomics), amortized.hip
     if (rc != ASD_OK) return rc;
-    hipLaunchKernelGGL((field_wgrad_kernel<128, 32>), dim3(chunks), block, 0, s, da, enc_save, enc_fd, n, (int)rows, (const int*)nullptr, n, slabs);
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(asd_div_up(64 * 32, 32)), dim3(1024), 0, s, slabs, chunks, 128 * 32, 64 * 32, dw1_sdf, (const int*)nullptr, WG_ROWS);
+    hipLaunchKernelGGL((field_wgrad_kernel<128, 32>), dim3(n_slabs), block, 0, s, da, enc_save, enc_fd, n, (int)rows, (const int*)nullptr, n, slabs);
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3(asd_div_up(64 * 32, 32)), dim3(1024), 0, s, slabs, n_slabs, 128 * 32, 64 * 32, dw1_sdf, (const int*)nullptr, WG_ROWS);
     if (cfg->n_feature_dims == 3)
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(asd_div_up(64 * 32, 32)), dim3(1024), 0, s, slabs + 64 * 32, chunks, 128 * 32, 64 * 32, dw1_feature,
+        hipLaunchKernelGGL(slab_reduce_kernel, dim3(asd_div_up(64 * 32, 32)), dim3(1024), 0, s, slabs + 64 * 32, n_slabs, 128 * 32, 64 * 32, dw1_feature,
                            (const int*)nullptr, WG_ROWS);
     ASD_LAUNCH_CHECK();
     return ASD_OK;

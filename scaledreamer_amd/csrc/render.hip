@@ -644,12 +644,26 @@ int asd_render_fwd(const asd_render_params* p, void* workspace, void* stream) {
     return ASD_OK;
 }
 
-int asd_render_bwd_workspace(const asd_render_params* p, int64_t* n_floats) {
-    ASD_CHECK_ARG(p && p->field && n_floats, "null argument");
+// the backward workspace (floats): the compositing pass's gradients w.r.t. the kept samples' densities and features, then the field's own workspace
+struct render_bwd_layout { int64_t d_sigma, d_feats, field, total; };
+static int render_bwd_layout_init(const asd_render_params* p, render_bwd_layout* L) {
     int64_t nf = 0;
     const int rc = asd_field_bwd_workspace(p->field, p->capacity, 0, &nf);
     if (rc != ASD_OK) return rc;
-    *n_floats = nf + (int64_t)4 * p->capacity + 64;
+    asd_ws_cursor w;
+    L->d_sigma = w.take((int64_t)p->capacity);
+    L->d_feats = w.take((int64_t)3 * p->capacity);
+    L->field = w.take(nf);
+    L->total = w.o;
+    return ASD_OK;
+}
+
+int asd_render_bwd_workspace(const asd_render_params* p, int64_t* n_floats) {
+    ASD_CHECK_ARG(p && p->field && n_floats, "null argument");
+    render_bwd_layout B;
+    const int rc = render_bwd_layout_init(p, &B);
+    if (rc != ASD_OK) return rc;
+    *n_floats = B.total;
     return ASD_OK;
 }
 
@@ -659,11 +673,14 @@ int asd_render_bwd(const asd_render_params* p, void* workspace, const float* d_c
     ASD_CHECK_ARG(workspace && bwd_workspace && d_grid && dw1d && dw2d && dw1f && dw2f, "null argument");
     asd_render_layout L;
     asd_render_layout_init(p->n_rays, p->capacity, &L);
+    render_bwd_layout B;
+    const int rb = render_bwd_layout_init(p, &B);
+    if (rb != ASD_OK) return rb;
     char* w = (char*)workspace;
     const int nr = p->n_rays, cap = p->capacity;
-    float* d_sigma = bwd_workspace;
-    float* d_feats = d_sigma + cap;
-    float* fws = d_feats + (int64_t)3 * cap + 32;
+    float* const d_sigma = bwd_workspace + B.d_sigma;
+    float* const d_feats = bwd_workspace + B.d_feats;
+    float* const fws = bwd_workspace + B.field;
     hipLaunchKernelGGL((composite_bwd_kernel<0>), dim3(asd_div_up(nr, RAYS_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream, AT(float, sigma), AT(float, t0), AT(float, t1),
                        AT(float, feats), AT(int32_t, koff), AT(int32_t, kept), nr, p->bg, AT(float, weights), AT(float, opacity), AT(float, depth), d_comp_rgb, d_rgb_fg,
                        d_opacity, d_depth, d_z_var, (const float*)nullptr, d_sigma, d_feats, d_bg, p->color_act);

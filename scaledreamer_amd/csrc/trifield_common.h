@@ -1,5 +1,5 @@
-// trifield_common.h — geometry helpers shared by the two evaluations of the tri-plane field (trifield.hip: one thread per sample on the vector
-// pipe; trifield_mfma.hip: tiles of rows on the matrix pipe): contraction to grid_sample coordinates, plane projection, bilinear taps.
+// trifield_common.h — geometry helpers of the tri-plane field (trifield_mfma.hip: tiles of rows on the matrix pipe; trifield_scatter.hip: the
+// scatter into the planes): contraction to grid_sample coordinates, plane projection, bilinear taps.
 #pragma once
 #include "asd_common.h"
 
@@ -22,23 +22,6 @@ __device__ __forceinline__ float tf_bias(const asd_field_cfg& c, float px, float
     if (c.bias_mode == ASD_BIAS_SPHERE) return sqrtf(px * px + py * py + pz * pz) - c.bias_value;
     return c.bias_value;
 }
-// the bilinear setup of one plane for a point in grid_sample coordinates
-struct tf_tap { int off[4]; float w[4]; };
-__device__ __forceinline__ void tf_setup(const tf_geom& g, int plane, float nx, float ny, float nz, tf_tap& t) {
-    float u, v, fx, fy;
-    int x0, y0;
-    tf_plane_uv(nx, ny, nz, plane, u, v);
-    tf_axis(u, g.W, x0, fx); tf_axis(v, g.H, y0, fy);
-#pragma unroll
-    for (int corner = 0; corner < 4; ++corner) {
-        const int dx = corner & 1, dy = corner >> 1;
-        const int x = x0 + dx, y = y0 + dy;
-        const bool ok = x >= 0 && x < g.W && y >= 0 && y < g.H;
-        t.off[corner] = ok ? ((plane * g.H + y) * g.W + x) * 32 : -1;
-        t.w[corner] = ok ? (dx ? fx : 1.f - fx) * (dy ? fy : 1.f - fy) : 0.f;
-    }
-}
-
 // a / d, as a multiplication when d is a power of two (the usual box: +-radius) — both are exact, so the result is the same bit for bit; d is
 // wave-uniform, the branch is scalar (an fp32 division is ten instructions, three of them per point)
 __device__ __forceinline__ float tf_div(float a, float d) {

@@ -324,8 +324,7 @@ _SAMPLED_COMMON = {"radius": 2.0, "normal_type": "finite_difference", "finite_di
 _TRI_GEN = dict(backend="library", inner_dim=64, condition_dim=128, triplane_low_res=32, triplane_high_res=64, triplane_dim=32, num_layers=1, num_heads=4, local_text=True, mlp_ratio=4)
 
 
-@pytest.mark.parametrize("kind", ["voxel", "triplane"])
-def test_fused_sampled_field_matches_the_composed_path(kind, monkeypatch):
+def _fused_vs_composed(kind, output_normal, monkeypatch):
     """`3DConv-net` / `Triplane-transformer-sdf` with lookup + MLP heads + bias + finite differences as ONE kernel each way (asd_voxfield_* /
     asd_trifield_*) against the composed path of the same module (HIP sampler + library heads, itself pinned by the reference goldens above):
     outputs and every gradient - feature volume / planes, all head weights."""
@@ -348,6 +347,8 @@ def test_fused_sampled_field_matches_the_composed_path(kind, monkeypatch):
     assert geo._fcfg is not None
     pts = (torch.rand(2, n, 3, generator=g) * 4.4 - 2.2).cuda()          # some points outside the box: zero padding of the lookup
     gs = {k: torch.randn(2 * n, d, generator=g).cuda() for k, d in (("sdf", 1), ("features", 3), ("normal", 3), ("sdf_grad", 3))}
+    if not output_normal:
+        gs = {k: gs[k] for k in ("sdf", "features")}
 
     def run(fused):
         monkeypatch.setenv("ASD_VOXFIELD", "1" if fused else "0")
@@ -355,7 +356,7 @@ def test_fused_sampled_field_matches_the_composed_path(kind, monkeypatch):
         for p in geo.parameters():
             p.grad = None
         c = cache.clone().cuda().requires_grad_(True)
-        out = geo(pts, c, output_normal=True)
+        out = geo(pts, c, output_normal=output_normal)
         sum((out[k] * gs[k]).sum() for k in gs).backward()
         heads = {k: p.grad.clone() for k, p in geo.named_parameters() if p.grad is not None and ("sdf_network" in k or "feature_network" in k)}
         return {k: out[k].detach() for k in gs}, c.grad, heads
@@ -370,6 +371,18 @@ def test_fused_sampled_field_matches_the_composed_path(kind, monkeypatch):
     assert set(h1) == set(h0) and len(h1) == (4 if kind == "voxel" else 6)
     for k in h0:
         assert rel(h1[k], h0[k]) < 2e-3, k
+
+
+@pytest.mark.parametrize("kind", ["voxel", "triplane"])
+def test_fused_sampled_field_matches_the_composed_path(kind, monkeypatch):
+    _fused_vs_composed(kind, True, monkeypatch)
+
+
+@pytest.mark.parametrize("kind", ["voxel", "triplane"])
+def test_fused_sampled_field_matches_the_composed_path_without_normal(kind, monkeypatch):
+    """output_normal=False: no finite-difference rows — for `3DConv-net` the configuration whose first-layer weight gradients used to sum slabs
+    that no block had written"""
+    _fused_vs_composed(kind, False, monkeypatch)
 
 
 def test_fused_triplane_field_across_backward_chunks_against_float64(monkeypatch):

@@ -69,6 +69,125 @@ def test_render_pass_stays_inside_its_workspace_and_outputs():
     assert torch.isfinite(dgrid).all() and float(dgrid.abs().sum()) > 0
 
 
+# ---- the field backward passes: asd_field_bwd (hash grid: the smoke system's field), asd_voxfield_bwd (16^3 x 32 volume), asd_trifield_bwd (64^2 planes) ----
+_FIELD_CASES = [(kind, wn, None) for kind in ("field", "voxfield", "trifield") for wn in (True, False)] + [("trifield", True, 1000), ("trifield", False, 1000)]
+_FIELD_IDS = [f"{k}-{'normal' if wn else 'plain'}" + (f"-chunk{ch}" if ch else "") for k, wn, ch in _FIELD_CASES]
+
+
+def _sdf_cfg():
+    from scaledreamer_amd import _lib
+
+    f = _lib.FieldCfg()
+    for d in range(3):
+        f.bbox_min[d], f.bbox_max[d] = -2.0, 2.0
+    f.radius, f.bias_mode, f.bias_value = 2.0, _lib.ASD_BIAS_SPHERE, 0.8
+    f.blob_scale, f.blob_std, f.activation = 0.0, 1.0, _lib.ASD_ACT_NONE
+    f.fd_eps, f.n_hidden, f.n_feature_dims, f.field_mode = 0.01, 64, 3, _lib.ASD_FIELD_SDF
+    return f
+
+
+def _field_bwd_case(kind, with_normal):
+    """One backward call of `kind` at 3001 points -> (workspace floats, {gradient output: element count}, call(workspace pointer, {output: pointer})).
+    The forward pass runs here, through ops; the backward entry is called through bare ctypes."""
+    from scaledreamer_amd import _lib, ops
+
+    L, n = _lib.lib(), 3001
+    g = torch.Generator().manual_seed(11)
+    rnd = lambda *sh, scale=1.0: (torch.randn(*sh, generator=g) * scale).cuda()
+    d_out, d_feats = rnd(n), rnd(n, 3)
+    d_normal, d_fdg = (rnd(n, 3), rnd(n, 3)) if with_normal else (None, None)
+    nf = C.c_int64(0)
+    if kind == "field":
+        from scaledreamer_amd.smoke import build_smoke_system
+
+        geo = build_smoke_system(0, 1)[0].geometry
+        meta, cfg = geo._meta, geo._fcfg
+        grid = geo.encoding.encoding.encoding.params.detach()
+        w = [t.detach().contiguous() for t in geo._weights()]
+        pts = ((torch.rand(n, 3, generator=g) * 2 - 1) * float(cfg.radius)).cuda()
+        sigma, _, _, enc = ops.field_fwd(meta, cfg, grid, *w, pts, with_normal)
+        _lib.check(L.asd_field_bwd_workspace(C.byref(cfg), _lib.i32(n), _lib.i32(int(with_normal)), C.byref(nf)))
+        outs = {"grid": grid.numel(), "w1d": 64 * 32, "w2d": 64, "w1f": 64 * 32, "w2f": 3 * 64}
+
+        def call(ws, o):
+            _lib.check(L.asd_field_bwd(C.byref(meta), C.byref(cfg), _lib.ptr(grid), *[_lib.ptr(t) for t in w], _lib.ptr(pts), _lib.ptr(enc), _lib.ptr(sigma),
+                                       _lib.i32(n), None, _lib.ptr(d_out), _lib.ptr(d_feats), _lib.ptr(d_normal), None, o["grid"], o["w1d"], o["w2d"], o["w1f"],
+                                       o["w2f"], ws, _lib.stream()))
+        return nf.value, outs, call
+    cfg = _sdf_cfg()
+    pts = (torch.rand(n, 3, generator=g) * 4.4 - 2.2).cuda()          # some points outside the box: zero padding of the lookup
+    if kind == "voxfield":
+        vol = rnd(16, 16, 16, 32, scale=0.5)
+        w = [rnd(64, 32, scale=0.2), rnd(1, 64, scale=0.2), rnd(64, 32, scale=0.2), rnd(3, 64, scale=0.2)]
+        sdf, _, _, _, enc = ops.voxfield_fwd(vol, cfg, *w, pts, with_normal)
+        _lib.check(L.asd_voxfield_bwd_workspace(C.byref(cfg), _lib.i32(n), _lib.i32(int(with_normal)), C.byref(nf)))
+        outs = {"voxel": vol.numel(), "dw1_sdf": 64 * 32, "dw2_sdf": 64, "dw1_feature": 64 * 32, "dw2_feature": 3 * 64}
+
+        def call(ws, o):
+            _lib.check(L.asd_voxfield_bwd(_lib.ptr(vol), _lib.i32(16), _lib.i32(16), _lib.i32(16), _lib.i32(32), C.byref(cfg), *[_lib.ptr(t) for t in w],
+                                          _lib.ptr(pts), _lib.ptr(enc), _lib.ptr(sdf), _lib.i32(n), _lib.ptr(d_out), _lib.ptr(d_feats), _lib.ptr(d_normal),
+                                          _lib.ptr(d_fdg), o["voxel"], o["dw1_sdf"], o["dw2_sdf"], o["dw1_feature"], o["dw2_feature"], ws, _lib.stream()))
+        return nf.value, outs, call
+    planes = rnd(3, 64, 64, 32, scale=0.5)
+    shapes = ((96, 64), (64, 64), (1, 64), (96, 64), (64, 64), (3, 64))
+    w6 = [rnd(*sh, scale=0.2) for sh in shapes]
+    sdf = ops.trifield_fwd(planes, cfg, w6, pts, with_normal)[0]
+    _lib.check(L.asd_trifield_bwd_workspace(_lib.i32(64), _lib.i32(64), _lib.i32(n), _lib.i32(int(with_normal)), C.byref(nf)))
+    outs = {"planes": planes.numel(), **{f"dw{j}": sh[0] * sh[1] for j, sh in enumerate(shapes)}}
+
+    def call(ws, o):
+        _lib.check(L.asd_trifield_bwd(_lib.ptr(planes), _lib.i32(64), _lib.i32(64), _lib.i32(32), C.byref(cfg), ops._ptr6(w6), _lib.ptr(pts), _lib.ptr(sdf),
+                                      _lib.i32(n), _lib.ptr(d_out), _lib.ptr(d_feats), _lib.ptr(d_normal), _lib.ptr(d_fdg), o["planes"],
+                                      (C.c_void_p * 6)(*[o[f"dw{j}"].value for j in range(6)]), ws, _lib.stream()))
+    return nf.value, outs, call
+
+
+def _run_field_bwd(case, ws_byte):
+    """the call on a workspace of exactly asd_*_bwd_workspace() floats pre-filled with `ws_byte` and zeroed gradient outputs (the entries accumulate), every
+    buffer inside a sentinel-filled allocation -> ({output: gradient}, all guard bytes intact)"""
+    nf, outs, call = case
+    wbuf, ws = _guarded(nf * 4)
+    ws.fill_(ws_byte)
+    bufs = {k: _guarded(ne * 4) for k, ne in outs.items()}
+    for _, v in bufs.values():
+        v.zero_()
+    call(C.c_void_p(ws.data_ptr()), {k: C.c_void_p(v.data_ptr()) for k, (_, v) in bufs.items()})
+    torch.cuda.synchronize()
+    intact = _intact(wbuf, nf * 4) and all(_intact(b, outs[k] * 4) for k, (b, _) in bufs.items())
+    return {k: v.view(torch.float32).clone() for k, (_, v) in bufs.items()}, intact
+
+
+@pytest.mark.parametrize("kind,with_normal,chunk", _FIELD_CASES, ids=_FIELD_IDS)
+def test_field_backward_passes_stay_inside_their_workspace_and_outputs(kind, with_normal, chunk, monkeypatch):
+    if chunk:
+        monkeypatch.setenv("ASD_TRI_CHUNK", str(chunk))         # 3001 points: four chunks
+    grads, intact = _run_field_bwd(_field_bwd_case(kind, with_normal), 0xA5)
+    assert intact, f"asd_{kind}_bwd wrote outside its workspace or a gradient output"
+    for k, v in grads.items():
+        assert torch.isfinite(v).all() and float(v.abs().sum()) > 0, k
+
+
+@pytest.mark.parametrize("kind,with_normal,chunk", _FIELD_CASES, ids=_FIELD_IDS)
+def test_field_backward_passes_never_read_unwritten_workspace(kind, with_normal, chunk, monkeypatch):
+    """The callers hand these entries a torch.empty workspace.  Pre-filled with 0xFF bytes (a NaN as a float, -1 as an integer) and with zeros, every
+    gradient must be finite and the two runs must agree: to 2e-3 of the largest entry (the bound of test_fused_sampled_field_matches_the_composed_path
+    for head gradients; the scatters and the second-layer sums are fp32 atomics), bit for bit for the voxel entry's first-layer weight gradients
+    (field_wgrad_kernel + slab_reduce_kernel: no atomics)."""
+    if chunk:
+        monkeypatch.setenv("ASD_TRI_CHUNK", str(chunk))
+    case = _field_bwd_case(kind, with_normal)
+    poisoned, ok1 = _run_field_bwd(case, 0xFF)
+    zeroed, ok0 = _run_field_bwd(case, 0x00)
+    assert ok1 and ok0
+    for k in zeroed:
+        assert torch.isfinite(poisoned[k]).all() and torch.isfinite(zeroed[k]).all(), k
+        rel = float((poisoned[k] - zeroed[k]).abs().max() / zeroed[k].abs().max().clamp_min(1e-20))
+        print(f"{kind} {k}: 0xFF-filled vs zero-filled workspace differ by {rel:.2e} of the largest entry")
+        assert rel < 2e-3, k
+        if kind == "voxfield" and k.startswith("dw1_"):
+            assert torch.equal(poisoned[k], zeroed[k]), k
+
+
 def test_conv3d_passes_stay_inside_their_buffers():
     from scaledreamer_amd import _lib
     from scaledreamer_amd import ops

@@ -1,5 +1,5 @@
 """ops.trifield_fwd / trifield_bwd against a float64 restatement, straight at the C ABI (no module around it), plus kernel timings.
-   python tools/tri_mfma_check.py [n] [--bwd]      (ASD_TRI_MFMA=0: the one-thread-per-sample kernels)"""
+   python tools/tri_mfma_check.py [n] [--bwd]"""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch
