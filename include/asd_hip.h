@@ -202,6 +202,52 @@ int asd_triplane_sample_bwd_rows(const float* d_out, int32_t H, int32_t W, int32
 int asd_relayout_f32(const float* x, int32_t batch, int32_t rows, int32_t cols, float* y, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Importance-sampled VolSDF renderer, pass level: everything of `generative-space-volsdf-volume-renderer`
+ * (custom/amortized/models/renderers/generative_space_volsdf_volume_renderer.py:205-430) between the rays and the image that is
+ * not a field, background or hypernetwork call.  Forward: edges, samples, [field sdf], proposal_cdf, edges, asd_merge_sorted,
+ * samples, [field], composite_fwd; backward: composite_bwd.  All tensors are dense [n_rays, S] fp32: every ray holds exactly S
+ * samples (offset = ray * S, count = S), `t_edges` [n_rays, S+1] holds t_start = [:, :-1] and t_end = [:, 1:] and is read in place.
+ * `inv_std_param` is a DEVICE pointer to the one raw float of LearnedVariance._inv_std (neus_volume_renderer.py:31-44), never a host
+ * value: a = clamp(clamp(exp(10 p), 1e-6, 1e6), 0, 80) is formed in every kernel, sigma(s) = a (0.5 + 0.5 sign(s) expm1(-|s| a))
+ * (volsdf_density, neus_volume_renderer.py:19-23).
+ * ---------------------------------------------------------------------------------------------- */
+/* asd_importance_resample (same arguments, same placement convention, bit-identical `s_edges`) and the "uniform" s -> t map
+ * t = s * far + (1 - s) * near in the same launch (estimators.py:72-74,80 + _transform_stot :48-60). */
+int asd_volsdf_edges(const float* vals /*[n_rays,e_in] sorted*/, const float* cdfs /*[n_rays,e_in]*/, int32_t n_rays, int32_t e_in,
+                     int32_t n_out, const float* jitter /*[n_rays] or NULL*/, float near_plane, float far_plane,
+                     float* s_edges /*[n_rays,n_out+1] or NULL*/, float* t_edges /*[n_rays,n_out+1]*/, void* stream);
+/* Per interval, each output optional (NULL: skip): points = o + d * t_mid, t_dirs = d, t_mid = (t0 + t1) / 2, t_len = t1 - t0,
+ * ray_idx = ray (generative_space_volsdf_volume_renderer.py:233-240 for the proposal mid-points, :276-301 for the final samples). */
+int asd_volsdf_samples(const float* rays_o /*[n_rays,3]*/, const float* rays_d /*[n_rays,3]*/, const float* t_edges /*[n_rays,S+1]*/,
+                       int32_t n_rays, int32_t S, float* points /*[n_rays*S,3]*/, float* t_dirs /*[n_rays*S,3]*/, float* t_mid /*[n_rays*S]*/,
+                       float* t_len /*[n_rays*S]*/, int64_t* ray_idx /*[n_rays*S]*/, void* stream);
+/* cdf = asd_transmittance_cdf(t_edges, sigma(sdf)): prop_sigma_fn (generative_space_volsdf_volume_renderer.py:205-260) and
+ * `1 - cat([trans, 0])` (estimators.py:84-86) in one launch.  S <= 2048. */
+int asd_volsdf_proposal_cdf(const float* sdf /*[n_rays,S]*/, const float* t_edges /*[n_rays,S+1]*/, const float* inv_std_param /*[1]*/,
+                            int32_t n_rays, int32_t S, float* cdf /*[n_rays,S+1]*/, void* stream);
+/* One pass per ray (generative_space_volsdf_volume_renderer.py:357-430, get_alpha neus_volume_renderer.py:93-96): alpha_i = |t1 - t0|
+ * sigma(sdf_i), NOT clamped; T_i = prod_{k<i} (1 - alpha_k); weights = T alpha; opacity = sum w; depth = sum w t_mid; rgb_fg = sum w c
+ * with c = features (color_act 0) or sigmoid(features) (color_act 1, as asd_render_params.color_act); z_var = sum w (t_mid - depth)^2;
+ * comp_rgb = rgb_fg + bg (1 - opacity); and, when `normal` is given, comp_normal = (normalize(sum w n, eps 1e-12) + 1) / 2 * opacity
+ * (else `comp_normal` is not touched).  The backward pass forms alpha again: nothing but weights / opacity / depth is kept. */
+int asd_volsdf_composite_fwd(const float* sdf /*[n_rays*S]*/, const float* features /*[n_rays*S,3]*/, int32_t color_act,
+                             const float* normal /*[n_rays*S,3] or NULL*/, const float* t_edges /*[n_rays,S+1]*/,
+                             const float* inv_std_param /*[1]*/, const float* bg /*[n_rays,3]*/, int32_t n_rays, int32_t S,
+                             float* weights /*[n_rays*S]*/, float* opacity /*[n_rays]*/, float* depth /*[n_rays]*/, float* rgb_fg /*[n_rays,3]*/,
+                             float* z_var /*[n_rays]*/, float* comp_rgb /*[n_rays,3]*/, float* comp_normal /*[n_rays,3] or NULL*/, void* stream);
+/* The autograd backward of the pass above.  Upstream gradients: any may be NULL.  comp_normal is differentiable in the opacity only (the
+ * reference detaches the normals), nothing flows to t_edges (detached `dists`, no-grad sampler).  d_sdf, d_features, d_bg (or NULL) are
+ * written (=), not accumulated.  d_inv_std_param [1] (NULL: the variance is frozen) needs `dp_partial`, [n_rays] floats of scratch: one
+ * partial per ray, added in a fixed order by a second small launch — no atomics, the same bits every run. */
+int asd_volsdf_composite_bwd(const float* sdf, const float* features, int32_t color_act, const float* normal /* or NULL */,
+                             const float* t_edges, const float* inv_std_param, const float* bg, int32_t n_rays, int32_t S,
+                             const float* weights, const float* opacity, const float* depth /* forward outputs */,
+                             const float* d_comp_rgb, const float* d_rgb_fg, const float* d_opacity, const float* d_depth,
+                             const float* d_z_var, const float* d_weights, const float* d_comp_normal,
+                             float* d_sdf /*[n_rays*S]*/, float* d_features /*[n_rays*S,3]*/, float* d_bg /*[n_rays,3] or NULL*/,
+                             float* d_inv_std_param /*[1] or NULL*/, float* dp_partial /*[n_rays] or NULL*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Occupancy-grid ray marching (replaces nerfacc.OccGridEstimator.sampling -> CUDA traverse_grids /
  * ray_aabb_intersect / render_visibility_from_density; call site nerf_volume_renderer.py:139-180).
  * Sample placement convention (nerfacc's is unpinned): per ray the samples lie on the

@@ -61,6 +61,7 @@ class ImportanceEstimator(nn.Module):
         super().__init__()
         self.register_buffer("_dev", torch.zeros(0), persistent=False)
         self.jitter_fn: Callable = lambda n, device: torch.rand(n, device=device)
+        self._unit_edges: Optional[torch.Tensor] = None      # the first level's vals = cdfs = [0, 1] per ray (sampling_volsdf)
 
     @property
     def device(self):
@@ -87,3 +88,20 @@ class ImportanceEstimator(nn.Module):
         t_vals_fine = _transform_stot(sampling_type, intervals.vals, near_plane, far_plane)
         t_vals = ops.merge_sorted(t_vals, t_vals_fine)            # sort(cat([t_vals, t_vals_fine]))
         return t_vals[..., :-1], t_vals[..., 1:]
+
+    @torch.no_grad()
+    def sampling_volsdf(self, sdf_fn: Callable, inv_std_param: torch.Tensor, rays_o: torch.Tensor, rays_d: torch.Tensor, prop_samples: int,
+                        num_samples: int, near_plane: float, far_plane: float, stratified: bool = False) -> torch.Tensor:
+        """`sampling` with one VolSDF proposal level, sampling_type "uniform", on the pass-level entries (include/asd_hip.h: asd_volsdf_*): five
+        launches around the proposal field call.  sdf_fn(points [n_rays * prop_samples, 3]) -> the no-grad proposal SDF (n_rays * prop_samples values);
+        inv_std_param: the raw LearnedVariance._inv_std, read on the device.  Returns the merged edges [n_rays, prop_samples + num_samples + 2]:
+        t_starts = [:, :-1], t_ends = [:, 1:].  Same jitter draws, in the same order, as `sampling`."""
+        n_rays, dev = rays_o.shape[0], rays_o.device
+        unit = self._unit_edges
+        if unit is None or unit.shape[0] != n_rays or unit.device != dev:
+            unit = self._unit_edges = torch.tensor([0.0, 1.0], device=dev).repeat(n_rays, 1)
+        s_prop, t_prop = ops.volsdf_edges(unit, unit, prop_samples, self.jitter_fn(n_rays, dev) if stratified else None, near_plane, far_plane)
+        sdf = sdf_fn(ops.volsdf_samples(rays_o, rays_d, t_prop, everything=False))
+        cdfs = ops.volsdf_proposal_cdf(sdf, t_prop, inv_std_param)
+        _, t_fine = ops.volsdf_edges(s_prop, cdfs, num_samples, self.jitter_fn(n_rays, dev) if stratified else None, near_plane, far_plane, want_s=False)
+        return ops.merge_sorted(t_prop, t_fine)

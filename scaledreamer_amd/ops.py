@@ -276,6 +276,80 @@ def merge_sorted(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ---- importance-sampled VolSDF renderer, pass level (include/asd_hip.h: asd_volsdf_*) ---------------------------------
+def volsdf_edges(vals: torch.Tensor, cdfs: torch.Tensor, n_out: int, jitter: Optional[torch.Tensor], near: float, far: float, want_s: bool = True):
+    """importance_resample + the "uniform" s -> t map in one launch -> (s_edges or None, t_edges), both [n_rays, n_out + 1]"""
+    _need_cuda(vals, cdfs)
+    k = _Keep()
+    n_rays, e_in = vals.shape
+    t = torch.empty((n_rays, n_out + 1), device=vals.device, dtype=torch.float32)
+    s = torch.empty_like(t) if want_s else None
+    check(lib().asd_volsdf_edges(k(vals), k(cdfs), i32(n_rays), i32(e_in), i32(n_out), k(jitter), f32(near), f32(far), ptr(s), ptr(t), stream()))
+    return s, t
+
+
+def volsdf_samples(rays_o: torch.Tensor, rays_d: torch.Tensor, t_edges: torch.Tensor, everything: bool = True):
+    """t_edges [n_rays, S + 1] -> points [n, 3] alone (the proposal mid-points), or (points, t_dirs, t_mid [n, 1], t_len [n, 1], ray_idx int64 [n])"""
+    _need_cuda(rays_o, rays_d, t_edges)
+    k = _Keep()
+    n_rays, S = t_edges.shape[0], t_edges.shape[1] - 1
+    n, dev = n_rays * S, t_edges.device
+    points = torch.empty((n, 3), device=dev, dtype=torch.float32)
+    dirs = mid = length = idx = None
+    if everything:
+        dirs = torch.empty((n, 3), device=dev, dtype=torch.float32)
+        mid, length = torch.empty((n, 1), device=dev, dtype=torch.float32), torch.empty((n, 1), device=dev, dtype=torch.float32)
+        idx = torch.empty(n, device=dev, dtype=torch.int64)
+    check(lib().asd_volsdf_samples(k(rays_o), k(rays_d), k(t_edges), i32(n_rays), i32(S), ptr(points), ptr(dirs), ptr(mid), ptr(length), ptr(idx),
+                                   stream()))
+    return (points, dirs, mid, length, idx) if everything else points
+
+
+def volsdf_proposal_cdf(sdf: torch.Tensor, t_edges: torch.Tensor, inv_std_param: torch.Tensor) -> torch.Tensor:
+    """proposal sdf (n_rays * S values, any shape) -> transmittance cdf [n_rays, S + 1] of its VolSDF density"""
+    _need_cuda(sdf, t_edges, inv_std_param)
+    k = _Keep()
+    n_rays, S = t_edges.shape[0], t_edges.shape[1] - 1
+    assert sdf.numel() == n_rays * S
+    cdf = torch.empty((n_rays, S + 1), device=t_edges.device, dtype=torch.float32)
+    check(lib().asd_volsdf_proposal_cdf(k(sdf), k(t_edges), k(inv_std_param), i32(n_rays), i32(S), ptr(cdf), stream()))
+    return cdf
+
+
+def volsdf_composite_fwd(sdf, features, normal, t_edges, inv_std_param, bg, color_act: int):
+    """the whole compositing pass of the VolSDF renderer; `normal` None: no comp_normal"""
+    _need_cuda(sdf, features, t_edges, inv_std_param, bg)
+    k = _Keep()
+    n_rays, S = t_edges.shape[0], t_edges.shape[1] - 1
+    assert sdf.numel() == n_rays * S
+    dev = t_edges.device
+    new = lambda *sh: torch.empty(sh, device=dev, dtype=torch.float32)
+    out = dict(weights=new(n_rays * S), opacity=new(n_rays), depth=new(n_rays), rgb_fg=new(n_rays, 3), z_var=new(n_rays), comp_rgb=new(n_rays, 3),
+               comp_normal=None if normal is None else new(n_rays, 3))
+    check(lib().asd_volsdf_composite_fwd(k(sdf), k(features), i32(color_act), k(normal), k(t_edges), k(inv_std_param), k(bg), i32(n_rays), i32(S),
+                                         ptr(out["weights"]), ptr(out["opacity"]), ptr(out["depth"]), ptr(out["rgb_fg"]), ptr(out["z_var"]),
+                                         ptr(out["comp_rgb"]), ptr(out["comp_normal"]), stream()))
+    return out
+
+
+def volsdf_composite_bwd(sdf, features, normal, t_edges, inv_std_param, bg, color_act: int, fwd, d_comp_rgb=None, d_rgb_fg=None, d_opacity=None,
+                         d_depth=None, d_z_var=None, d_weights=None, d_comp_normal=None, want_bg: bool = True, want_inv_std: bool = False):
+    """-> (d_sdf [n], d_features [n, 3], d_bg [n_rays, 3] or None, d_inv_std_param (shaped like the parameter) or None)"""
+    _need_cuda(sdf, features, t_edges, inv_std_param, bg)
+    k = _Keep()
+    n_rays, S = t_edges.shape[0], t_edges.shape[1] - 1
+    dev = t_edges.device
+    new = lambda *sh: torch.empty(sh, device=dev, dtype=torch.float32)
+    d_sdf, d_feat = new(n_rays * S), new(n_rays * S, 3)
+    d_bg = new(n_rays, 3) if want_bg else None
+    d_p, partial = (torch.empty_like(inv_std_param, dtype=torch.float32), new(n_rays)) if want_inv_std else (None, None)
+    check(lib().asd_volsdf_composite_bwd(k(sdf), k(features), i32(color_act), k(normal), k(t_edges), k(inv_std_param), k(bg), i32(n_rays), i32(S),
+                                         ptr(fwd["weights"]), ptr(fwd["opacity"]), ptr(fwd["depth"]), k(d_comp_rgb), k(d_rgb_fg), k(d_opacity),
+                                         k(d_depth), k(d_z_var), k(d_weights), k(d_comp_normal), ptr(d_sdf), ptr(d_feat), ptr(d_bg), ptr(d_p),
+                                         ptr(partial), stream()))
+    return d_sdf, d_feat, d_bg, d_p
+
+
 def relayout(x: torch.Tensor) -> torch.Tensor:
     """[batch, rows, cols] -> [batch, cols, rows] (fp32)."""
     _need_cuda(x)

@@ -12,9 +12,16 @@ is offset = ray * S, count = S — no bincount, no masks, no dummy samples):
     _composite        ONE fused alpha-compositing pass             (:357-430: render_weight_from_alpha + 4 accumulate_along_rays +
                       (asd_composite_*, mode 2) and a no-grad      comp_normal): weights, opacity, depth, foreground, z-variance
                       second pass for the normal image            and the background blend come out of a single kernel
+
+Two routes through stages 2 and 4 (ASD_VOLSDF, read at every call; "0" = the composed route above, kept as fallback and A/B partner):
+the pass-level entries asd_volsdf_* (include/asd_hip.h) enqueue seven launches forward — edges, samples, proposal_cdf, edges, merge_sorted,
+samples, composite_fwd — and one backward (two with a trainable variance) around the two field calls, with the material's activation, the
+VolSDF density, the normal image and the learned variance (read on the device) inside the kernels.  Eligible: CUDA fp32 rays, use_volsdf,
+a material that is colour = sigmoid | identity (features).  Same output dictionary on both routes.
 """
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 from typing import Any, Dict, Optional, Tuple
 
@@ -22,7 +29,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import nerfacc_api
+from . import nerfacc_api, ops
 from .estimators import ImportanceEstimator
 from .registry import register
 from .renderer import VolumeRenderer
@@ -46,6 +53,32 @@ class LearnedVariance(nn.Module):
 
     def forward(self, x):
         return torch.ones_like(x) * self.inv_std.clamp(1.0e-6, 1.0e6)
+
+
+class _VolSDFCompositeFn(torch.autograd.Function):
+    """The compositing pass of the VolSDF renderer as one node: asd_volsdf_composite_fwd / _bwd (density -> alpha -> weights -> every per-ray
+    image, the normal image included).  Gradients for sdf, features, bg and the raw variance parameter; normals and edges take none."""
+
+    @staticmethod
+    def forward(ctx, sdf, features, bg, inv_std_param, normal, t_edges, color_act):
+        sdf, features, bg, t_edges = sdf.contiguous(), features.contiguous(), bg.contiguous(), t_edges.contiguous()
+        normal = None if normal is None else normal.detach().contiguous()
+        out = ops.volsdf_composite_fwd(sdf, features, normal, t_edges, inv_std_param, bg, color_act)
+        saved = [sdf, features, bg, inv_std_param, t_edges, out["weights"], out["opacity"], out["depth"]] + ([] if normal is None else [normal])
+        ctx.save_for_backward(*saved)
+        ctx.color_act = color_act
+        ctx.set_materialize_grads(False)
+        return out["weights"], out["opacity"], out["depth"], out["rgb_fg"], out["z_var"], out["comp_rgb"], out["comp_normal"]
+
+    @staticmethod
+    def backward(ctx, d_w, d_op, d_dp, d_fg, d_zv, d_comp, d_cn):
+        sdf, features, bg, inv_std_param, t_edges, w, op, dp, *rest = ctx.saved_tensors
+        normal = rest[0] if rest else None
+        d_sdf, d_feat, d_bg, d_p = ops.volsdf_composite_bwd(
+            sdf, features, normal, t_edges, inv_std_param, bg, ctx.color_act, dict(weights=w, opacity=op, depth=dp), d_comp_rgb=d_comp, d_rgb_fg=d_fg,
+            d_opacity=d_op, d_depth=d_dp, d_z_var=d_zv, d_weights=d_w, d_comp_normal=d_cn if normal is not None else None,
+            want_bg=ctx.needs_input_grad[2], want_inv_std=ctx.needs_input_grad[3])
+        return d_sdf.view(sdf.shape), d_feat, d_bg, d_p, None, None, None
 
 
 def _cache_batch(space_cache) -> int:
@@ -128,21 +161,25 @@ class GenerativeSpaceVolSDFVolumeRenderer(VolumeRenderer):
         return space_cache
 
     # ---- stage 2 ----------------------------------------------------------------------------------------------------------------------
+    def _proposal_sdf(self, mid, space_cache) -> torch.Tensor:
+        """the no-grad SDF [n, 1] at the proposal mid-points (any shape [..., 3], ray-major)"""
+        B = _cache_batch(space_cache)
+        with torch.no_grad():
+            fused_sdf = getattr(self.geometry, "_use_fused", None)
+            if fused_sdf is not None and fused_sdf(mid):
+                # the reference evaluates the whole field here and keeps `sdf` (generative_space_volsdf_volume_renderer.py:233-252); the fused
+                # fields have an sdf-only entry (same value: the sdf head does not depend on the feature head)
+                return self.geometry.forward_sdf(mid.reshape(B, -1, 3), space_cache).reshape(-1, 1)
+            return _field_in_chunks(self.geometry, mid.reshape(B, -1, 3), self._chunk(), space_cache=space_cache, output_normal=False)["sdf"]
+
     def _intervals(self, ro, rd, space_cache) -> Tuple[torch.Tensor, torch.Tensor]:
         if not self.cfg.use_volsdf:
             raise ValueError("Currently only VolSDF supports importance sampling.")
-        B = _cache_batch(space_cache)
 
         def proposal_density(t0, t1):      # [n_rays, S] interval edges -> sigma at the mid-points, no gradient
             mid = ro[:, None, :] + rd[:, None, :] * ((t0 + t1) * 0.5)[..., None]
             with torch.no_grad():
-                fused_sdf = getattr(self.geometry, "_use_fused", None)
-                if fused_sdf is not None and fused_sdf(mid):
-                    # the reference evaluates the whole field here and keeps `sdf` (generative_space_volsdf_volume_renderer.py:233-252); the fused
-                    # fields have an sdf-only entry (same value: the sdf head does not depend on the feature head)
-                    sdf = self.geometry.forward_sdf(mid.reshape(B, -1, 3), space_cache).reshape(-1, 1)
-                else:
-                    sdf = _field_in_chunks(self.geometry, mid.reshape(B, -1, 3), self._chunk(), space_cache=space_cache, output_normal=False)["sdf"]
+                sdf = self._proposal_sdf(mid, space_cache)
                 return volsdf_density(sdf, self.variance(sdf)).reshape(t0.shape)
 
         return self.estimator.sampling(prop_sigma_fns=[proposal_density], prop_samples=[self.cfg.num_samples_per_ray_importance],
@@ -158,9 +195,11 @@ class GenerativeSpaceVolSDFVolumeRenderer(VolumeRenderer):
             n, c = positions.shape[0], max(1, self.cfg.eval_chunk_size)
             rgb = torch.cat([self.material(viewdirs=t_dirs[i:i + c], positions=positions[i:i + c], light_positions=t_light[i:i + c],
                                            **{k: v[i:i + c] for k, v in geo.items()}) for i in range(0, n, c)], dim=0)
+        return geo, rgb, self._background(rays_d, text_embed)
+
+    def _background(self, rays_d, text_embed):
         hyper_bg = getattr(self.background, "enabling_hypernet", False)
-        bg = self.background(dirs=rays_d, text_embed=text_embed) if hyper_bg else self.background(dirs=rays_d)
-        return geo, rgb, bg
+        return self.background(dirs=rays_d, text_embed=text_embed) if hyper_bg else self.background(dirs=rays_d)
 
     # ---- stage 4 ----------------------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -177,11 +216,59 @@ class GenerativeSpaceVolSDFVolumeRenderer(VolumeRenderer):
             comp_normal = unit * opacity[:, None]                  # lerp(0, (n + 1) / 2, opacity): differentiable in the opacity only
         return weights, opacity, depth, fg, z_var, comp, comp_normal
 
+    def _outputs(self, vhw, composited, bg, samples, geo) -> Dict[str, torch.Tensor]:
+        """the renderer's output dictionary (generative_space_volsdf_volume_renderer.py:395-446): the images, and while training the per-sample tensors"""
+        weights, opacity, depth, fg, z_var, comp, comp_normal = composited
+        img = lambda x, c: x.reshape(*vhw, c)
+        out = {"comp_rgb": img(comp, 3), "comp_rgb_fg": img(fg, 3), "comp_rgb_bg": img(bg, 3), "opacity": img(opacity, 1),
+               "depth": img(depth, 1), "z_variance": img(z_var, 1)}
+        if comp_normal is not None:
+            out["comp_normal"] = img(comp_normal, 3)
+        if self.training:
+            t_mid, t_len, t_dirs, ray_indices, positions = samples
+            out.update(weights=weights[:, None], t_points=t_mid, t_intervals=t_len, t_dirs=t_dirs, ray_indices=ray_indices, points=positions, **geo)
+            out["inv_std"] = self.variance.inv_std
+        return out
+
+    # ---- the pass-level route ---------------------------------------------------------------------------------------------------------
+    def _color_act(self) -> Optional[int]:
+        """asd_volsdf_composite_*'s color_act when the material is colour = activation(features) with an activation the kernels carry, else None"""
+        mat = self.material
+        if not getattr(mat, "elementwise", False) or getattr(mat.cfg, "n_output_dims", None) != 3:
+            return None
+        name = getattr(mat.cfg, "color_activation", None)
+        name = "none" if name is None else str(name).lower()
+        return {"none": 0, "sigmoid": 1}.get(name)
+
+    def _pass_level(self, rays_o) -> bool:
+        return (os.environ.get("ASD_VOLSDF", "1") != "0" and rays_o.is_cuda and rays_o.dtype == torch.float32 and self.cfg.use_volsdf
+                and self._color_act() is not None)
+
+    def _render_pass_level(self, rays_o, rays_d, bg_color, space_cache, text_embed) -> Dict[str, torch.Tensor]:
+        V, H, W = rays_o.shape[:3]
+        ro, rd = rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous().float()
+        n_rays = ro.shape[0]
+        p = self.variance._inv_std
+        t_edges = self.estimator.sampling_volsdf(lambda mid: self._proposal_sdf(mid, space_cache), p.detach(), ro, rd,
+                                                 self.cfg.num_samples_per_ray_importance, self.cfg.num_samples_per_ray, self.cfg.near_plane,
+                                                 self.cfg.far_plane, stratified=self.randomized)
+        positions, t_dirs, t_mid, t_len, ray_indices = ops.volsdf_samples(ro, rd, t_edges)
+        geo = _field_in_chunks(self.geometry, positions.reshape(V, -1, 3), self._chunk(), space_cache=space_cache, output_normal=True)
+        bg = self._background(rays_d, text_embed)
+        blend = bg if bg_color is None else bg_color
+        if blend.dim() == 2 and blend.shape[0] == V:                      # one colour per view
+            blend = blend[:, None, None, :].expand(-1, H, W, -1)
+        weights, opacity, depth, fg, z_var, comp, comp_normal = _VolSDFCompositeFn.apply(
+            geo["sdf"], geo["features"], blend.reshape(n_rays, -1).float(), p, geo.get("normal"), t_edges, self._color_act())
+        return self._outputs((V, H, W), (weights, opacity, depth, fg, z_var, comp, comp_normal), bg, (t_mid, t_len, t_dirs, ray_indices, positions), geo)
+
     # ---- one set of views with one cache entry per view -------------------------------------------------------------------------------
     def _render(self, rays_o, rays_d, light_positions, bg_color, space_cache, text_embed, extra) -> Dict[str, torch.Tensor]:
         V, H, W = rays_o.shape[:3]
         if torch.is_tensor(space_cache) and space_cache.shape[0] != V:
             raise AssertionError("space_cache must have the same batch size as rays_o")
+        if self._pass_level(rays_o):
+            return self._render_pass_level(rays_o, rays_d, bg_color, space_cache, text_embed)
         ro, rd = rays_o.reshape(-1, 3).contiguous().float(), rays_d.reshape(-1, 3).contiguous().float()
         n_rays = ro.shape[0]
         t0, t1 = self._intervals(ro, rd, space_cache)                     # [n_rays, S]
@@ -199,15 +286,7 @@ class GenerativeSpaceVolSDFVolumeRenderer(VolumeRenderer):
             blend = blend[:, None, None, :].expand(-1, H, W, -1)
         weights, opacity, depth, fg, z_var, comp, comp_normal = self._composite(
             alpha, rgb, blend.reshape(n_rays, -1).float(), t0f, t1f, geo.get("normal"), n_rays, S)
-        img = lambda x, c: x.reshape(V, H, W, c)
-        out = {"comp_rgb": img(comp, 3), "comp_rgb_fg": img(fg, 3), "comp_rgb_bg": img(bg, 3), "opacity": img(opacity, 1),
-               "depth": img(depth, 1), "z_variance": img(z_var, 1)}
-        if comp_normal is not None:
-            out["comp_normal"] = img(comp_normal, 3)
-        if self.training:
-            out.update(weights=weights[:, None], t_points=t_mid, t_intervals=t_len, t_dirs=t_dirs, ray_indices=ray_indices, points=positions, **geo)
-            out["inv_std"] = self.variance.inv_std
-        return out
+        return self._outputs((V, H, W), (weights, opacity, depth, fg, z_var, comp, comp_normal), bg, (t_mid, t_len, t_dirs, ray_indices, positions), geo)
 
     def forward(self, rays_o, rays_d, light_positions, bg_color=None, noise=None, space_cache=None, text_embed=None, **kwargs):
         V = rays_o.shape[0]
