@@ -392,8 +392,8 @@ typedef struct asd_gemm_args {
     const void* zero_page;  /* >= 16 B of zeros: source of out-of-range rows / taps */
     int32_t split_k;        /* >= 1; > 1 needs workspace[split_k, M, N] fp32 */
     float*  workspace;
-    int32_t tile_cfg;       /* 0: tile chosen by the built-in cost model; 1 + i: tile configuration i (see asd_gemm_force_tile),
-                               as found by the caller's autotuner (scaledreamer_amd/diffusion/hip_ops.py) */
+    int32_t tile_cfg;       /* 0: tile chosen by the built-in cost model; 1 + i: tile configuration i (asd_gemm_tile_info(i)),
+                               as found by the autotuner (asd_gemm_tune) */
     int32_t ld_row_bias;    /* row stride (halfs) of row_bias; 0 = N.  Lets a column slice of a wider matrix be used in place
                                (the UNet keeps every ResBlock's time-embedding projection in one [B, sum Cout] matrix) */
     int32_t group_m, group_n; /* block order: workgroups of one XCD walk group_m x group_n super-tiles so that they share operand
@@ -449,10 +449,14 @@ int32_t asd_gemm_gn_records(const asd_gemm_args* args);
 /* 1 when asd_gemm_f16(args) with args->gn_apply set will write args->gn_apply_y itself under the current plan (pointers may be null) */
 int32_t asd_gemm_gn_applies(const asd_gemm_args* args);
 int asd_gemm_f16(const asd_gemm_args* args, void* stream);
-/* Tuning hook (tools/gemm_sweep.py): force tile configuration `cfg` (index into the table of csrc/gemm.hip: 128x64, 128x128,
- * 256x64, 256x128, 128x320, 256x256, 256x320, 320x128, and for 3x3 stride-1 convolutions the LDS-window kernel with
- * 16x16-pixel patches x 64 / x 128 channels) for all following asd_gemm_f16 calls; -1 restores the cost model. */
+/* Tuning hook (tools/gemm_sweep.py): force tile configuration `cfg` (0-based row of the table asd_gemm_tile_info reads) for all
+ * following asd_gemm_f16 calls; -1 restores the cost model. */
 int asd_gemm_force_tile(int32_t cfg);
+/* The tile configurations, one table in csrc/gemm.hip: row i -> out7 = {kind, bm, bn, wm, wn, stages, k-groups}; rows 0 .. n - 1 give
+ * ASD_OK, every other i an error status (host only, no device needed).  kind: the plain MFMA GEMM / implicit-GEMM convolution, the
+ * LDS-window 3x3 convolution with one or two blocks per CU, its ping-pong form, the weight-streaming 3x3 convolution of 8x8 images. */
+enum { ASD_TILE_PLAIN = 0, ASD_TILE_WIN = 1, ASD_TILE_WIN2 = 2, ASD_TILE_PP = 3, ASD_TILE_WS = 4 };
+int asd_gemm_tile_info(int32_t i, int32_t* out7);
 
 #define ASD_GN_STATS_FLOATS(batch) (64 * (batch) + 64 * (512 + (batch)))
 /* GroupNorm(32 groups) [+ SiLU] on NHWC fp16 with fp32 statistics (GroupNorm32, diffusionmodules/util.py:229-231);

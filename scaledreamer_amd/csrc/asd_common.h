@@ -35,8 +35,8 @@ struct asd_ws_cursor {
     int64_t take(int64_t floats) { const int64_t at = o; o += (floats + 63) & ~(int64_t)63; return at; }
 };
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) must be issued once per kernel AND device (a process may drive several GPUs): one bit
-// per device in a per-call-site mask; the call is idempotent, so two threads racing here both set it and nothing is lost
+// The limit on a kernel's dynamic LDS must be raised once per kernel AND device (a process may drive several GPUs): one bit
+// per device in a per-kernel mask (asd_launch_lds); the call is idempotent, so two threads racing here both set it and nothing is lost
 #include <atomic>
 static inline bool asd_attr_needed(std::atomic<unsigned long long>& mask) {
     int dev = 0;
@@ -46,6 +46,17 @@ static inline bool asd_attr_needed(std::atomic<unsigned long long>& mask) {
     mask.fetch_or(bit, std::memory_order_relaxed);
     return true;
 }
+
+#ifdef __HIPCC__
+// Launch of a kernel with dynamic LDS (beyond the 64 KB a launch gets unasked).  The attribute is set to `lds`, or to MAX_LDS for a
+// kernel whose launches differ in size, at the first launch of K on each device: the mask is one per kernel, whatever the call site.
+template <auto K, int MAX_LDS = 0, typename... Args>
+static inline void asd_launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args&... args) {
+    static std::atomic<unsigned long long> devmask{0};
+    if (asd_attr_needed(devmask)) (void)hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS ? MAX_LDS : (int)lds);
+    hipLaunchKernelGGL(K, grid, block, lds, s, args...);
+}
+#endif
 
 // Memory-bound grid sizing (guide G11): cap at 256 CUs x 8 blocks and grid-stride the rest.
 static inline int asd_grid_for(int64_t n, int block) {

@@ -896,19 +896,10 @@ static int c3_run(int D, int H, int W, int cin, int cout, const float* x, const 
     k.group_m = 32 / k.group_n;
     const int blocks = 8 * asd_div_up(tiles_m * tiles_n, 8);
     const size_t lds = (size_t)4 * 18 * 24 * 64 + (size_t)6 * bn * 64;
-    if (tn == 4) {
-        static std::atomic<unsigned long long> attr_devmask{0}; bool attr = !asd_attr_needed(attr_devmask);
-        if (!attr) { (void)hipFuncSetAttribute((const void*)conv3d_pp_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-        ASD_PROBE_START(s);
-        hipLaunchKernelGGL((conv3d_pp_kernel<4>), dim3(blocks), dim3(512), lds, s, k);
-        ASD_PROBE_STOP(s);
-    } else {
-        static std::atomic<unsigned long long> attr_devmask{0}; bool attr = !asd_attr_needed(attr_devmask);
-        if (!attr) { (void)hipFuncSetAttribute((const void*)conv3d_pp_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-        ASD_PROBE_START(s);
-        hipLaunchKernelGGL((conv3d_pp_kernel<2>), dim3(blocks), dim3(512), lds, s, k);
-        ASD_PROBE_STOP(s);
-    }
+    ASD_PROBE_START(s);
+    if (tn == 4) asd_launch_lds<conv3d_pp_kernel<4>>(dim3(blocks), dim3(512), lds, s, k);
+    else asd_launch_lds<conv3d_pp_kernel<2>>(dim3(blocks), dim3(512), lds, s, k);
+    ASD_PROBE_STOP(s);
     return ASD_OK;
 }
 
@@ -989,13 +980,13 @@ int asd_conv3d_wgrad(const asd_conv3d_desc* d, const float* x, const float* dy, 
         a.W = yh;
         // launch 1: X_hi . [dY_hi | dY_lo]
         static const int tile_env = getenv("ASD_C3_WGRAD_TILE") ? atoi(getenv("ASD_C3_WGRAD_TILE")) : 0;       // A/B hook (tools): 1-based tile configuration
-        a.A = xh; a.N = 2 * N; a.ldc = 2 * N; a.split_k = split1; a.workspace = slabs; a.tile_cfg = tile_env ? tile_env : 8;      // 320 x 128 (6 Cout % 128 == 0): 4.24 vs 4.49 ms with 128 x 128 on 64 -> 64 @128^3 (tools/c3_wgrad_ab.py)
+        a.A = xh; a.N = 2 * N; a.ldc = 2 * N; a.split_k = split1; a.workspace = slabs; a.tile_cfg = tile_env ? tile_env : ASD_CFG_320x128 + 1;      // 320 x 128 (6 Cout % 128 == 0): 4.24 vs 4.49 ms with 128 x 128 on 64 -> 64 @128^3 (tools/c3_wgrad_ab.py)
         ASD_PROBE_START(s);
         int rc = asd_gemm_f16(&a, stream);
         ASD_PROBE_STOP(s);
         if (rc != ASD_OK) return rc;
         // launch 2: X_lo . dY_hi
-        a.A = xl; a.N = N; a.ldc = N; a.split_k = split2; a.workspace = slabs2; a.tile_cfg = N % 128 == 0 ? 2 : 1;
+        a.A = xl; a.N = N; a.ldc = N; a.split_k = split2; a.workspace = slabs2; a.tile_cfg = (N % 128 == 0 ? ASD_CFG_128x128 : ASD_CFG_128x64) + 1;
         rc = asd_gemm_f16(&a, stream);
         if (rc != ASD_OK) return rc;
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(asd_div_up((size_t)M * N, 256)), dim3(256), 0, s, slabs, split1, slabs2, split2, Cin, Cout, ax, ay,

@@ -1054,53 +1054,134 @@ static void asd_launch_splitk_epilogue(const asd_gemm_args* a, hipStream_t s) {
 
 
 // ---- tile configurations -------------------------------------------------------------------------------------------
-struct asd_gemm_tile { int bm, bn, wm, wn, nst, kg; };   // nst: stages of the operand ring (0 = the default two); kg: k-groups (0 = one)
-#define ASD_GEMM_NCFG 29
-#define ASD_GEMM_WIN0 8   // configurations >= this are the LDS-window 3x3 convolution (16x16-pixel patch x BN): 8, 9 one block per
-                          // CU (double-buffered window, pipelined loop), 10, 11 two blocks per CU (conv3x3_win2_kernel)
-#define ASD_GEMM_PP0 20   // configurations 20-24: the ping-pong window convolution of gemm_pp.hip (eight waves, two per SIMD staggered by a
-                          // barrier; one block per CU): (4 TM x 16) pixels x (32 TN) channels
-static const asd_gemm_tile asd_gemm_tiles[ASD_GEMM_NCFG] = {
-    {128, 64, 2, 2}, {128, 128, 2, 2}, {256, 64, 4, 2}, {256, 128, 4, 2}, {128, 320, 2, 4}, {256, 256, 2, 4}, {256, 320, 2, 4},
-    {320, 128, 5, 2}, {256, 64, 4, 2}, {256, 128, 4, 2}, {256, 64, 4, 2}, {256, 128, 4, 2},
-    {64, 64, 2, 2},    // 12: small tile, 32 KB LDS: five blocks per CU for the latency-bound K <= 1280 linears
-    {256, 64, 4, 1}, {256, 128, 4, 1},    // 13, 14: window convolution, two blocks per CU, FOUR waves with 64 px x BN wave tiles
+// ONE table: a row is the kind, the numbers and the launcher instantiated FROM those numbers (ASD_TILE), so the geometry a launch
+// computes and the kernel it starts cannot differ.  Dispatch, tuner, cost model and asd_gemm_tile_info (Python, tools) read the rows;
+// the 1-based tile_cfg of the plans (gemm_plans.json) is the row index + 1, so rows are appended, never moved.
+struct asd_gemm_tile {
+    int kind;                  // ASD_TILE_*
+    int bm, bn, wm, wn;        // block tile (rows x channels) and its wm x wn waves: a block has wm * wn * kg * 64 threads in every kind
+    int nst, kg;               // stages of the operand ring and k-groups of the plain kernel (2, 1 in the other kinds)
+    int (*launch)(asd_gemm_args* a, hipStream_t s);     // group_m / group_n, grid, LDS size and launch of a validated problem
+};
+
+// super-tile of the block order (asd_grouped_tile): about one XCD's worth of concurrent blocks, near-square in bytes
+static void asd_pick_group(int tiles_m, int tiles_n, int bm, int bn, size_t lds, int* gm, int* gn) {
+    const int conc = 32 * (2 * lds <= 160 * 1024 ? 2 : 1);      // blocks an XCD (32 CUs) runs at a time
+    int m = (int)lroundf(sqrtf((float)conc * (float)bn / (float)bm));
+    m = m < 1 ? 1 : (m > tiles_m ? tiles_m : m);
+    int n = conc / m;
+    n = n < 1 ? 1 : (n > tiles_n ? tiles_n : n);
+    if (n == tiles_n) { m = conc / n; m = m < 1 ? 1 : (m > tiles_m ? tiles_m : m); }
+    *gm = m; *gn = n;
+}
+
+template <int BM, int BN, int WM, int WN, int NST, int KG>
+static int asd_launch_plain(asd_gemm_args* a, hipStream_t s) {
+    const int tiles = (a->conv && a->upsample == 3 ? 4 * asd_div_up(a->M / 4, BM) : asd_div_up(a->M, BM)) * asd_div_up(a->N, BN);
+    const size_t lds = (size_t)NST * KG * (BM + BN) * 128;
+    if (a->group_m < 1 || a->group_n < 1) asd_pick_group(asd_div_up(a->M, BM), asd_div_up(a->N, BN), BM, BN, lds, &a->group_m, &a->group_n);
+    const dim3 grid(8 * asd_div_up(tiles * a->split_k, 8)), block(WM * WN * KG * 64);   // asd_xcd_item
+    if (a->conv) asd_launch_lds<gemm_f16_kernel<BM, BN, WM, WN, true, NST, KG, false>>(grid, block, lds, s, *a);
+    else if (a->ln_mode == 1) asd_launch_lds<gemm_f16_kernel<BM, BN, WM, WN, false, NST, KG, true>>(grid, block, lds, s, *a);
+    else asd_launch_lds<gemm_f16_kernel<BM, BN, WM, WN, false, NST, KG, false>>(grid, block, lds, s, *a);
+    return ASD_OK;
+}
+
+// LDS-window 3x3 convolution, 16x16-pixel patch x BN, NW waves.  One block per CU (conv3x3_win_kernel: double-buffered window, pipelined
+// loop), or TWO (conv3x3_win2_kernel: single window buffer, two weight slots)
+template <bool TWO, int BN, int NW>
+static int asd_launch_window(asd_gemm_args* a, hipStream_t s) {
+    const size_t lds = (size_t)(TWO ? 1 : 2) * (41 * 1024 + 2 * BN * 128);
+    const int tiles_n = asd_div_up(a->N, BN);
+    if (a->group_m < 1 || a->group_n < 1) asd_pick_group(a->M / 256, tiles_n, 256, BN, TWO ? (size_t)80 * 1024 : lds, &a->group_m, &a->group_n);
+    const dim3 grid(8 * asd_div_up((a->M / 256) * tiles_n * a->split_k, 8)), block(NW * 64);   // asd_xcd_item
+    if constexpr (TWO) asd_launch_lds<conv3x3_win2_kernel<BN, NW>>(grid, block, lds, s, *a);
+    else asd_launch_lds<conv3x3_win_kernel<BN>>(grid, block, lds, s, *a);
+    return ASD_OK;
+}
+
+// ping-pong window convolution of gemm_pp.hip (eight waves, two per SIMD staggered by a barrier; one block per CU):
+// (4 TM x 16) pixels x (32 TN) channels.  The instantiations live there: a row without one does not load.
+size_t asd_conv_pp_lds_bytes(int tm, int tn);
+template <int TM, int TN> void asd_conv_pp_launch(const asd_gemm_args* a, int blocks, hipStream_t s);
+template <int TM, int TN>
+static int asd_launch_pp(asd_gemm_args* a, hipStream_t s) {
+    const int tiles_m = a->M / (64 * TM), tiles_n = a->N / (32 * TN);
+    if (a->group_m < 1 || a->group_n < 1) asd_pick_group(tiles_m, tiles_n, 64 * TM, 32 * TN, asd_conv_pp_lds_bytes(TM, TN), &a->group_m, &a->group_n);
+    asd_conv_pp_launch<TM, TN>(a, 8 * asd_div_up(tiles_m * tiles_n * a->split_k, 8), s);
+    return ASD_OK;
+}
+
+// weight-streaming 3x3 convolution of the 8x8 level (gemm_ws.hip): all <= 320 rows x 64 channels x one channel slice per block
+int asd_conv_ws_launch(const asd_gemm_args* a, hipStream_t s);
+static int asd_launch_ws(asd_gemm_args* a, hipStream_t s) {
+    if (asd_conv_ws_launch(a, s) != ASD_OK) { asd_set_error("weight-streaming convolution: bad image count"); return ASD_ERR_ARG; }
+    return ASD_OK;
+}
+
+// the launcher of a row, instantiated from the row's own numbers; what a kind's kernel fixes is asserted here
+template <int KIND, int BM, int BN, int WM, int WN, int NST, int KG>
+static int asd_tile_launch(asd_gemm_args* a, hipStream_t s) {
+    if constexpr (KIND == ASD_TILE_PLAIN) return asd_launch_plain<BM, BN, WM, WN, NST, KG>(a, s);
+    else {
+        static_assert(NST == 2 && KG == 1, "only the plain kernel has a ring depth and k-groups to choose");
+        if constexpr (KIND == ASD_TILE_WIN) { static_assert(BM == 256 && WM * WN == 8, "window: 256 pixels, eight waves"); return asd_launch_window<false, BN, 8>(a, s); }
+        else if constexpr (KIND == ASD_TILE_WIN2) { static_assert(BM == 256, "window: 256 pixels"); return asd_launch_window<true, BN, WM * WN>(a, s); }
+        else if constexpr (KIND == ASD_TILE_PP) { static_assert(BM % 64 == 0 && BN % 32 == 0 && WM * WN == 8, "ping-pong: eight waves"); return asd_launch_pp<BM / 64, BN / 32>(a, s); }
+        else { static_assert(KIND == ASD_TILE_WS && BM == 320 && BN == 64 && WM * WN == 4, "weight streaming: 5 x 64 rows, four waves"); return asd_launch_ws(a, s); }
+    }
+}
+#define ASD_TILE(KIND, BM, BN, WM, WN, NST, KG) {ASD_TILE_##KIND, BM, BN, WM, WN, NST, KG, &asd_tile_launch<ASD_TILE_##KIND, BM, BN, WM, WN, NST, KG>}
+static constexpr asd_gemm_tile asd_gemm_tiles[] = {
+    // 0-7: the tiles of the cost model (asd_gemm_pick_tile)
+    ASD_TILE(PLAIN, 128, 64, 2, 2, 2, 1), ASD_TILE(PLAIN, 128, 128, 2, 2, 2, 1), ASD_TILE(PLAIN, 256, 64, 4, 2, 2, 1), ASD_TILE(PLAIN, 256, 128, 4, 2, 2, 1),
+    ASD_TILE(PLAIN, 128, 320, 2, 4, 2, 1), ASD_TILE(PLAIN, 256, 256, 2, 4, 2, 1), ASD_TILE(PLAIN, 256, 320, 2, 4, 2, 1), ASD_TILE(PLAIN, 320, 128, 5, 2, 2, 1),
+    // 8-11: window convolution, one block per CU (8, 9) and two (10, 11)
+    ASD_TILE(WIN, 256, 64, 4, 2, 2, 1), ASD_TILE(WIN, 256, 128, 4, 2, 2, 1), ASD_TILE(WIN2, 256, 64, 4, 2, 2, 1), ASD_TILE(WIN2, 256, 128, 4, 2, 2, 1),
+    ASD_TILE(PLAIN, 64, 64, 2, 2, 2, 1),    // 12: small tile, 32 KB LDS: five blocks per CU for the latency-bound K <= 1280 linears
+    ASD_TILE(WIN2, 256, 64, 4, 1, 2, 1), ASD_TILE(WIN2, 256, 128, 4, 1, 2, 1),    // 13, 14: window convolution, two blocks per CU, FOUR waves with 64 px x BN wave tiles
     // 15-19: for launches with few blocks (a block alone on its CU runs one wave per SIMD and has nobody to hide its LDS / barrier /
     // load latencies): 15 = 64x64 with a 4-stage operand ring; 16-19 = intra-block split-K (k-groups sharing the block's barriers):
     // 64x64 x 2 groups, 64x64 x 4 groups, 128x64 x 2, 128x128 x 2
-    {64, 64, 2, 2, 4, 1}, {64, 64, 2, 2, 2, 2}, {64, 64, 2, 2, 2, 4}, {128, 64, 2, 2, 2, 2}, {128, 128, 2, 2, 2, 2},
+    ASD_TILE(PLAIN, 64, 64, 2, 2, 4, 1), ASD_TILE(PLAIN, 64, 64, 2, 2, 2, 2), ASD_TILE(PLAIN, 64, 64, 2, 2, 2, 4), ASD_TILE(PLAIN, 128, 64, 2, 2, 2, 2),
+    ASD_TILE(PLAIN, 128, 128, 2, 2, 2, 2),
     // 20-24: ping-pong window convolution: 32x16 px x 128 ch, 16x16 px x 256 / 320 / 128 / 160 ch
-    {512, 128, 4, 2}, {256, 256, 4, 2}, {256, 320, 4, 2}, {256, 128, 4, 2}, {256, 160, 4, 2},
-    // 25: weight-streaming 3x3 convolution of the 8x8 level (gemm_ws.hip): all <= 320 rows x 64 channels x one channel slice per block
-    {320, 64, 2, 2},
+    ASD_TILE(PP, 512, 128, 4, 2, 2, 1), ASD_TILE(PP, 256, 256, 4, 2, 2, 1), ASD_TILE(PP, 256, 320, 4, 2, 2, 1), ASD_TILE(PP, 256, 128, 4, 2, 2, 1),
+    ASD_TILE(PP, 256, 160, 4, 2, 2, 1),
+    ASD_TILE(WS, 320, 64, 2, 2, 2, 1),      // 25
     // 26-28: deeper operand rings for the one-block-per-CU launches of the 16x16 / 8x8 levels (K >= 1280 linears that take 13 us for 1.7 us
     // of MFMA work: with NST - 1 tiles in flight a k-step costs 1 / (NST - 1) of an L2 / HBM round trip): 128x64 x 6 stages (144 KB),
     // 64x64 x 8 (128 KB), 128x128 x 4 (128 KB)
-    {128, 64, 2, 2, 6, 1}, {64, 64, 2, 2, 8, 1}, {128, 128, 2, 2, 4, 1}};
-#define ASD_GEMM_WS 25
-static int asd_cfg_stages(int cfg) { return asd_gemm_tiles[cfg].nst > 2 ? asd_gemm_tiles[cfg].nst : 2; }
-static int asd_cfg_kgroups(int cfg) { return asd_gemm_tiles[cfg].kg > 1 ? asd_gemm_tiles[cfg].kg : 1; }
-static bool asd_cfg_is_pp(int cfg) { return cfg >= ASD_GEMM_PP0 && cfg < ASD_GEMM_PP0 + 5; }
-static bool asd_cfg_is_window(int cfg) { return (cfg >= ASD_GEMM_WIN0 && cfg < ASD_GEMM_WIN0 + 4) || cfg == 13 || cfg == 14 || asd_cfg_is_pp(cfg); }
-static bool asd_cfg_is_win2(int cfg) { return cfg == ASD_GEMM_WIN0 + 2 || cfg == ASD_GEMM_WIN0 + 3 || cfg == 13 || cfg == 14; }
-static bool asd_cfg_is_ws(int cfg) { return cfg == ASD_GEMM_WS; }
-int asd_conv_ws_launch(const asd_gemm_args* a, hipStream_t s);                                 // gemm_ws.hip
+    ASD_TILE(PLAIN, 128, 64, 2, 2, 6, 1), ASD_TILE(PLAIN, 64, 64, 2, 2, 8, 1), ASD_TILE(PLAIN, 128, 128, 2, 2, 4, 1)};
+#define ASD_GEMM_NCFG ((int)(sizeof(asd_gemm_tiles) / sizeof(asd_gemm_tiles[0])))
+
+// the rows the selection rules name (gemm_tile.h) are the rows they mean
+static constexpr bool asd_cfg_is(int cfg, int kind, int bm, int bn) {
+    return asd_gemm_tiles[cfg].kind == kind && asd_gemm_tiles[cfg].bm == bm && asd_gemm_tiles[cfg].bn == bn;
+}
+static_assert(asd_cfg_is(ASD_CFG_128x64, ASD_TILE_PLAIN, 128, 64) && asd_cfg_is(ASD_CFG_128x128, ASD_TILE_PLAIN, 128, 128) &&
+              asd_cfg_is(ASD_CFG_256x64, ASD_TILE_PLAIN, 256, 64) && asd_cfg_is(ASD_CFG_256x128, ASD_TILE_PLAIN, 256, 128) &&
+              asd_cfg_is(ASD_CFG_256x256, ASD_TILE_PLAIN, 256, 256) && asd_cfg_is(ASD_CFG_320x128, ASD_TILE_PLAIN, 320, 128) &&
+              asd_cfg_is(ASD_CFG_WIN_64, ASD_TILE_WIN, 256, 64) && asd_cfg_is(ASD_CFG_WIN_128, ASD_TILE_WIN, 256, 128) &&
+              asd_cfg_is(ASD_CFG_WIN2_64, ASD_TILE_WIN2, 256, 64) && asd_cfg_is(ASD_CFG_WIN2_128, ASD_TILE_WIN2, 256, 128),
+              "a named tile configuration moved");
+
+static bool asd_cfg_is_plain(int cfg) { return asd_gemm_tiles[cfg].kind == ASD_TILE_PLAIN; }
+static bool asd_cfg_is_pp(int cfg) { return asd_gemm_tiles[cfg].kind == ASD_TILE_PP; }
+static bool asd_cfg_is_ws(int cfg) { return asd_gemm_tiles[cfg].kind == ASD_TILE_WS; }
+static bool asd_cfg_is_window(int cfg) { return !asd_cfg_is_plain(cfg) && !asd_cfg_is_ws(cfg); }      // WIN, WIN2, PP
+static int asd_cfg_wave_n(int cfg) { return asd_gemm_tiles[cfg].bn / asd_gemm_tiles[cfg].wn; }         // columns per wave
 // (split_k resolved) 3x3 stride-1 pad-1 convolution on <= 5 images of 8 x 8 pixels, whole 32-channel chunks per slice, fp32 slabs
 static bool asd_conv_ws_ok(const asd_gemm_args* a) {
     return a->conv && a->stride == 1 && a->pad == 1 && a->upsample == 0 && a->Hin == 8 && a->Win == 8 && a->Hout == 8 && a->Wout == 8 &&
            a->M % 64 == 0 && a->M / 64 <= 5 && a->N % 64 == 0 && a->split_k >= 2 && a->Cin % (32 * a->split_k) == 0 && !a->gn_bwd_x && !a->ln_mode;
 }
-size_t asd_conv_pp_lds_bytes(int variant);                                                    // gemm_pp.hip
-int asd_conv_pp_launch(int variant, const asd_gemm_args* a, int blocks, hipStream_t s);
 
 static bool asd_conv_window_ok(const asd_gemm_args* a) {
     return a->conv && a->stride == 1 && a->pad == 1 && a->upsample == 0 && a->Cin % 64 == 0 && a->Hin == a->Hout &&
            a->Win == a->Wout && a->Hout % 16 == 0 && a->Wout % 16 == 0;
 }
 
-// Load-bound cost model (see the kernel comment): a block spends ~ k_steps * (BM + BN) on its tile loads, the chip runs
-// 256 blocks at a time at full aggregate rate (fewer blocks run up to ~1.5x faster each), padding is wasted work, and
-// every block pays a fixed prologue/epilogue.  Returns the cheapest configuration for the given split.
 // ping-pong window kernel: whole patches (rows of the image divisible by the patch rows), whole N tiles
 static bool asd_conv_pp_ok(const asd_gemm_args* a, int cfg) {   // 32-channel chunks: Cin = 32 (the padded RGB input of the VAE) qualifies too
     return a->conv && a->stride == 1 && a->pad == 1 && a->upsample == 0 && a->Cin % 32 == 0 && a->Hin == a->Hout && a->Win == a->Wout &&
@@ -1108,11 +1189,14 @@ static bool asd_conv_pp_ok(const asd_gemm_args* a, int cfg) {   // 32-channel ch
 }
 static int g_force_tile = -1;   // tuning hook (asd_gemm_force_tile, tools/gemm_sweep.py); -1 = cost model
 
+// Load-bound cost model (see the kernel comment): a block spends ~ k_steps * (BM + BN) on its tile loads, the chip runs
+// 256 blocks at a time at full aggregate rate (fewer blocks run up to ~1.5x faster each), padding is wasted work, and
+// every block pays a fixed prologue/epilogue.  Returns the cheapest configuration for the given split.
 static int asd_gemm_pick_tile(int M, int N, int K, int split) {
     const int ksteps = asd_div_up(asd_div_up(K, 64), split);
     double best = 1e300;
     int best_cfg = 1;
-    for (int c = 0; c < ASD_GEMM_WIN0; ++c) {
+    for (int c = 0; c < ASD_GEMM_NCFG && asd_cfg_is_plain(c); ++c) {      // the plain rows in front of the first window row
         const int bm = asd_gemm_tiles[c].bm, bn = asd_gemm_tiles[c].bn;
         if (bn > 64 && N % bn != 0 && !(bn == 128 && N % 128 == 0)) continue;   // wide tiles only without N padding
         if (bn == 64 && N % 128 == 0) continue;
@@ -1187,13 +1271,15 @@ static int asd_gemm_resolve_cfg(const asd_gemm_args* a) {
     int cfg = asd_gemm_pick_tile(a->M, a->N, a->K, a->split_k);
     // without a tuned plan: the LDS-window kernel wins on every stride-1 3x3 layer with at least 16 patches (tools/gemm_sweep.py)
     if (asd_conv_window_ok(a) && a->M >= 4096 && a->split_k <= a->Cin / 64) {
-        cfg = a->N % 128 == 0 ? 9 : 8;
-        if ((a->M / 256) * asd_div_up(a->N, asd_gemm_tiles[cfg].bn) * a->split_k >= 512) cfg += 2;   // enough blocks for two per CU
+        const bool wide = a->N % 128 == 0;
+        cfg = wide ? ASD_CFG_WIN_128 : ASD_CFG_WIN_64;
+        if ((a->M / 256) * asd_div_up(a->N, asd_gemm_tiles[cfg].bn) * a->split_k >= 512) cfg = wide ? ASD_CFG_WIN2_128 : ASD_CFG_WIN2_64;   // enough blocks for two per CU
     }
-    if (a->act == 2 && (cfg == 4 || cfg == 6)) cfg = a->N % 256 == 0 ? 5 : (a->N % 128 == 0 ? 3 : 2);   // per-wave width % 32
+    if (a->act == 2 && asd_cfg_wave_n(cfg) % 32 != 0)      // GEGLU: per-wave width % 32 (the 320-wide tiles have 80)
+        cfg = a->N % 256 == 0 ? ASD_CFG_256x256 : (a->N % 128 == 0 ? ASD_CFG_256x128 : ASD_CFG_256x64);
     if (a->tile_cfg >= 1 && a->tile_cfg <= ASD_GEMM_NCFG) cfg = a->tile_cfg - 1;
     if (g_force_tile >= 0 && g_force_tile < ASD_GEMM_NCFG) cfg = g_force_tile;
-    if (a->conv && a->upsample == 3 && asd_cfg_is_window(cfg)) cfg = a->N % 128 == 0 ? 1 : 0;
+    if (a->conv && a->upsample == 3 && asd_cfg_is_window(cfg)) cfg = a->N % 128 == 0 ? ASD_CFG_128x128 : ASD_CFG_128x64;
     return cfg;
 }
 
@@ -1208,10 +1294,17 @@ static int asd_gemm_gn_records_cfg(const asd_gemm_args* a, int cfg, bool need_pt
         const int nrec = (a->gn_rows / 64) * (a->N / 64);
         return nrec <= ASD_SPLITK_GN_MAX_RECORDS ? nrec : 0;
     }
-    const int bn = asd_gemm_tiles[cfg].bn, tiles_n = asd_div_up(a->N, bn);
-    if (asd_cfg_is_window(cfg)) return a->gn_rows % asd_gemm_tiles[cfg].bm == 0 ? (a->gn_rows / asd_gemm_tiles[cfg].bm) * tiles_n : 0;   // patches never leave their image
-    const int bm = asd_gemm_tiles[cfg].bm;
-    return a->gn_rows % bm == 0 ? (a->gn_rows / bm) * tiles_n : 0;
+    const int bm = asd_gemm_tiles[cfg].bm, tiles_n = asd_div_up(a->N, asd_gemm_tiles[cfg].bn);
+    return a->gn_rows % bm == 0 ? (a->gn_rows / bm) * tiles_n : 0;      // whole row tiles per image (window patches never leave theirs)
+}
+
+// split_k == 0 ("auto"): the tuned plan of this shape, else cost model + default split; a tile the caller named stays
+static void asd_gemm_resolve_plan(asd_gemm_args* a) {
+    if (a->split_k != 0) return;
+    int32_t t = 0, sk = 1;
+    asd_gemm_plan_get(a, &t, &sk);
+    a->split_k = sk;
+    if (!a->tile_cfg) a->tile_cfg = t;
 }
 
 extern "C" {
@@ -1246,23 +1339,14 @@ int asd_gemm_plan_get(const asd_gemm_args* a, int32_t* tile_cfg, int32_t* split_
 int32_t asd_gemm_gn_records(const asd_gemm_args* a_in) {
     if (!a_in || a_in->M <= 0 || a_in->N <= 0 || a_in->K <= 0) return 0;
     asd_gemm_args a = *a_in;
-    if (a.split_k == 0) {
-        int32_t t = 0, sk = 1;
-        asd_gemm_plan_get(&a, &t, &sk);
-        a.split_k = sk;
-        if (a.tile_cfg == 0) a.tile_cfg = t;
-    }
+    asd_gemm_resolve_plan(&a);
     return asd_gemm_gn_records_cfg(&a, asd_gemm_resolve_cfg(&a), false);
 }
 
 int32_t asd_gemm_gn_applies(const asd_gemm_args* a_in) {
     if (!a_in || a_in->M <= 0 || a_in->N <= 0 || a_in->K <= 0) return 0;
     asd_gemm_args a = *a_in;
-    if (a.split_k == 0) {
-        int32_t t = 0, sk = 1;
-        asd_gemm_plan_get(&a, &t, &sk);
-        a.split_k = sk;
-    }
+    asd_gemm_resolve_plan(&a);
     return asd_gemm_gn_apply_nv(&a) > 0 ? 1 : 0;
 }
 
@@ -1271,22 +1355,13 @@ int asd_gemm_plan_count(void) {
     return (int)g_plans.size();
 }
 
-int64_t asd_gemm_workspace_bytes(const asd_gemm_args* a) {
-    int32_t t = 0, s = 1;
-    if (!a) return 0;
-    if (a->split_k >= 1) s = a->split_k; else asd_gemm_plan_get(a, &t, &s);
-    return s > 1 ? (int64_t)s * a->M * a->N * 4 : 0;
-}
-
-// super-tile of the block order (asd_grouped_tile): about one XCD's worth of concurrent blocks, near-square in bytes
-static void asd_pick_group(int tiles_m, int tiles_n, int bm, int bn, size_t lds, int* gm, int* gn) {
-    const int conc = 32 * (2 * lds <= 160 * 1024 ? 2 : 1);      // blocks an XCD (32 CUs) runs at a time
-    int m = (int)lroundf(sqrtf((float)conc * (float)bn / (float)bm));
-    m = m < 1 ? 1 : (m > tiles_m ? tiles_m : m);
-    int n = conc / m;
-    n = n < 1 ? 1 : (n > tiles_n ? tiles_n : n);
-    if (n == tiles_n) { m = conc / n; m = m < 1 ? 1 : (m > tiles_m ? tiles_m : m); }
-    *gm = m; *gn = n;
+int64_t asd_gemm_workspace_bytes(const asd_gemm_args* a_in) {
+    if (!a_in) return 0;
+    asd_gemm_args a = *a_in;
+    if (a.split_k < 0) a.split_k = 0;       // this entry has always read a negative split as "auto"
+    asd_gemm_resolve_plan(&a);
+    // an upper bound under ln_mode, whose launch drops to split 1 whatever the plan says
+    return a.split_k > 1 ? (int64_t)a.split_k * a.M * a.N * 4 : 0;
 }
 
 int asd_gemm_f16(const asd_gemm_args* a_in, void* stream) {
@@ -1294,12 +1369,7 @@ int asd_gemm_f16(const asd_gemm_args* a_in, void* stream) {
     asd_gemm_args a_copy = *a_in;           // group_m / group_n / ld_row_bias are filled in here when the caller left them 0
     asd_gemm_args* a = &a_copy;
     if (a->ld_row_bias <= 0) a->ld_row_bias = a->N;
-    if (a->split_k == 0) {   // auto: the tuned plan of this shape, else cost model + default split
-        int32_t t = 0, sk = 1;
-        asd_gemm_plan_get(a, &t, &sk);
-        a->split_k = sk;
-        if (a->tile_cfg == 0) a->tile_cfg = t;
-    }
+    asd_gemm_resolve_plan(a);
     ASD_CHECK_ARG(a && a->A && a->W && a->C && a->zero_page, "null argument");
     ASD_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0, "empty problem");
     ASD_CHECK_ARG(a->K % 8 == 0, "K must be a multiple of 8");
@@ -1328,16 +1398,15 @@ int asd_gemm_f16(const asd_gemm_args* a_in, void* stream) {
         if (a->split_k > 1) { a->split_k = 1; a->tile_cfg = 0; }      // the row statistics (mode 1) and the fold itself need the whole K in one block
     }
     int cfg = asd_gemm_resolve_cfg(a);
-    ASD_CHECK_ARG(a->act != 2 || (!asd_cfg_is_window(cfg) && (asd_gemm_tiles[cfg].bn / asd_gemm_tiles[cfg].wn) % 32 == 0),
+    ASD_CHECK_ARG(a->act != 2 || (!asd_cfg_is_window(cfg) && asd_cfg_wave_n(cfg) % 32 == 0),
                   "GEGLU epilogue needs a tile whose per-wave width is a multiple of 32 columns");
     ASD_CHECK_ARG(asd_gemm_tiles[cfg].bn == 64 || a->N % asd_gemm_tiles[cfg].bn == 0 || (asd_gemm_tiles[cfg].bn == 128 && a->N % 4 == 0),
                   "tile configuration does not divide N");
-    const int bm = asd_gemm_tiles[cfg].bm, bn = asd_gemm_tiles[cfg].bn;
     if (asd_gemm_gn_records_cfg(a, cfg, true) == 0) a->gn_partials = nullptr;
     {   // wide-row epilogue (tile_epilogue): whole 32-channel groups per wave, 16-byte aligned rows everywhere
         static const bool wide_on = !(getenv("ASD_WIDE_ROWS") && getenv("ASD_WIDE_ROWS")[0] == '0');     // A/B switch (tools)
         auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-        const int wave_n = bn / asd_gemm_tiles[cfg].wn;
+        const int wave_n = asd_cfg_wave_n(cfg);
         a->wide_rows = wide_on && wave_n % 32 == 0 && a->act != 2 && a->N % 8 == 0 && a->ldc % 8 == 0 && al16(a->C) && (!a->bias || al16(a->bias)) &&
                        (!a->row_bias || (al16(a->row_bias) && a->ld_row_bias % 8 == 0)) && (!a->residual || (al16(a->residual) && a->ldr % 8 == 0)) &&
                        !(a->gn_partials && a->gn_bwd_x);
@@ -1347,119 +1416,17 @@ int asd_gemm_f16(const asd_gemm_args* a_in, void* stream) {
         fprintf(stderr, "ASD_GEMM %d %d %d conv=%d %d %d %d %d %d s=%d p=%d u=%d cfg=%d split=%d act=%d res=%d f32=%d gn=%d\n", a->M, a->N, a->K, a->conv, a->Hin,
                 a->Win, a->Cin, a->Hout, a->Wout, a->stride, a->pad, a->upsample, cfg, a->split_k, a->act, a->residual != nullptr, a->out_f32,
                 a->gn_partials ? (a->gn_bwd_x ? 2 : 1) : 0);
-    if (asd_cfg_is_ws(cfg)) {
+    if (asd_cfg_is_ws(cfg))
         ASD_CHECK_ARG(asd_conv_ws_ok(a), "weight-streaming convolution: 3x3 stride-1 pad-1 on <= 5 images of 8x8, N % 64 == 0, split_k >= 2, Cin % (32 split_k) == 0");
-        hipStream_t sws = (hipStream_t)stream;
-        if (asd_conv_ws_launch(a, sws) != ASD_OK) { asd_set_error("weight-streaming convolution: bad image count"); return ASD_ERR_ARG; }
-        if (!a->partials_only) asd_launch_splitk_epilogue(a, sws);
-        ASD_LAUNCH_CHECK();
-        return ASD_OK;
-    }
     if (asd_cfg_is_window(cfg)) {
         ASD_CHECK_ARG(asd_cfg_is_pp(cfg) ? asd_conv_pp_ok(a, cfg) : asd_conv_window_ok(a),
                       "window convolution needs a 3x3 stride-1 pad-1 conv with Cin % 64 == 0 (ping-pong: % 32) and H, W % 16 == 0");
         ASD_CHECK_ARG(a->split_k == 1 || a->split_k <= a->Cin / 64, "window convolution: split_k exceeds the channel chunks");
-        if (asd_cfg_is_pp(cfg)) {
-            ASD_CHECK_ARG(asd_conv_pp_ok(a, cfg), "ping-pong window convolution: image rows % patch rows == 0 and N % tile == 0");
-            const int tiles_mp = a->M / bm, tiles_np = a->N / bn;
-            if (a->group_m < 1 || a->group_n < 1) asd_pick_group(tiles_mp, tiles_np, bm, bn, asd_conv_pp_lds_bytes(cfg - ASD_GEMM_PP0), &a->group_m, &a->group_n);
-            hipStream_t sp = (hipStream_t)stream;
-            if (asd_conv_pp_launch(cfg - ASD_GEMM_PP0, a, 8 * asd_div_up(tiles_mp * tiles_np * a->split_k, 8), sp) != ASD_OK) { asd_set_error("bad ping-pong variant"); return ASD_ERR_ARG; }
-            if (a->split_k > 1) {
-                asd_launch_splitk_epilogue(a, sp);
-            }
-            ASD_LAUNCH_CHECK();
-            return ASD_OK;
-        }
-        const size_t lds_w = (size_t)2 * 41 * 1024 + (size_t)4 * bn * 128;
-        if (a->group_m < 1 || a->group_n < 1)
-            asd_pick_group(a->M / 256, asd_div_up(a->N, bn), 256, bn, asd_cfg_is_win2(cfg) ? (size_t)80 * 1024 : lds_w, &a->group_m, &a->group_n);
-        const int tiles_w = 8 * asd_div_up((a->M / 256) * asd_div_up(a->N, bn) * a->split_k, 8);   // asd_xcd_item
-        hipStream_t sw = (hipStream_t)stream;
-        if (asd_cfg_is_win2(cfg)) {     // two blocks per CU: single window buffer, two weight slots
-            const size_t lds2 = (size_t)41 * 1024 + (size_t)2 * bn * 128;
-#define WIN2_LAUNCH(BN_, NW_)                                                                                                          \
-    do {                                                                                                                               \
-        static std::atomic<unsigned long long> attr_set_devmask{0}; bool attr_set = !asd_attr_needed(attr_set_devmask);                                                                                                  \
-        if (!attr_set) {                                                                                                               \
-            (void)hipFuncSetAttribute((const void*)conv3x3_win2_kernel<BN_, NW_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2); \
-            attr_set = true;                                                                                                           \
-        }                                                                                                                              \
-        hipLaunchKernelGGL((conv3x3_win2_kernel<BN_, NW_>), dim3(tiles_w), dim3(NW_ * 64), lds2, sw, *a);                              \
-    } while (0)
-            if (cfg == 13) WIN2_LAUNCH(64, 4);
-            else if (cfg == 14) WIN2_LAUNCH(128, 4);
-            else if (bn == 64) WIN2_LAUNCH(64, 8);
-            else WIN2_LAUNCH(128, 8);
-#undef WIN2_LAUNCH
-            if (a->split_k > 1) {
-                asd_launch_splitk_epilogue(a, sw);
-            }
-            ASD_LAUNCH_CHECK();
-            return ASD_OK;
-        }
-        static std::atomic<unsigned long long> attr64_devmask{0}; bool attr64 = !asd_attr_needed(attr64_devmask);static std::atomic<unsigned long long> attr128_devmask{0}; bool attr128 = !asd_attr_needed(attr128_devmask);
-        if (bn == 64) {
-            if (!attr64) { (void)hipFuncSetAttribute((const void*)conv3x3_win_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w); attr64 = true; }
-            hipLaunchKernelGGL((conv3x3_win_kernel<64>), dim3(tiles_w), dim3(512), lds_w, sw, *a);
-        } else {
-            if (!attr128) { (void)hipFuncSetAttribute((const void*)conv3x3_win_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w); attr128 = true; }
-            hipLaunchKernelGGL((conv3x3_win_kernel<128>), dim3(tiles_w), dim3(512), lds_w, sw, *a);
-        }
-        if (a->split_k > 1) {
-            asd_launch_splitk_epilogue(a, sw);
-        }
-        ASD_LAUNCH_CHECK();
-        return ASD_OK;
     }
-    const int tiles = (a->conv && a->upsample == 3 ? 4 * asd_div_up(a->M / 4, bm) : asd_div_up(a->M, bm)) * asd_div_up(a->N, bn);
-    const size_t lds = (size_t)asd_cfg_stages(cfg) * asd_cfg_kgroups(cfg) * (bm + bn) * 128;
-    if (a->group_m < 1 || a->group_n < 1) asd_pick_group(asd_div_up(a->M, bm), asd_div_up(a->N, bn), bm, bn, lds, &a->group_m, &a->group_n);
-    const dim3 grid(8 * asd_div_up(tiles * a->split_k, 8)), block(asd_gemm_tiles[cfg].wm * asd_gemm_tiles[cfg].wn * asd_cfg_kgroups(cfg) * 64);   // asd_xcd_item
     hipStream_t s = (hipStream_t)stream;
-#define GEMM_LAUNCH(BM_, BN_, WM_, WN_, CONV_, NST_, KG_, LN_)                                                           \
-    do {                                                                                                                 \
-        static std::atomic<unsigned long long> attr_set_devmask{0}; bool attr_set = !asd_attr_needed(attr_set_devmask);                                                                                    \
-        if (!attr_set) {                                                                                                 \
-            (void)hipFuncSetAttribute((const void*)gemm_f16_kernel<BM_, BN_, WM_, WN_, CONV_, NST_, KG_, LN_>,           \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, NST_ * KG_ * (BM_ + BN_) * 128);       \
-            attr_set = true;                                                                                             \
-        }                                                                                                                \
-        hipLaunchKernelGGL((gemm_f16_kernel<BM_, BN_, WM_, WN_, CONV_, NST_, KG_, LN_>), grid, block, lds, s, *a);       \
-    } while (0)
-#define GEMM_CASE_N(IDX_, BM_, BN_, WM_, WN_, NST_, KG_)                                                                 \
-    case IDX_:                                                                                                           \
-        if (a->conv) GEMM_LAUNCH(BM_, BN_, WM_, WN_, true, NST_, KG_, false);                                            \
-        else if (a->ln_mode == 1) GEMM_LAUNCH(BM_, BN_, WM_, WN_, false, NST_, KG_, true);                               \
-        else GEMM_LAUNCH(BM_, BN_, WM_, WN_, false, NST_, KG_, false);                                                   \
-        break
-#define GEMM_CASE(IDX_, BM_, BN_, WM_, WN_) GEMM_CASE_N(IDX_, BM_, BN_, WM_, WN_, 2, 1)
-    switch (cfg) {
-        GEMM_CASE(0, 128, 64, 2, 2);
-        GEMM_CASE(1, 128, 128, 2, 2);
-        GEMM_CASE(2, 256, 64, 4, 2);
-        GEMM_CASE(3, 256, 128, 4, 2);
-        GEMM_CASE(4, 128, 320, 2, 4);
-        GEMM_CASE(5, 256, 256, 2, 4);
-        GEMM_CASE(6, 256, 320, 2, 4);
-        GEMM_CASE(7, 320, 128, 5, 2);
-        GEMM_CASE(12, 64, 64, 2, 2);
-        GEMM_CASE_N(15, 64, 64, 2, 2, 4, 1);
-        GEMM_CASE_N(16, 64, 64, 2, 2, 2, 2);
-        GEMM_CASE_N(17, 64, 64, 2, 2, 2, 4);
-        GEMM_CASE_N(18, 128, 64, 2, 2, 2, 2);
-        GEMM_CASE_N(19, 128, 128, 2, 2, 2, 2);
-        GEMM_CASE_N(26, 128, 64, 2, 2, 6, 1);
-        GEMM_CASE_N(27, 64, 64, 2, 2, 8, 1);
-        GEMM_CASE_N(28, 128, 128, 2, 2, 4, 1);
-        default: asd_set_error("bad tile configuration %d", cfg); return ASD_ERR_ARG;
-    }
-#undef GEMM_CASE
-#undef GEMM_CASE_N
-#undef GEMM_LAUNCH
-    if (a->split_k > 1 && !a->partials_only) {
-        asd_launch_splitk_epilogue(a, s);
-    }
+    const int rc = asd_gemm_tiles[cfg].launch(a, s);
+    if (rc != ASD_OK) return rc;
+    if (a->split_k > 1 && !a->partials_only) asd_launch_splitk_epilogue(a, s);      // (the convolution kinds never see partials_only: plain GEMM only)
     ASD_LAUNCH_CHECK();
     return ASD_OK;
 }
@@ -1494,7 +1461,7 @@ static int asd_tune_candidates(const asd_gemm_args* a, int (*out)[2], int max_ou
         if (bn != 64 && a->N % bn != 0) continue;
         const bool few = asd_gemm_tiles[t].nst > 2 || asd_gemm_tiles[t].kg > 1;      // the few-block variants: only where they can win
         if (few && ((a->conv && a->upsample == 2) || (long long)asd_div_up(a->M, bm) * asd_div_up(a->N, bn) > 512 || a->K < 512)) continue;
-        if (geglu && (t == 4 || t == 6)) continue;
+        if (geglu && asd_cfg_wave_n(t) % 32 != 0) continue;
         if (bn == 64 && a->N % 128 == 0 && a->N >= 256 && bm == 128) continue;
         const int tiles = asd_div_up(a->M, bm) * asd_div_up(a->N, bn);
         for (int sk : sk_plain) {
@@ -1592,6 +1559,15 @@ int asd_gemm_plan_entry(int32_t i, int32_t* out11) {
     const asd_plan_key& k = it->first;
     const int32_t v[11] = {k.M, k.N, k.K, k.conv, k.a, k.b, k.c, k.d, k.e, it->second.tile, it->second.split};
     memcpy(out11, v, sizeof(v));
+    return ASD_OK;
+}
+
+/* row i of the tile table -> 7 ints {kind (ASD_TILE_*), bm, bn, wm, wn, stages, k-groups}; an error status past the end */
+int asd_gemm_tile_info(int32_t i, int32_t* out7) {
+    if (i < 0 || i >= ASD_GEMM_NCFG || !out7) return ASD_ERR_ARG;
+    const asd_gemm_tile& t = asd_gemm_tiles[i];
+    const int32_t v[7] = {t.kind, t.bm, t.bn, t.wm, t.wn, t.nst, t.kg};
+    memcpy(out7, v, sizeof(v));
     return ASD_OK;
 }
 

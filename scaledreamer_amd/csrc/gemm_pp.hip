@@ -305,34 +305,15 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(const asd_gemm_args p) 
 #endif
 }
 
-// ---- host side: variants and launch (called by asd_gemm_f16 of gemm.hip) ----------------------------------------------------------
-struct asd_pp_variant { int tm, tn; };
-static const asd_pp_variant asd_pp_variants[] = {{8, 4}, {4, 8}, {4, 10}, {4, 4}, {4, 5}};
+// ---- host side: launch (a row of the tile table of gemm.hip names its instantiation) ------------------------------------------------
+size_t asd_conv_pp_lds_bytes(int tm, int tn) { return (size_t)2 * (4 * tm + 2) * 24 * 64 + (size_t)3 * (2 * tn * 16) * 64; }
 
-size_t asd_conv_pp_lds_bytes(int variant) {
-    const int tm = asd_pp_variants[variant].tm, tn = asd_pp_variants[variant].tn;
-    return (size_t)2 * (4 * tm + 2) * 24 * 64 + (size_t)3 * (2 * tn * 16) * 64;
+template <int TM, int TN>
+void asd_conv_pp_launch(const asd_gemm_args* a, int blocks, hipStream_t s) {
+    asd_launch_lds<conv3x3_pp_kernel<TM, TN>>(dim3(blocks), dim3(512), asd_conv_pp_lds_bytes(TM, TN), s, *a);
 }
-
-int asd_conv_pp_launch(int variant, const asd_gemm_args* a, int blocks, hipStream_t s) {
-    const size_t lds = asd_conv_pp_lds_bytes(variant);
-#define PP_LAUNCH(TM_, TN_)                                                                                                       \
-    do {                                                                                                                          \
-        static std::atomic<unsigned long long> attr_set_devmask{0}; bool attr_set = !asd_attr_needed(attr_set_devmask);                                                                                             \
-        if (!attr_set) {                                                                                                          \
-            (void)hipFuncSetAttribute((const void*)conv3x3_pp_kernel<TM_, TN_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            attr_set = true;                                                                                                      \
-        }                                                                                                                         \
-        hipLaunchKernelGGL((conv3x3_pp_kernel<TM_, TN_>), dim3(blocks), dim3(512), lds, s, *a);                                   \
-    } while (0)
-    switch (variant) {
-        case 0: PP_LAUNCH(8, 4); break;
-        case 1: PP_LAUNCH(4, 8); break;
-        case 2: PP_LAUNCH(4, 10); break;
-        case 3: PP_LAUNCH(4, 4); break;
-        case 4: PP_LAUNCH(4, 5); break;
-        default: return ASD_ERR_ARG;
-    }
-#undef PP_LAUNCH
-    return ASD_OK;
-}
+template void asd_conv_pp_launch<8, 4>(const asd_gemm_args*, int, hipStream_t);
+template void asd_conv_pp_launch<4, 8>(const asd_gemm_args*, int, hipStream_t);
+template void asd_conv_pp_launch<4, 10>(const asd_gemm_args*, int, hipStream_t);
+template void asd_conv_pp_launch<4, 4>(const asd_gemm_args*, int, hipStream_t);
+template void asd_conv_pp_launch<4, 5>(const asd_gemm_args*, int, hipStream_t);

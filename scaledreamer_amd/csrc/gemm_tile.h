@@ -8,6 +8,14 @@ typedef half_t half8 __attribute__((ext_vector_type(8)));
 typedef half_t half4 __attribute__((ext_vector_type(4)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
+// The rows of the tile table (asd_gemm_tiles of gemm.hip, which asserts these names against its rows) that a selection rule names:
+// 0-based, a caller's asd_gemm_args.tile_cfg is the index + 1
+enum {
+    ASD_CFG_128x64 = 0, ASD_CFG_128x128 = 1, ASD_CFG_256x64 = 2, ASD_CFG_256x128 = 3, ASD_CFG_256x256 = 5, ASD_CFG_320x128 = 7,
+    ASD_CFG_WIN_64 = 8, ASD_CFG_WIN_128 = 9,        // window convolution, one block per CU
+    ASD_CFG_WIN2_64 = 10, ASD_CFG_WIN2_128 = 11     // two blocks per CU
+};
+
 #define GLOBAL_AS __attribute__((address_space(1)))
 #define LDS_AS __attribute__((address_space(3)))
 

@@ -221,14 +221,7 @@ size_t asd_conv_ws_lds_bytes(int images) { return (size_t)WS_LDS_BYTES(images); 
 int asd_conv_ws_launch(const asd_gemm_args* a, hipStream_t s) {
     const int images = a->M / 64;
     const dim3 grid((a->N / 64) * a->split_k);
-#define WS_LAUNCH(NB_)                                                                                                             \
-    do {                                                                                                                          \
-        static std::atomic<unsigned long long> attr_set_devmask{0};                                                               \
-        const size_t lds = asd_conv_ws_lds_bytes(NB_);                                                                            \
-        if (asd_attr_needed(attr_set_devmask))                                                                                    \
-            (void)hipFuncSetAttribute((const void*)conv3x3_ws_kernel<NB_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((conv3x3_ws_kernel<NB_>), grid, dim3(256), lds, s, *a);                                                \
-    } while (0)
+#define WS_LAUNCH(NB_) asd_launch_lds<conv3x3_ws_kernel<NB_>>(grid, dim3(256), asd_conv_ws_lds_bytes(NB_), s, *a)
     switch (images) {
         case 1: WS_LAUNCH(1); break;
         case 2: WS_LAUNCH(2); break;

@@ -1116,24 +1116,17 @@ int tfm_prepare(const float* planes_cl, int H, int W, const float* const* w6, fl
 
 int tfm_forward(const tf_geom g, const asd_field_cfg* cfg, const float* planes_cl, const float* const* w6, const float* prep, const float* points, int n, float* sdf,
                 float* features, float* normal, float* fd_grad, hipStream_t s) {
-    static std::atomic<unsigned long long> attr_devmask{0}; bool attr = !asd_attr_needed(attr_devmask);
     const size_t lds = (size_t)2 * TFM_FWD_HALVES * 2;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)tfm_fwd_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)tfm_fwd_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)tfm_fwd_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
     const bool fd = normal || fd_grad;
     const int tiles = asd_div_up(n, fd ? 16 : 64);
     int blocks = asd_div_up(tiles, 4);
     if (blocks > 512) blocks = 512;
     if (fd) {
-        hipLaunchKernelGGL(tfm_fwd_kernel<0>, dim3(blocks), dim3(256), lds, s, g, *cfg, prep + TFM_PREP_FIXED, prep, w6[2], w6[5], points, n, sdf, features, normal, fd_grad);
+        asd_launch_lds<tfm_fwd_kernel<0>>(dim3(blocks), dim3(256), lds, s, g, *cfg, prep + TFM_PREP_FIXED, prep, w6[2], w6[5], points, n, sdf, features, normal, fd_grad);
     } else {
-        hipLaunchKernelGGL(tfm_fwd_kernel<1>, dim3(blocks), dim3(256), lds / 2, s, g, *cfg, prep + TFM_PREP_FIXED, prep, w6[2], w6[5], points, n, sdf, features, normal, fd_grad);
+        asd_launch_lds<tfm_fwd_kernel<1>>(dim3(blocks), dim3(256), lds / 2, s, g, *cfg, prep + TFM_PREP_FIXED, prep, w6[2], w6[5], points, n, sdf, features, normal, fd_grad);
         if (features)
-            hipLaunchKernelGGL(tfm_fwd_kernel<2>, dim3(blocks), dim3(256), lds / 2, s, g, *cfg, prep + TFM_PREP_FIXED, prep, w6[2], w6[5], points, n, sdf, features, normal, fd_grad);
+            asd_launch_lds<tfm_fwd_kernel<2>>(dim3(blocks), dim3(256), lds / 2, s, g, *cfg, prep + TFM_PREP_FIXED, prep, w6[2], w6[5], points, n, sdf, features, normal, fd_grad);
     }
     return ASD_OK;
 }
@@ -1142,18 +1135,8 @@ int tfm_forward(const tf_geom g, const asd_field_cfg* cfg, const float* planes_c
 int tfm_backward_chunk(const tf_geom g, const asd_field_cfg* cfg, const float* planes_cl, const float* const* w6, const float* prep, const float* points,
                        const float* sdf, int i0, int nc, int npt, const float* d_sdf, const float* d_features, const float* d_normal, const float* d_fd_grad,
                        float* denc, float* pts, float* const* dw6, hipStream_t s) {
-    static std::atomic<unsigned long long> attr_devmask{0}; bool attr = !asd_attr_needed(attr_devmask);
     auto ldsd = [](int) { return (size_t)TFM_HEAD_HALVES * 2; };
     auto ldsw = [](int O) { return (size_t)TFM_OFF_A1TH * 2 + 4 * (3 * 4 * 2 * 64 * 16) + 4 * (1 + O) * 64 * sizeof(float) + (size_t)O * TF_H * sizeof(float); };
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)tfm_bwd_weights_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw(1));
-        (void)hipFuncSetAttribute((const void*)tfm_bwd_weights_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw(1));
-        (void)hipFuncSetAttribute((const void*)tfm_bwd_weights_kernel<3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw(3));
-        (void)hipFuncSetAttribute((const void*)tfm_bwd_data_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsd(1));
-        (void)hipFuncSetAttribute((const void*)tfm_bwd_data_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsd(1));
-        (void)hipFuncSetAttribute((const void*)tfm_bwd_data_kernel<3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsd(3));
-        attr = true;
-    }
     tfm_bwd_args a;
     a.g = g; a.c = *cfg; a.planes = prep + TFM_PREP_FIXED; a.prep = prep; a.points = points; a.sdf = sdf; a.i0 = i0; a.n_chunk = nc; a.npt = npt;
     a.d_sdf = d_sdf; a.d_features = d_features; a.d_normal = d_normal; a.d_fd_grad = d_fd_grad; a.denc = denc; a.pts = pts;
@@ -1161,16 +1144,16 @@ int tfm_backward_chunk(const tf_geom g, const asd_field_cfg* cfg, const float* p
     auto gridw = [&](int per_tile) { int b = asd_div_up(asd_div_up(nc, per_tile), 4); return b > 256 ? 256 : b; };
     a.w3 = w6[2]; a.dw1 = dw6[0]; a.dw2 = dw6[1]; a.dw3 = dw6[2];
     if (npt == 4) {
-        hipLaunchKernelGGL((tfm_bwd_data_kernel<1, true>), dim3(grid(16)), dim3(256), ldsd(1), s, a);
-        hipLaunchKernelGGL((tfm_bwd_weights_kernel<1, true>), dim3(gridw(16)), dim3(256), ldsw(1), s, a);
+        asd_launch_lds<tfm_bwd_data_kernel<1, true>>(dim3(grid(16)), dim3(256), ldsd(1), s, a);
+        asd_launch_lds<tfm_bwd_weights_kernel<1, true>>(dim3(gridw(16)), dim3(256), ldsw(1), s, a);
     } else {
-        hipLaunchKernelGGL((tfm_bwd_data_kernel<1, false>), dim3(grid(64)), dim3(256), ldsd(1), s, a);
-        hipLaunchKernelGGL((tfm_bwd_weights_kernel<1, false>), dim3(gridw(64)), dim3(256), ldsw(1), s, a);
+        asd_launch_lds<tfm_bwd_data_kernel<1, false>>(dim3(grid(64)), dim3(256), ldsd(1), s, a);
+        asd_launch_lds<tfm_bwd_weights_kernel<1, false>>(dim3(gridw(64)), dim3(256), ldsw(1), s, a);
     }
     if (d_features) {
         a.w3 = w6[5]; a.dw1 = dw6[3]; a.dw2 = dw6[4]; a.dw3 = dw6[5];
-        hipLaunchKernelGGL((tfm_bwd_data_kernel<3, false>), dim3(grid(64)), dim3(256), ldsd(3), s, a);
-        hipLaunchKernelGGL((tfm_bwd_weights_kernel<3, false>), dim3(gridw(64)), dim3(256), ldsw(3), s, a);
+        asd_launch_lds<tfm_bwd_data_kernel<3, false>>(dim3(grid(64)), dim3(256), ldsd(3), s, a);
+        asd_launch_lds<tfm_bwd_weights_kernel<3, false>>(dim3(gridw(64)), dim3(256), ldsw(3), s, a);
     }
     return ASD_OK;
 }

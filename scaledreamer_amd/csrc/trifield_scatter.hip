@@ -159,7 +159,8 @@ __global__ __launch_bounds__(256) void ts_reduce_kernel(const float* __restrict_
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
 int64_t tfs_work_ints(int rows, int H, int W) { return (int64_t)3 * rows + (int64_t)9 * (H + 1) * (W + 1) + 64; }
-bool tfs_supported(int H, int W) { return (size_t)6 * (H + 1) * (W + 1) * sizeof(int) <= 150 * 1024; }
+#define TS_MAX_LDS (150 * 1024)
+bool tfs_supported(int H, int W) { return (size_t)6 * (H + 1) * (W + 1) * sizeof(int) <= TS_MAX_LDS; }
 
 int tfs_scatter(const float* denc, const float* pts, int R, int H, int W, float* d_planes, int* work, hipStream_t s) {
     const int cells = (H + 1) * (W + 1);
@@ -168,18 +169,12 @@ int tfs_scatter(const float* denc, const float* pts, int R, int H, int W, float*
     int* cursor = off + 3 * cells;
     int* len = cursor + 3 * cells;                  // [3] (+ pad)
     int* sorted = len + 64;                         // [3][R]
-    static std::atomic<unsigned long long> attr_devmask{0}; bool attr = !asd_attr_needed(attr_devmask);
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)ts_hist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        (void)hipFuncSetAttribute((const void*)ts_fill_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        attr = true;
-    }
     (void)hipMemsetAsync(cnt, 0, (size_t)3 * cells * sizeof(int), s);
     int blocks = asd_div_up(R, 2048);
     if (blocks > 512) blocks = 512;
-    hipLaunchKernelGGL(ts_hist_kernel, dim3(blocks), dim3(256), (size_t)3 * cells * sizeof(int), s, pts, R, H, W, cnt);
+    asd_launch_lds<ts_hist_kernel, TS_MAX_LDS>(dim3(blocks), dim3(256), (size_t)3 * cells * sizeof(int), s, pts, R, H, W, cnt);
     hipLaunchKernelGGL(ts_scan_kernel, dim3(3), dim3(1024), 0, s, cnt, cells, off, cursor, len);
-    hipLaunchKernelGGL(ts_fill_kernel, dim3(blocks), dim3(256), (size_t)6 * cells * sizeof(int), s, pts, R, H, W, cursor, sorted);
+    asd_launch_lds<ts_fill_kernel, TS_MAX_LDS>(dim3(blocks), dim3(256), (size_t)6 * cells * sizeof(int), s, pts, R, H, W, cursor, sorted);
     const int waves = 3 * asd_div_up(R, TS_SEG);
     hipLaunchKernelGGL(ts_reduce_kernel, dim3(asd_div_up(waves, 4)), dim3(256), 0, s, denc, pts, sorted, len, R, H, W, d_planes);
     return ASD_OK;

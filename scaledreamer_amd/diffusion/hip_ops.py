@@ -32,12 +32,26 @@ def _p(t: Optional[torch.Tensor]):
 # split_k = 0 uses the recorded plan of the shape, else its cost model.  The winners for the shapes of the shipped configs are
 # committed in gemm_plans.json and pushed into the library when this module is imported; a shape met for the first time is tuned
 # once (a few ms, never under graph capture) unless ASD_GEMM_AUTOTUNE=0.
-TILE_BN = (64, 128, 64, 128, 320, 256, 320, 128, 64, 128, 64, 128, 64, 64, 128, 64, 64, 64, 64, 128, 128, 256, 320, 128, 160, 64, 64, 64, 128)
-TILE_BM = (128, 128, 256, 256, 128, 256, 256, 320, 256, 256, 256, 256, 64, 256, 256, 64, 64, 64, 128, 128, 512, 256, 256, 256, 256, 320, 128, 64, 128)
-WS_TILE = 25                             # weight-streaming 3x3 convolution of the 8x8 level (csrc/gemm_ws.hip): split_k >= 2, Cin % (32 split_k) == 0
-WINDOW_TILES = (8, 9, 10, 11, 13, 14, 20, 21, 22, 23, 24)   # LDS-window 3x3 convolution (16x16-pixel patch x 64 / 128 channels); 10, 11: two blocks per CU; 13, 14: + four-wave form
-PP_TILES = (20, 21, 22, 23, 24)          # ping-pong window convolution (csrc/gemm_pp.hip): whole N tiles, image rows % (TILE_BM / 16) == 0
-# 15: 64x64 with a 4-stage operand ring; 16-19: intra-block split-K (64x64 x 2 / x 4 k-groups, 128x64 x 2, 128x128 x 2) — few-block launches
+# The tile configurations are ONE table in the library (csrc/gemm.hip: asd_gemm_tiles); tile_cfg = index + 1.  Read, not restated:
+
+
+def tile_table():
+    """rows (kind, bm, bn, wm, wn, stages, k-groups) of asd_gemm_tile_info; () without a built library"""
+    if not os.path.exists(L.LIB_PATH):
+        return ()
+    rows, buf = [], (C.c_int32 * 7)()
+    while lib().asd_gemm_tile_info(i32(len(rows)), buf) == 0:
+        rows.append(tuple(buf))
+    return tuple(rows)
+
+
+KIND_PLAIN, KIND_WIN, KIND_WIN2, KIND_PP, KIND_WS = range(5)      # ASD_TILE_* of include/asd_hip.h
+TILES = tile_table()
+TILE_BM = tuple(r[1] for r in TILES)
+TILE_BN = tuple(r[2] for r in TILES)
+WINDOW_TILES = tuple(i for i, r in enumerate(TILES) if r[0] in (KIND_WIN, KIND_WIN2, KIND_PP))   # LDS-window 3x3 convolution (16x16-pixel patches), every form
+PP_TILES = tuple(i for i, r in enumerate(TILES) if r[0] == KIND_PP)     # its ping-pong form (csrc/gemm_pp.hip): whole N tiles, image rows % (TILE_BM / 16) == 0
+WS_TILE = next((i for i, r in enumerate(TILES) if r[0] == KIND_WS), None)   # weight-streaming 3x3 convolution of the 8x8 level (csrc/gemm_ws.hip): split_k >= 2, Cin % (32 split_k) == 0
 AUTOTUNE = os.environ.get("ASD_GEMM_AUTOTUNE", "1") != "0"
 PLAN_FILE = os.environ.get("ASD_GEMM_PLAN_FILE", os.path.join(os.path.dirname(os.path.abspath(__file__)), "gemm_plans.json"))
 TUNE_SCRATCH_BYTES = 512 << 20

@@ -109,3 +109,70 @@ def test_gemm_plan_table_round_trip():
     g.lda = 80                                   # another leading dimension is another shape: defaults, reported as un-tuned
     assert lib().asd_gemm_plan_get(C.byref(g), C.byref(t), C.byref(sk)) == 1 and t.value == 0 and sk.value >= 1
     assert lib().asd_gemm_plan_set(i32(1), i32(1), i32(1), i32(0), i32(0), i32(0), i32(0), i32(0), i32(0), i32(99), i32(1)) != 0
+
+
+def test_gemm_tile_table_is_the_one_python_and_the_plans_use():
+    """asd_gemm_tile_info reads the table the launches dispatch on: the tile names of hip_ops are its rows by kind, a host-side decision
+    that depends on a row's tile (the GroupNorm record count of asd_gemm_gn_records) follows the numbers it reports, and every committed
+    plan names a row whose kind and tile fit the plan's shape, by the conditions asd_gemm_f16 checks before it launches."""
+    import ast
+    import ctypes as C
+    import json
+
+    from scaledreamer_amd._lib import GemmArgs, i32, lib
+    from scaledreamer_amd.diffusion import hip_ops as H
+
+    buf = (C.c_int32 * 7)()
+    rows = []
+    while lib().asd_gemm_tile_info(i32(len(rows)), buf) == 0:
+        rows.append(tuple(buf))
+        assert len(rows) < 1000
+    n = len(rows)
+    assert n >= 1 and lib().asd_gemm_tile_info(i32(-1), buf) != 0 and lib().asd_gemm_tile_info(i32(n), buf) != 0 and lib().asd_gemm_tile_info(i32(n + 7), buf) != 0
+    assert lib().asd_gemm_tile_info(i32(0), None) != 0
+    assert rows == list(H.TILES) and len(H.TILE_BM) == len(H.TILE_BN) == n
+    for i, (kind, bm, bn, wm, wn, nst, kg) in enumerate(rows):
+        assert kind in (H.KIND_PLAIN, H.KIND_WIN, H.KIND_WIN2, H.KIND_PP, H.KIND_WS)
+        assert (i in H.WINDOW_TILES) == (kind in (H.KIND_WIN, H.KIND_WIN2, H.KIND_PP)) and (i in H.PP_TILES) == (kind == H.KIND_PP) and (i == H.WS_TILE) == (kind == H.KIND_WS)
+        assert (H.TILE_BM[i], H.TILE_BN[i]) == (bm, bn) and bm % 64 == 0 and bn % 32 == 0 and wm * wn in (4, 8, 10) and nst >= 2 and kg >= 1
+        assert wm * wn * kg * 64 <= 1024, "threads of a block"
+        if kind == H.KIND_PLAIN:
+            assert nst * kg * (bm + bn) * 128 <= 160 * 1024, "operand ring within the CU's LDS"
+        else:
+            assert (nst, kg) == (2, 1)
+        if kind in (H.KIND_WIN, H.KIND_WIN2):
+            assert bm == 256 and bn in (64, 128)
+        # the launch side reads the same row: one record per (bm x bn) tile of an image, for a 3x3 convolution every kind but WS can run
+        g = GemmArgs()
+        g.N, g.Cin = 640, 64
+        g.M, g.K, g.conv, g.Hin, g.Win, g.Hout, g.Wout, g.stride, g.pad = 2 * 64 * 64, 9 * 64, 1, 64, 64, 64, 64, 1, 1
+        g.split_k, g.tile_cfg, g.gn_cg, g.gn_rows, g.ldc = 1, i + 1, 640 // 32, 64 * 64, 640
+        want = (4096 // bm) * -(-640 // bn) if 4096 % bm == 0 else 0
+        assert lib().asd_gemm_gn_records(C.byref(g)) == want, (i, rows[i])
+    g.tile_cfg = n + 1          # past the end: not a tile, the cost model's choice (window 256 x 128 on this shape)
+    assert lib().asd_gemm_gn_records(C.byref(g)) == 16 * 5
+
+    with open(H.PLAN_FILE if os.path.exists(H.PLAN_FILE) else os.path.join(ROOT, "scaledreamer_amd", "diffusion", "gemm_plans.json")) as f:
+        plans = {ast.literal_eval(k): v for k, v in json.load(f).items()}
+    assert len(plans) >= 100
+    for (M, N, K, tail), (tile, split) in plans.items():
+        assert 1 <= tile <= n and split >= 1, (M, N, K, tail, tile, split)
+        kind, bm, bn, wm, wn, nst, kg = rows[tile - 1]
+        conv = isinstance(tail, tuple)
+        where = f"plan {(M, N, K, tail)} -> tile {tile} split {split}"
+        assert bn == 64 or N % bn == 0 or (bn == 128 and N % 4 == 0), where
+        if kind == H.KIND_PLAIN:
+            if not conv and tail < 0:     # GEGLU epilogue: whole 32-column groups per wave, no split
+                assert (bn // wn) % 32 == 0 and split == 1, where
+            continue
+        assert conv, where + ": a convolution kernel on a linear"
+        hin, cin, stride, ups, pad = tail
+        assert (stride, ups, pad) == (1, 0, 1) and K == 9 * cin, where
+        if kind == H.KIND_WS:
+            assert hin == 8 and M % 64 == 0 and M // 64 <= 5 and N % 64 == 0 and split >= 2 and cin % (32 * split) == 0, where
+            continue
+        assert hin % 16 == 0 and M % (hin * hin) == 0 and (split == 1 or split <= cin // 64), where + ": window kernels split over 64-channel chunks"
+        if kind == H.KIND_PP:
+            assert cin % 32 == 0 and N % bn == 0 and hin % (bm // 16) == 0, where
+        else:
+            assert cin % 64 == 0, where
