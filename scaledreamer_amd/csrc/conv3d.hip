@@ -814,7 +814,6 @@ __global__ __launch_bounds__(256) void modw_bwd_kernel(const float* __restrict__
     }
 }
 
-static inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 static inline int c3_grid(size_t n) { size_t g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }
 
 struct c3_cm_layout { int Hp, Wp; size_t Vp, ld, guard; };
@@ -838,20 +837,38 @@ static int c3_wgrad_split(const asd_conv3d_desc* d, size_t ld, int planes) {
     return split;
 }
 
+// The workspaces, in bytes from their start: asd_conv3d_workspace_bytes returns `total`, the passes take every pointer from here.  Both begin
+// with the two absmax words; every region starts on a 256-byte boundary (the float cursor of asd_common.h, counting bytes).
+struct c3_ws_cursor : asd_ws_cursor { size_t take(size_t bytes) { return (size_t)asd_ws_cursor::take((int64_t)((bytes + 3) / 4)) * 4; } };
+struct c3_run_layout { size_t amax, xh, xl, wh, wl, total; };      // c3_run, one sample at a time: x [vox, cin], w [cout, 27, cin] as hi / lo halfs
+static c3_run_layout c3_run_ws(size_t vox, int cin, int cout) {
+    c3_run_layout L;
+    c3_ws_cursor w;
+    const size_t xs = vox * cin * 2, ws = (size_t)cout * 27 * cin * 2;
+    L.amax = w.take(8); L.xh = w.take(xs); L.xl = w.take(xs); L.wh = w.take(ws); L.wl = w.take(ws);
+    L.total = w.take(0);
+    return L;
+}
+// asd_conv3d_wgrad: four channel-major planes (x, dy as hi / lo), then the split-K slabs of its two GEMM launches ([M, 2N] and [M, N] per split)
+struct c3_wgrad_layout { c3_cm_layout cm; int split1, split2; size_t amax, xh, xl, yh, yl, slabs, slabs2, total; };
+static c3_wgrad_layout c3_wgrad_ws(const asd_conv3d_desc* d) {
+    c3_wgrad_layout L;
+    c3_ws_cursor w;
+    L.cm = c3_cm(d->D, d->H, d->W); L.split1 = c3_wgrad_split(d, L.cm.ld, 2); L.split2 = c3_wgrad_split(d, L.cm.ld, 1);
+    const size_t plane_x = ((size_t)d->Cin * L.cm.ld + 2 * L.cm.guard) * 2, plane_y = ((size_t)d->Cout * L.cm.ld + 2 * L.cm.guard) * 2;
+    const size_t slab = (size_t)9 * d->Cin * 3 * d->Cout * 4;
+    L.amax = w.take(8); L.xh = w.take(plane_x); L.xl = w.take(plane_x); L.yh = w.take(plane_y); L.yl = w.take(plane_y);
+    L.slabs = w.take(((size_t)2 * L.split1 + L.split2) * slab); L.slabs2 = L.slabs + (size_t)2 * L.split1 * slab;
+    L.total = w.take(0);
+    return L;
+}
+
 extern "C" {
 
 int64_t asd_conv3d_workspace_bytes(const asd_conv3d_desc* d, int32_t pass) {
     if (!d) return 0;
-    const size_t vox = (size_t)d->D * d->H * d->W;
-    if (pass == 2) {      // weight gradient: four channel-major planes + slabs + scalars
-        const c3_cm_layout l = c3_cm(d->D, d->H, d->W);
-        const size_t plane_x = ((size_t)d->Cin * l.ld + 2 * l.guard) * 2, plane_y = ((size_t)d->Cout * l.ld + 2 * l.guard) * 2;
-        const size_t slabs = ((size_t)2 * c3_wgrad_split(d, l.ld, 2) + c3_wgrad_split(d, l.ld, 1)) * 9 * d->Cin * 3 * d->Cout * 4;
-        return (int64_t)(256 + 2 * al256(plane_x) + 2 * al256(plane_y) + al256(slabs));
-    }
-    const int cin = pass == 1 ? d->Cout : d->Cin, cout = pass == 1 ? d->Cin : d->Cout;
-    const size_t xs = vox * cin * 2, ws = (size_t)cout * 27 * cin * 2;     // one sample at a time
-    return (int64_t)(256 + 2 * al256(xs) + 2 * al256(ws));
+    if (pass == 2) return (int64_t)c3_wgrad_ws(d).total;
+    return (int64_t)c3_run_ws((size_t)d->D * d->H * d->W, pass == 1 ? d->Cout : d->Cin, pass == 1 ? d->Cin : d->Cout).total;
 }
 
 static int c3_check(const asd_conv3d_desc* d) {
@@ -866,11 +883,9 @@ static int c3_check(const asd_conv3d_desc* d) {
 static int c3_run(int D, int H, int W, int cin, int cout, const float* x, const unsigned* amax_x, const float* w, int transpose_w, float* y,
                   const asd_conv3d_epilogue* ep, size_t noise_off, char* ws, hipStream_t s) {
     const size_t vox = (size_t)D * H * W;
-    unsigned* amax = (unsigned*)ws;                                   // [0] x, [1] w
-    half_t* xh = (half_t*)(ws + 256);
-    half_t* xl = (half_t*)((char*)xh + al256(vox * cin * 2));
-    half_t* wh = (half_t*)((char*)xl + al256(vox * cin * 2));
-    half_t* wl = (half_t*)((char*)wh + al256((size_t)cout * 27 * cin * 2));
+    const c3_run_layout L = c3_run_ws(vox, cin, cout);
+    unsigned* amax = (unsigned*)(ws + L.amax);                        // [0] x, [1] w
+    half_t *xh = (half_t*)(ws + L.xh), *xl = (half_t*)(ws + L.xl), *wh = (half_t*)(ws + L.wh), *wl = (half_t*)(ws + L.wl);
     (void)hipMemsetAsync(amax, 0, 8, s);
     if (!amax_x) {
         hipLaunchKernelGGL(absmax_kernel, dim3(c3_amax_grid(vox * cin / 4)), dim3(256), 0, s, x, vox * cin / 4, amax);
@@ -935,18 +950,14 @@ int asd_conv3d_wgrad(const asd_conv3d_desc* d, const float* x, const float* dy, 
     hipStream_t s = (hipStream_t)stream;
     const int D = d->D, H = d->H, W = d->W, Cin = d->Cin, Cout = d->Cout;
     const size_t vox = (size_t)D * H * W;
-    const c3_cm_layout l = c3_cm(D, H, W);
+    const c3_wgrad_layout L = c3_wgrad_ws(d);
+    const c3_cm_layout l = L.cm;
     ASD_CHECK_ARG(((size_t)(Cin > Cout ? Cin : Cout) * l.ld + 2 * l.guard) * 2 < ((size_t)1 << 31), "a channel-major plane is addressed with 32-bit byte offsets");
     char* base = (char*)ws;
-    unsigned* amax = (unsigned*)base;                                 // [0] x, [1] dy
-    const size_t plane_x = ((size_t)Cin * l.ld + 2 * l.guard) * 2, plane_y = ((size_t)Cout * l.ld + 2 * l.guard) * 2;
-    half_t* xh = (half_t*)(base + 256);
-    half_t* xl = (half_t*)((char*)xh + al256(plane_x));
-    half_t* yh = (half_t*)((char*)xl + al256(plane_x));
-    half_t* yl = (half_t*)((char*)yh + al256(plane_y));
-    float* slabs = (float*)((char*)yl + al256(plane_y));
+    unsigned* amax = (unsigned*)(base + L.amax);                      // [0] x, [1] dy
+    half_t *xh = (half_t*)(base + L.xh), *xl = (half_t*)(base + L.xl), *yh = (half_t*)(base + L.yh), *yl = (half_t*)(base + L.yl);
+    float *slabs = (float*)(base + L.slabs), *slabs2 = (float*)(base + L.slabs2);
     const int M = 9 * Cin, N = 3 * Cout;
-    const int split1 = c3_wgrad_split(d, l.ld, 2), split2 = c3_wgrad_split(d, l.ld, 1);
     ASD_CHECK_ARG((char*)yl - (char*)yh < ((ptrdiff_t)1 << 30), "the two gradient planes must lie within 1 GiB of each other");
     for (int n = 0; n < d->N; ++n) {
         (void)hipMemsetAsync(amax, 0, 8, s);
@@ -975,21 +986,20 @@ int asd_conv3d_wgrad(const asd_conv3d_desc* d, const float* x, const float* dy, 
         for (int t9 = 0; t9 < 9; ++t9) a.a_seg_off[t9] = (int)(((long long)l.guard + (long long)(t9 / 3 - 1) * l.Hp * l.Wp + (long long)(t9 % 3 - 1) * l.Wp) * 2);
         const long long lo_off = (long long)((char*)yl - (char*)yh);
         for (int q = 0; q < 6; ++q) a.w_seg_off[q] = (int)((q / 3) * lo_off + ((long long)l.guard - (q % 3 - 1)) * 2);
-        float* slabs2 = slabs + (size_t)split1 * M * 2 * N;
         a.C = slabs;        // unused (partials_only) but must be non-null
         a.W = yh;
         // launch 1: X_hi . [dY_hi | dY_lo]
         static const int tile_env = getenv("ASD_C3_WGRAD_TILE") ? atoi(getenv("ASD_C3_WGRAD_TILE")) : 0;       // A/B hook (tools): 1-based tile configuration
-        a.A = xh; a.N = 2 * N; a.ldc = 2 * N; a.split_k = split1; a.workspace = slabs; a.tile_cfg = tile_env ? tile_env : ASD_CFG_320x128 + 1;      // 320 x 128 (6 Cout % 128 == 0): 4.24 vs 4.49 ms with 128 x 128 on 64 -> 64 @128^3 (tools/c3_wgrad_ab.py)
+        a.A = xh; a.N = 2 * N; a.ldc = 2 * N; a.split_k = L.split1; a.workspace = slabs; a.tile_cfg = tile_env ? tile_env : ASD_CFG_320x128 + 1;      // 320 x 128 (6 Cout % 128 == 0): 4.24 vs 4.49 ms with 128 x 128 on 64 -> 64 @128^3 (tools/c3_wgrad_ab.py)
         ASD_PROBE_START(s);
         int rc = asd_gemm_f16(&a, stream);
         ASD_PROBE_STOP(s);
         if (rc != ASD_OK) return rc;
         // launch 2: X_lo . dY_hi
-        a.A = xl; a.N = N; a.ldc = N; a.split_k = split2; a.workspace = slabs2; a.tile_cfg = (N % 128 == 0 ? ASD_CFG_128x128 : ASD_CFG_128x64) + 1;
+        a.A = xl; a.N = N; a.ldc = N; a.split_k = L.split2; a.workspace = slabs2; a.tile_cfg = (N % 128 == 0 ? ASD_CFG_128x128 : ASD_CFG_128x64) + 1;
         rc = asd_gemm_f16(&a, stream);
         if (rc != ASD_OK) return rc;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(asd_div_up((size_t)M * N, 256)), dim3(256), 0, s, slabs, split1, slabs2, split2, Cin, Cout, ax, ay,
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(asd_div_up((size_t)M * N, 256)), dim3(256), 0, s, slabs, L.split1, slabs2, L.split2, Cin, Cout, ax, ay,
                            dw + (size_t)n * dw_sample_stride);
     }
     ASD_LAUNCH_CHECK();

@@ -14,6 +14,7 @@
 //
 // Roofline: MFMA for the GEMMs / attention (3 fp16 products per fp32-equivalent multiply-add), HBM for the split / epilogue / LayerNorm
 // passes (4-10 B per element).
+#include <algorithm>
 #include <math.h>
 #include <mutex>
 #include <stdlib.h>
@@ -22,6 +23,7 @@
 #include <hip/hip_fp16.h>
 
 #include "asd_common.h"
+#include "gemm_tile.h"      // ASD_CFG_*: the names of the tile table's rows
 
 namespace {
 
@@ -965,27 +967,53 @@ unsigned* tx_zeroed(unsigned* own, size_t words, hipStream_t s) {
 inline int64_t tx_al(int64_t floats) { return (floats + 63) & ~(int64_t)63; }
 inline int tx_rp(int r) { return (r + 63) & ~63; }      // rows of a transposed operand padded to the GEMM's k-step
 
-// tile configuration (1-based index into csrc/gemm.hip's table) and split-K per product shape, from tools/tritx_gemm_sweep.py on the shipped
-// model's shapes (12 layers x 768 wide x 3072 tokens; profiles/r05_tritx_gemm_sweep.txt); other shapes: cost model, no split
+// tile configuration (asd_gemm_args.tile_cfg: a row of csrc/gemm.hip's table + 1) and split-K per product shape, from tools/tritx_gemm_sweep.py
+// on the shipped model's shapes (12 layers x 768 wide x 3072 tokens; profiles/r05_tritx_gemm_sweep.txt); other shapes: cost model, no split
 struct TxPlan { int M, N, K3, cfg, sk; };
 const TxPlan tx_plans[] = {
-    {3072, 768, 2304, 1, 1}, {3072, 2304, 2304, 4, 1}, {3072, 3072, 2304, 8, 1}, {3072, 768, 9216, 4, 3}, {3072, 768, 6912, 2, 3}, {77, 1536, 3072, 1, 6},
-    {3072, 128, 2304, 1, 4}, {3072, 768, 384, 1, 1}, {768, 768, 9216, 1, 6}, {2304, 768, 9216, 2, 4}, {768, 3072, 9216, 4, 3}, {1536, 1024, 384, 1, 1},
-    {768, 128, 9216, 1, 8},
+    {3072, 768, 2304, ASD_CFG_128x64 + 1, 1}, {3072, 2304, 2304, ASD_CFG_256x128 + 1, 1}, {3072, 3072, 2304, ASD_CFG_320x128 + 1, 1}, {3072, 768, 9216, ASD_CFG_256x128 + 1, 3},
+    {3072, 768, 6912, ASD_CFG_128x128 + 1, 3}, {77, 1536, 3072, ASD_CFG_128x64 + 1, 6}, {3072, 128, 2304, ASD_CFG_128x64 + 1, 4}, {3072, 768, 384, ASD_CFG_128x64 + 1, 1},
+    {768, 768, 9216, ASD_CFG_128x64 + 1, 6}, {2304, 768, 9216, ASD_CFG_128x128 + 1, 4}, {768, 3072, 9216, ASD_CFG_256x128 + 1, 3}, {1536, 1024, 384, ASD_CFG_128x64 + 1, 1},
+    {768, 128, 9216, ASD_CFG_128x64 + 1, 8},
 };
-void tx_plan(int M, int N, int K3, int* cfg, int* sk) {
-    *cfg = 0; *sk = 1;
+TxPlan tx_plan(int M, int N, int K3) {
     for (const TxPlan& p : tx_plans)
-        if (p.M == M && p.N == N && p.K3 == K3) { *cfg = p.cfg; *sk = p.sk; return; }
+        if (p.M == M && p.N == N && p.K3 == K3) return p;
+    return {M, N, K3, 0, 1};
 }
-inline int64_t tx_gemm_ws_floats(int M, int N, int K3) {
-    int cfg, sk;
-    tx_plan(M, N, K3, &cfg, &sk);
-    return sk > 1 ? tx_al((int64_t)sk * M * N) : 0;
+
+// ---- workspace layouts -----------------------------------------------------------------------------------------------------------------
+// One struct per workspace, offsets in floats from its start, every region on a 256-byte boundary (asd_ws_cursor): the size query returns
+// `total`, the pass takes every pointer from the struct.
+inline int64_t tx_plane_floats(int64_t rows, int64_t k) { return rows * 3 * k / 2 + 64; }      // an operand plane [rows, 3 k] of halfs
+// asd_tx_linear: x planes [M, 3K], row scales [M] (a LayerNorm kernel that produced x leaves both here; neither offset depends on N), product
+// [M, N], split-K slabs [sk][M][N] (empty without a split)
+struct TxLinearWs { int64_t planes, inv, c32, slabs, total; };
+TxLinearWs tx_linear_ws(int M, int N, int K) {
+    TxLinearWs L;
+    asd_ws_cursor w;
+    const int sk = tx_plan(M, N, 3 * K).sk;
+    L.planes = w.take(tx_plane_floats(M, K)); L.inv = w.take(M); L.c32 = w.take((int64_t)M * N);
+    L.slabs = w.take(sk > 1 ? (int64_t)sk * M * N : 0);
+    L.total = w.o;
+    return L;
+}
+// asd_tx_linear_wgrad (Mp = tx_rp(M) rows to contract over): dy^T [N, 3 Mp], x^T [K, 3 Mp], their scales [N], [K], the column maxima of dy and of
+// x (from word cmax_x on) as ONE span of cmax_words that tx_zeroed clears or draws from the pool at once, product [N, K], slabs [sk][N][K]
+struct TxWgradWs { int64_t dyt, xt, inv_dy, inv_x, cmax, cmax_x, cmax_words, c32, slabs, total; };
+TxWgradWs tx_wgrad_ws(int M, int N, int K) {
+    TxWgradWs L;
+    asd_ws_cursor w;
+    const int Mp = tx_rp(M), sk = tx_plan(N, K, 3 * Mp).sk;
+    L.dyt = w.take(tx_plane_floats(N, Mp)); L.xt = w.take(tx_plane_floats(K, Mp)); L.inv_dy = w.take(N); L.inv_x = w.take(K);
+    L.cmax_x = tx_al(N); L.cmax_words = L.cmax_x + tx_al(K); L.cmax = w.take(L.cmax_words);
+    L.c32 = w.take((int64_t)N * K); L.slabs = w.take(sk > 1 ? (int64_t)sk * N * K : 0);
+    L.total = w.o;
+    return L;
 }
 
 // planeA [M, 3K] . planeW [N, 3K]^T (fp32 result of the three fp16 products): *res / *nslab tell the epilogue where the result is — c32
-// [M, N] (nslab 1) or the unreduced split-K slabs [nslab][M][N] in `slabs` (tx_gemm_ws_floats(M, N, K3) floats)
+// [M, N] (nslab 1) or the unreduced split-K slabs [nslab][M][N] in `slabs` (the layouts above reserve them where the plan splits)
 int tx_gemm(const h16* pa, const h16* pw, int M, int N, int K3, float* c32, float* slabs, const float** res, int* nslab, hipStream_t s) {
     asd_gemm_args a;
     memset(&a, 0, sizeof(a));
@@ -993,8 +1021,7 @@ int tx_gemm(const h16* pa, const h16* pw, int M, int N, int K3, float* c32, floa
     a.M = M; a.N = N; a.K = K3;
     a.lda = K3; a.ldw = K3; a.ldc = N;
     a.out_f32 = 1;
-    int cfg, sk;
-    tx_plan(M, N, K3, &cfg, &sk);
+    const int cfg = tx_plan(M, N, K3).cfg, sk = tx_plan(M, N, K3).sk;
     a.split_k = sk; a.tile_cfg = cfg; a.workspace = slabs;
     a.partials_only = sk > 1;
     *res = sk > 1 ? slabs : c32;
@@ -1026,46 +1053,35 @@ int asd_tx_pack_weight(const float* w, int32_t N, int32_t K, void* plane_w, floa
     return ASD_OK;
 }
 
-int64_t asd_tx_linear_workspace(int32_t M, int32_t N, int32_t K) {
-    // A plane [M, 3K] halfs + row scales + fp32 product [M, N]
-    return tx_al((int64_t)M * 3 * K / 2 + 64) + tx_al(M) + tx_al((int64_t)M * N) + tx_gemm_ws_floats(M, N, 3 * K);
-}
+int64_t asd_tx_linear_workspace(int32_t M, int32_t N, int32_t K) { return tx_linear_ws(M, N, K).total; }
 
 // y [M, N] (ldy) = f(x [M, K] (ldx) . W^T + bias) + residual, W given as packed plane [N, 3K] + inv_w [N] (asd_tx_pack_weight; pass the
 // W^T plane for an input gradient).  mode 0 identity, 1 GELU (pre-activation saved to aux), 2 multiply by GELU'(aux) (aux [M, N], ld N)
 // planes_ready: the A-operand planes and row scales of x already sit in ws where this function would put them (written by the LayerNorm
-// kernel that produced x: tx_linear_planes_of)
-static int tx_linear_core(const float* x, int32_t M, int32_t K, int32_t ldx, const void* plane_w, const float* inv_w, int32_t N, const float* bias, int32_t mode,
-                          float* aux, const float* residual, int32_t ldr, float* y, int32_t ldy, float* ws, bool planes_ready, void* stream);
-static inline h16* tx_linear_planes_of(float* ws) { return reinterpret_cast<h16*>(ws); }
-static inline float* tx_linear_inv_of(float* ws, int M, int K) { return ws + tx_al((int64_t)M * 3 * K / 2 + 64); }
-int asd_tx_linear(const float* x, int32_t M, int32_t K, int32_t ldx, const void* plane_w, const float* inv_w, int32_t N, const float* bias, int32_t mode,
-                  float* aux, const float* residual, int32_t ldr, float* y, int32_t ldy, float* ws, void* stream) {
-    return tx_linear_core(x, M, K, ldx, plane_w, inv_w, N, bias, mode, aux, residual, ldr, y, ldy, ws, false, stream);
-}
+// kernel that produced x: TxLinearWs)
 static int tx_linear_core(const float* x, int32_t M, int32_t K, int32_t ldx, const void* plane_w, const float* inv_w, int32_t N, const float* bias, int32_t mode,
                           float* aux, const float* residual, int32_t ldr, float* y, int32_t ldy, float* ws, bool planes_ready, void* stream) {
     ASD_CHECK_ARG(x && plane_w && inv_w && y && ws && M > 0 && N > 0 && K > 0, "null argument");
     ASD_CHECK_ARG(K % 64 == 0 && N % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && (mode == 0 || aux), "K % 64, N % 4, leading dimensions % 4; aux for GELU modes");
     hipStream_t s = (hipStream_t)stream;
-    h16* pa = reinterpret_cast<h16*>(ws);
-    float* ia = ws + tx_al((int64_t)M * 3 * K / 2 + 64);
-    float* c32 = ia + tx_al(M);
+    const TxLinearWs L = tx_linear_ws(M, N, K);
+    h16* pa = reinterpret_cast<h16*>(ws + L.planes);
+    float *ia = ws + L.inv, *c32 = ws + L.c32;
     if (!planes_ready) hipLaunchKernelGGL((tx_split_rows_kernel<0>), dim3(asd_div_up(M, 4)), dim3(256), 0, s, x, M, K, ldx, pa, ia);
     const float* res;
     int nslab;
-    const int rc = tx_gemm(pa, (const h16*)plane_w, M, N, 3 * K, c32, c32 + tx_al((int64_t)M * N), &res, &nslab, s);
+    const int rc = tx_gemm(pa, (const h16*)plane_w, M, N, 3 * K, c32, ws + L.slabs, &res, &nslab, s);
     if (rc != ASD_OK) return rc;
     hipLaunchKernelGGL(tx_epilogue_kernel, dim3(asd_grid_for((int64_t)M * N / 4, 256)), dim3(256), 0, s, res, nslab, M, N, ia, inv_w, bias, mode, aux, N, residual, ldr, y, ldy);
     ASD_LAUNCH_CHECK();
     return ASD_OK;
 }
-
-int64_t asd_tx_wgrad_workspace(int32_t M, int32_t N, int32_t K) {
-    const int64_t Mp = tx_rp(M);
-    return tx_al((int64_t)N * 3 * Mp / 2 + 64) + tx_al((int64_t)K * 3 * Mp / 2 + 64) + tx_al(N) + tx_al(K) + tx_al(N) + tx_al(K) + tx_al((int64_t)N * K) +
-           tx_gemm_ws_floats(N, K, 3 * (int)Mp);
+int asd_tx_linear(const float* x, int32_t M, int32_t K, int32_t ldx, const void* plane_w, const float* inv_w, int32_t N, const float* bias, int32_t mode,
+                  float* aux, const float* residual, int32_t ldr, float* y, int32_t ldy, float* ws, void* stream) {
+    return tx_linear_core(x, M, K, ldx, plane_w, inv_w, N, bias, mode, aux, residual, ldr, y, ldy, ws, false, stream);
 }
+
+int64_t asd_tx_wgrad_workspace(int32_t M, int32_t N, int32_t K) { return tx_wgrad_ws(M, N, K).total; }
 
 // dw [N, K] = dy [M, N]^T . x [M, K]  (contraction over the M rows), db [N] = column sums of dy (optional)
 // x_planes / x_inv: the transposed planes of x made earlier (the text tokens serve all twelve layers); x_bound: per-column bounds of |x|
@@ -1076,17 +1092,11 @@ static int tx_wgrad_core(const float* dy, int32_t ldy, const float* x, int32_t l
     ASD_CHECK_ARG(dy && (x || x_planes) && dw && ws && M > 0 && N > 0 && K > 0 && N % 4 == 0 && K % 4 == 0, "bad argument");
     hipStream_t s = (hipStream_t)stream;
     const int Mp = tx_rp(M);
-    h16* pa = reinterpret_cast<h16*>(ws);                                   // dy^T [N, 3 Mp]
-    float* p = ws + tx_al((int64_t)N * 3 * Mp / 2 + 64);
-    h16* pw = reinterpret_cast<h16*>(p);                                    // x^T [K, 3 Mp]
-    p += tx_al((int64_t)K * 3 * Mp / 2 + 64);
-    float* ia = p; p += tx_al(N);
-    float* iw = p; p += tx_al(K);
-    unsigned* cmax_a = reinterpret_cast<unsigned*>(p); p += tx_al(N);
-    p += tx_al(K);
-    float* c32 = p;
-    cmax_a = tx_zeroed(cmax_a, (size_t)(tx_al(N) + tx_al(K)), s);
-    unsigned* cmax_w = cmax_a + tx_al(N);
+    const TxWgradWs L = tx_wgrad_ws(M, N, K);
+    h16 *pa = reinterpret_cast<h16*>(ws + L.dyt), *pw = reinterpret_cast<h16*>(ws + L.xt);
+    float *ia = ws + L.inv_dy, *iw = ws + L.inv_x, *c32 = ws + L.c32;
+    unsigned* cmax_a = tx_zeroed(reinterpret_cast<unsigned*>(ws + L.cmax), (size_t)L.cmax_words, s);
+    unsigned* cmax_w = cmax_a + L.cmax_x;
     if (db && !tx_pool.outputs_zeroed && !accumulate) tx_memset0(db, (size_t)N * 4, s);
     hipLaunchKernelGGL(tx_colstat_kernel, dim3(asd_div_up(N, 64), asd_div_up(M, 256)), dim3(256), 0, s, dy, M, N, ldy, 256, cmax_a, db);
     hipLaunchKernelGGL((tx_split_cols_kernel<0>), dim3(asd_div_up(N, 64), Mp / 64), dim3(256), 0, s, dy, M, N, ldy, Mp, cmax_a, pa, ia);
@@ -1096,7 +1106,7 @@ static int tx_wgrad_core(const float* dy, int32_t ldy, const float* x, int32_t l
     }
     const float* res;
     int nslab;
-    const int rc = tx_gemm(pa, x_planes ? x_planes : pw, N, K, 3 * Mp, c32, c32 + tx_al((int64_t)N * K), &res, &nslab, s);
+    const int rc = tx_gemm(pa, x_planes ? x_planes : pw, N, K, 3 * Mp, c32, ws + L.slabs, &res, &nslab, s);
     if (rc != ASD_OK) return rc;
     hipLaunchKernelGGL(tx_epilogue_kernel, dim3(asd_grid_for((int64_t)N * K / 4, 256)), dim3(256), 0, s, res, nslab, N, K, ia, x_planes ? x_inv : iw, (const float*)nullptr, 0,
                        (float*)nullptr, 0, accumulate ? (const float*)dw : (const float*)nullptr, K, dw, K);
@@ -1120,12 +1130,6 @@ int asd_tx_layernorm_fwd(const float* x, int32_t M, int32_t D, const float* gamm
 
 // dx = LayerNorm input gradient (+ dres); dgamma / dbeta are ACCUMULATED (+=: the caller zeroes them once per backward pass)
 static int tx_layernorm_bwd_core(const float* dy, const float* x, const float* stats, const float* gamma, int32_t M, int32_t D, const float* dres, float* dx,
-                                 float* dgamma, float* dbeta, h16* plane, float* inv, void* stream);
-int asd_tx_layernorm_bwd(const float* dy, const float* x, const float* stats, const float* gamma, int32_t M, int32_t D, const float* dres, float* dx,
-                         float* dgamma, float* dbeta, void* stream) {
-    return tx_layernorm_bwd_core(dy, x, stats, gamma, M, D, dres, dx, dgamma, dbeta, nullptr, nullptr, stream);
-}
-static int tx_layernorm_bwd_core(const float* dy, const float* x, const float* stats, const float* gamma, int32_t M, int32_t D, const float* dres, float* dx,
                                  float* dgamma, float* dbeta, h16* plane, float* inv, void* stream) {
     ASD_CHECK_ARG(dy && x && stats && gamma && dx && dgamma && dbeta && M > 0 && D > 0 && D % 4 == 0 && D <= 1024, "LayerNorm: D % 4 == 0, D <= 1024");
     static const int rows_per_wave = getenv("ASD_TX_LN_ROWS") ? atoi(getenv("ASD_TX_LN_ROWS")) : 8;      // tools/tritx_time.py: 81 / 44 / 29 / 28 / 40 us at 1 / 2 / 4 / 8 / 16 rows per wave (the per-block atomics of dgamma / dbeta dominate)
@@ -1135,7 +1139,10 @@ static int tx_layernorm_bwd_core(const float* dy, const float* x, const float* s
     ASD_LAUNCH_CHECK();
     return ASD_OK;
 }
-
+int asd_tx_layernorm_bwd(const float* dy, const float* x, const float* stats, const float* gamma, int32_t M, int32_t D, const float* dres, float* dx,
+                         float* dgamma, float* dbeta, void* stream) {
+    return tx_layernorm_bwd_core(dy, x, stats, gamma, M, D, dres, dx, dgamma, dbeta, nullptr, nullptr, stream);
+}
 
 // ---- attention ---------------------------------------------------------------------------------------------------------------------------
 static inline int tx_lp(int L) { return (L + 127) & ~127; }
@@ -1146,18 +1153,26 @@ static inline int tx_split_for(int blocks, int target, int tiles) {
     if (z > 16) z = 16;
     return z < 1 ? 1 : z;
 }
-static inline int64_t tx_attn_part_floats(int64_t Lq, int64_t Lk, int64_t H) {
-    const int64_t a = 16 * (Lq * H * TX_HD + 2 * H * Lq), b = 16 * 2 * Lk * H * TX_HD;     // at most 16 pieces
-    const int64_t zq = tx_split_for((int)((Lq + 127) / 128 * H), 768, (int)((Lk + 31) / 32)), zk = tx_split_for((int)((Lk + 127) / 128 * H), 1536, (int)((Lq + 31) / 32));
-    const int64_t nq = zq > 1 ? zq * (Lq * H * TX_HD + 2 * H * Lq) : 0, nk = zk > 1 ? zk * 2 * Lk * H * TX_HD : 0;
-    (void)a; (void)b;
-    return tx_al((nq > nk ? nq : nk) + 64);
-}      // plane rows: whole 128-row blocks (32 per wave) so no load leaves the plane
-int64_t asd_tx_attention_workspace(int32_t Lq, int32_t Lk, int32_t H) {
-    // six planes of halfs (Q, K row-major hi / lo; V^T hi / lo), the backward's extra planes (Q^T, dO, dO^T) and 5 * H scale words
-    const int64_t Lqp = tx_lp(Lq), Lkp = tx_lp(Lk);
-    return tx_al((int64_t)H * TX_HD * (8 * Lqp + 6 * Lkp) / 2 + 256) + tx_al(8 * H) + tx_al((int64_t)H * Lq) + tx_attn_part_floats(Lq, Lk, H);
+// The workspace of asd_tx_attention_fwd and _bwd (one layout serves both) and the splits of their launches.  planes: halfs, H * TX_HD * Lqp (query side)
+// or * Lkp (key side) each, whole 128-row blocks (32 per wave) so no load leaves a plane — forward Q, K, V^T as hi / lo; backward Q, dO, Q^T, dO^T (8 of the
+// query side) then K, V, K^T (6 of the key side).  amax [8 H]: absmax words per head; dsum [H, Lq]: rowwise d_o . o; part: the pieces of a split launch
+struct TxAttnWs {
+    int Lqp, Lkp, ksplit /* key-range pieces of the forward and of dQ */, qsplit /* query-range pieces of dK / dV */;
+    int64_t planes, amax, dsum, part, total;
+};
+static TxAttnWs tx_attn_ws(int Lq, int Lk, int H) {
+    TxAttnWs L;
+    asd_ws_cursor w;
+    L.Lqp = tx_lp(Lq); L.Lkp = tx_lp(Lk);
+    L.ksplit = tx_split_for(asd_div_up(Lq, 128) * H, 768, asd_div_up(Lk, 32));
+    L.qsplit = tx_split_for(asd_div_up(Lk, 128) * H, 1536, asd_div_up(Lq, 32));
+    const int64_t nq = L.ksplit > 1 ? L.ksplit * ((int64_t)Lq * H * TX_HD + 2 * (int64_t)H * Lq) : 0, nk = L.qsplit > 1 ? L.qsplit * 2 * (int64_t)Lk * H * TX_HD : 0;
+    L.planes = w.take((int64_t)H * TX_HD * (8 * (int64_t)L.Lqp + 6 * (int64_t)L.Lkp) / 2 + 256);
+    L.amax = w.take(8 * H); L.dsum = w.take((int64_t)H * Lq); L.part = w.take((nq > nk ? nq : nk) + 64);
+    L.total = w.o;
+    return L;
 }
+int64_t asd_tx_attention_workspace(int32_t Lq, int32_t Lk, int32_t H) { return tx_attn_ws(Lq, Lk, H).total; }
 
 // o [Lq, ldo] = softmax(q k^T / sqrt(48)) v per head (head h = columns 48 h .. 48 h + 47 of q / k / v / o), lse2 [H, Lq] for the backward
 int asd_tx_attention_fwd(const float* q, int32_t ldq, const float* k, int32_t ldk, const float* v, int32_t ldv, int32_t Lq, int32_t Lk, int32_t H,
@@ -1165,15 +1180,11 @@ int asd_tx_attention_fwd(const float* q, int32_t ldq, const float* k, int32_t ld
     ASD_CHECK_ARG(q && k && v && o && lse2 && ws && Lq > 0 && Lk > 0 && H > 0 && H <= 64, "null argument");
     ASD_CHECK_ARG(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0, "leading dimensions must be multiples of 4 floats");
     hipStream_t s = (hipStream_t)stream;
-    const int Lqp = tx_lp(Lq), Lkp = tx_lp(Lk);
-    h16* p = reinterpret_cast<h16*>(ws);
-    h16* qh = p; p += (size_t)H * Lqp * TX_HD;
-    h16* ql = p; p += (size_t)H * Lqp * TX_HD;
-    h16* kh = p; p += (size_t)H * Lkp * TX_HD;
-    h16* kl = p; p += (size_t)H * Lkp * TX_HD;
-    h16* vth = p; p += (size_t)H * Lkp * TX_HD;
-    h16* vtl = p; p += (size_t)H * Lkp * TX_HD;
-    unsigned* amax = tx_zeroed(reinterpret_cast<unsigned*>(ws + tx_al((int64_t)H * TX_HD * (8 * (int64_t)Lqp + 6 * (int64_t)Lkp) / 2 + 256)), (size_t)8 * H, s);
+    const TxAttnWs L = tx_attn_ws(Lq, Lk, H);
+    const int Lqp = L.Lqp, Lkp = L.Lkp, zk = L.ksplit;
+    const size_t nq = (size_t)H * Lqp * TX_HD, nk = (size_t)H * Lkp * TX_HD;
+    h16 *qh = reinterpret_cast<h16*>(ws + L.planes), *ql = qh + nq, *kh = qh + 2 * nq, *kl = kh + nk, *vth = kh + 2 * nk, *vtl = kh + 3 * nk;
+    unsigned* amax = tx_zeroed(reinterpret_cast<unsigned*>(ws + L.amax), (size_t)8 * H, s);
     {
         tx_absmax_args m;
         m.x[0] = q; m.L[0] = Lq; m.ld[0] = ldq; m.x[1] = k; m.L[1] = Lk; m.ld[1] = ldk; m.x[2] = v; m.L[2] = Lk; m.ld[2] = ldv; m.x[3] = nullptr; m.L[3] = 0; m.ld[3] = 0;
@@ -1182,15 +1193,13 @@ int asd_tx_attention_fwd(const float* q, int32_t ldq, const float* k, int32_t ld
     hipLaunchKernelGGL(tx_attn_prep_rows_kernel, dim3(asd_div_up((int64_t)Lqp * (TX_HD / 4), 256), H), dim3(256), 0, s, q, Lq, Lqp, ldq, H, amax, qh, ql);
     hipLaunchKernelGGL(tx_attn_prep_rows_kernel, dim3(asd_div_up((int64_t)Lkp * (TX_HD / 4), 256), H), dim3(256), 0, s, k, Lk, Lkp, ldk, H, amax + H, kh, kl);
     hipLaunchKernelGGL(tx_attn_prep_cols_kernel, dim3(Lkp / 64, H), dim3(256), 0, s, v, Lk, Lkp, ldv, H, amax + 2 * H, vth, vtl);
-    float* part = ws + tx_al((int64_t)H * TX_HD * (8 * (int64_t)Lqp + 6 * (int64_t)Lkp) / 2 + 256) + tx_al(8 * H) + tx_al((int64_t)H * Lq);
-    const int zk = tx_split_for(asd_div_up(Lq, 128) * H, 768, asd_div_up(Lk, 32));
+    float* part = ws + L.part;
     hipLaunchKernelGGL(tx_attn_fwd_kernel, dim3(asd_div_up(Lq, 128), H, zk), dim3(256), 0, s, qh, ql, kh, kl, vth, vtl, amax, Lq, Lqp, Lk, Lkp, H, o, ldo, lse2, part);
     if (zk > 1)
         hipLaunchKernelGGL(tx_attn_fwd_combine_kernel, dim3(asd_div_up((int64_t)Lq * H * (TX_HD / 4), 256)), dim3(256), 0, s, part, zk, Lq, H, o, ldo, lse2);
     ASD_LAUNCH_CHECK();
     return ASD_OK;
 }
-
 
 // (dq, dk, dv) of asd_tx_attention_fwd from the gradient d_o of its output; o and lse2 are the forward's outputs
 int asd_tx_attention_bwd(const float* q, int32_t ldq, const float* k, int32_t ldk, const float* v, int32_t ldv, const float* o, int32_t ldo,
@@ -1199,16 +1208,14 @@ int asd_tx_attention_bwd(const float* q, int32_t ldq, const float* k, int32_t ld
     ASD_CHECK_ARG(q && k && v && o && d_o && lse2 && dq && dk && dv && ws && Lq > 0 && Lk > 0 && H > 0 && H <= 64, "null argument");
     ASD_CHECK_ARG(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 && lddo % 4 == 0, "leading dimensions must be multiples of 4 floats");
     hipStream_t s = (hipStream_t)stream;
-    const int Lqp = tx_lp(Lq), Lkp = tx_lp(Lk);
+    const TxAttnWs L = tx_attn_ws(Lq, Lk, H);
+    const int Lqp = L.Lqp, Lkp = L.Lkp, qsplit = L.qsplit, ksplit = L.ksplit;
     const size_t nq = (size_t)H * Lqp * TX_HD, nk = (size_t)H * Lkp * TX_HD;
-    h16* p = reinterpret_cast<h16*>(ws);
     tx_attn_bwd_args a;
-    h16 *qh = p, *ql = p + nq, *doh = p + 2 * nq, *dol = p + 3 * nq, *qth = p + 4 * nq, *qtl = p + 5 * nq, *doth = p + 6 * nq, *dotl = p + 7 * nq;
-    p += 8 * nq;
-    h16 *kh = p, *kl = p + nk, *vh = p + 2 * nk, *vl = p + 3 * nk, *kth = p + 4 * nk, *ktl = p + 5 * nk;
-    float* tail = ws + tx_al((int64_t)H * TX_HD * (8 * (int64_t)Lqp + 6 * (int64_t)Lkp) / 2 + 256);
-    unsigned* amax = tx_zeroed(reinterpret_cast<unsigned*>(tail), (size_t)8 * H, s);
-    float* dsum = tail + tx_al(8 * H);
+    h16 *qh = reinterpret_cast<h16*>(ws + L.planes), *ql = qh + nq, *doh = qh + 2 * nq, *dol = qh + 3 * nq, *qth = qh + 4 * nq, *qtl = qh + 5 * nq, *doth = qh + 6 * nq, *dotl = qh + 7 * nq;
+    h16 *kh = qh + 8 * nq, *kl = kh + nk, *vh = kh + 2 * nk, *vl = kh + 3 * nk, *kth = kh + 4 * nk, *ktl = kh + 5 * nk;
+    unsigned* amax = tx_zeroed(reinterpret_cast<unsigned*>(ws + L.amax), (size_t)8 * H, s);
+    float* dsum = ws + L.dsum;
     {
         tx_absmax_args m;
         m.x[0] = q; m.L[0] = Lq; m.ld[0] = ldq; m.x[1] = k; m.L[1] = Lk; m.ld[1] = ldk; m.x[2] = v; m.L[2] = Lk; m.ld[2] = ldv; m.x[3] = d_o; m.L[3] = Lq; m.ld[3] = lddo;
@@ -1228,8 +1235,7 @@ int asd_tx_attention_bwd(const float* q, int32_t ldq, const float* k, int32_t ld
     a.amax = amax; a.lse2 = lse2; a.dsum = dsum;
     a.Lq = Lq; a.Lqp = Lqp; a.Lk = Lk; a.Lkp = Lkp; a.H = H;
     a.dq = dq; a.dk = dk; a.dv = dv; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
-    a.part = dsum + tx_al((int64_t)H * Lq);
-    const int qsplit = tx_split_for(asd_div_up(Lk, 128) * H, 1536, asd_div_up(Lq, 32));
+    a.part = ws + L.part;
     hipLaunchKernelGGL(tx_attn_bwd_kv_kernel, dim3(asd_div_up(Lk, 128), H, qsplit), dim3(256), 0, s, a);
     if (qsplit > 1) {
         const int HDa = H * TX_HD;
@@ -1237,14 +1243,12 @@ int asd_tx_attention_bwd(const float* q, int32_t ldq, const float* k, int32_t ld
         hipLaunchKernelGGL(tx_attn_sum_parts_kernel, g, dim3(256), 0, s, a.part, qsplit, Lk, HDa, dk, lddk);
         hipLaunchKernelGGL(tx_attn_sum_parts_kernel, g, dim3(256), 0, s, a.part + (size_t)qsplit * Lk * HDa, qsplit, Lk, HDa, dv, lddv);
     }
-    const int ksplit = tx_split_for(asd_div_up(Lq, 128) * H, 768, asd_div_up(Lk, 32));
     hipLaunchKernelGGL(tx_attn_bwd_q_kernel, dim3(asd_div_up(Lq, 128), H, ksplit), dim3(256), 0, s, a);
     if (ksplit > 1)
         hipLaunchKernelGGL(tx_attn_sum_parts_kernel, dim3(asd_div_up((int64_t)Lq * (H * TX_HD / 4), 256)), dim3(256), 0, s, a.part, ksplit, Lq, H * TX_HD, dq, lddq);
     ASD_LAUNCH_CHECK();
     return ASD_OK;
 }
-
 
 // ---- the whole generator: forward / backward schedules -------------------------------------------------------------------------------------
 // y [T, 4 C] (token t = (plane p, h, w) of the low-res grid R x R; column co * 4 + i * 2 + j) <-> channel-last planes [3][2R][2R][C]
@@ -1276,18 +1280,16 @@ struct TxDims {
     explicit TxDims(const asd_tritx_desc& d) : layers(d.n_layers), D(d.dim), H(d.heads), Dc(d.cond_dim), T(3 * d.low_res * d.low_res), Tc(d.cond_tokens),
                                                F(d.hidden), Cc(d.out_channels), R(d.low_res), O(4 * d.out_channels) {}
 };
-inline int64_t plane_floats(int64_t rows, int64_t k) { return tx_al(rows * 3 * k / 2 + 64); }
-
 // packed weights of one layer / of the head, as offsets (floats) into the packed buffer
 struct TxPackLayer { int64_t caq_w, caq_iw, caq_t, caq_it, cakv_w, cakv_iw, cao_w, cao_iw, cao_t, cao_it, qkv_w, qkv_iw, qkv_t, qkv_it, sao_w, sao_iw, sao_t, sao_it,
                              fc1_w, fc1_iw, fc1_t, fc1_it, fc2_w, fc2_iw, fc2_t, fc2_it, bn1, bn2, bn3, bh, end; };
 TxPackLayer tx_pack_layout(const TxDims& d, int64_t base) {
     TxPackLayer L;
-    int64_t o = base;
-    auto take = [&](int64_t n) { const int64_t at = o; o += tx_al(n); return at; };
+    asd_ws_cursor c;
+    c.o = base;
     auto planes = [&](int N, int K, int64_t& w, int64_t& iw, int64_t* t, int64_t* it) {
-        w = o; o += plane_floats(N, K); iw = take(N);
-        if (t) { *t = o; o += plane_floats(K, tx_rp(N)); *it = take(K); }
+        w = c.take(tx_plane_floats(N, K)); iw = c.take(N);
+        if (t) { *t = c.take(tx_plane_floats(K, tx_rp(N))); *it = c.take(K); }
     };
     planes(d.D, d.D, L.caq_w, L.caq_iw, &L.caq_t, &L.caq_it);
     planes(2 * d.D, d.Dc, L.cakv_w, L.cakv_iw, nullptr, nullptr);
@@ -1296,60 +1298,45 @@ TxPackLayer tx_pack_layout(const TxDims& d, int64_t base) {
     planes(d.D, d.D, L.sao_w, L.sao_iw, &L.sao_t, &L.sao_it);
     planes(d.F, d.D, L.fc1_w, L.fc1_iw, &L.fc1_t, &L.fc1_it);
     planes(d.D, d.F, L.fc2_w, L.fc2_iw, &L.fc2_t, &L.fc2_it);
-    L.bn1 = take(d.D); L.bn2 = take(d.D); L.bn3 = take(d.D); L.bh = take(d.F);        // column bounds of n1, n2, n3, gelu(fc1): tx_bounds_kernel
-    L.end = o;
+    L.bn1 = c.take(d.D); L.bn2 = c.take(d.D); L.bn3 = c.take(d.D); L.bh = c.take(d.F);        // column bounds of n1, n2, n3, gelu(fc1): tx_bounds_kernel
+    L.end = c.o;
     return L;
 }
-struct TxPackHead { int64_t dc_w, dc_iw, dc_t, dc_it, end; };
-TxPackHead tx_pack_head(const TxDims& d, int64_t base) {
-    TxPackHead h;
-    int64_t o = base;
-    h.dc_w = o; o += plane_floats(d.O, d.D); h.dc_iw = o; o += tx_al(d.O);
-    h.dc_t = o; o += plane_floats(d.D, tx_rp(d.O)); h.dc_it = o; o += tx_al(d.D);
-    h.end = o;
-    return h;
+// the whole packed buffer: `layers` x TxPackLayer (layer l at per_layer * l), the deconvolution's planes, then what only asd_tritx_pack uses:
+// staging for the stacked q|k|v and k|v weights and the column-max cells of asd_tx_pack_weight
+struct TxPacked { int64_t per_layer, dc_w, dc_iw, dc_t, dc_it, stage_qkv, stage_kv, cws, total; };
+TxPacked tx_packed_layout(const TxDims& d) {
+    TxPacked L;
+    asd_ws_cursor c;
+    L.per_layer = tx_pack_layout(d, 0).end;
+    c.o = L.per_layer * d.layers;
+    L.dc_w = c.take(tx_plane_floats(d.O, d.D)); L.dc_iw = c.take(d.O); L.dc_t = c.take(tx_plane_floats(d.D, tx_rp(d.O))); L.dc_it = c.take(d.D);
+    L.stage_qkv = c.take((int64_t)3 * d.D * d.D); L.stage_kv = c.take((int64_t)2 * d.D * d.Dc); L.cws = c.take(d.F + d.D + d.Dc + 64);
+    L.total = c.o;
+    return L;
 }
 
-// saved activations of one layer (offsets in floats from the layer's base)
-struct TxSave { int64_t x_in, st1, n1, q_ca, kv_ca, o_ca, lse_ca, x1, st2, n2, qkv, o_sa, lse_sa, x2, st3, n3, u, hmid, end; };
+// saved activations of one batch element: `layers` x (x_in .. hmid: offsets from the layer's base, layer l at end * l), then x_final, stF, nF, y
+// (offsets from the element's base, element n at per_sample * n)
+struct TxSave { int64_t x_in, st1, n1, q_ca, kv_ca, o_ca, lse_ca, x1, st2, n2, qkv, o_sa, lse_sa, x2, st3, n3, u, hmid, end, xf, stF, nF, y, per_sample; };
 TxSave tx_save_layout(const TxDims& d) {
     TxSave s;
-    int64_t o = 0;
-    auto take = [&](int64_t n) { const int64_t at = o; o += tx_al(n); return at; };
+    asd_ws_cursor c;
+    auto take = [&](int64_t n) { return c.take(n); };
     const int64_t TD = (int64_t)d.T * d.D;
     s.x_in = take(TD); s.st1 = take(2 * d.T); s.n1 = take(TD); s.q_ca = take(TD); s.kv_ca = take((int64_t)d.Tc * 2 * d.D); s.o_ca = take(TD);
     s.lse_ca = take((int64_t)d.H * d.T); s.x1 = take(TD); s.st2 = take(2 * d.T); s.n2 = take(TD); s.qkv = take(3 * TD); s.o_sa = take(TD);
     s.lse_sa = take((int64_t)d.H * d.T); s.x2 = take(TD); s.st3 = take(2 * d.T); s.n3 = take(TD); s.u = take((int64_t)d.T * d.F); s.hmid = take((int64_t)d.T * d.F);
-    s.end = o;
+    s.end = c.o;
+    c.o = s.end * d.layers;
+    s.xf = take(TD); s.stF = take(2 * d.T); s.nF = take(TD); s.y = take((int64_t)d.T * d.O);
+    s.per_sample = c.o;
     return s;
 }
-// per batch element: layers x TxSave, then x_final, stF, nF, y
-inline int64_t tx_save_per_sample(const TxDims& d) {
-    return (int64_t)d.layers * tx_save_layout(d).end + tx_al((int64_t)d.T * d.D) * 2 + tx_al(2 * d.T) + tx_al((int64_t)d.T * d.O);
-}
-inline int64_t tx_max64(int64_t a, int64_t b) { return a > b ? a : b; }
-inline int64_t tx_op_ws(const TxDims& d) {
-    int64_t w = 0;
-    w = tx_max64(w, asd_tx_linear_workspace(d.T, d.F, d.D));
-    w = tx_max64(w, asd_tx_linear_workspace(d.T, d.D, d.F));
-    w = tx_max64(w, asd_tx_linear_workspace(d.T, 3 * d.D, d.D));
-    w = tx_max64(w, asd_tx_linear_workspace(d.T, d.D, 3 * d.D));
-    w = tx_max64(w, asd_tx_linear_workspace(d.Tc, 2 * d.D, d.Dc));
-    w = tx_max64(w, asd_tx_wgrad_workspace(d.T, d.F, d.D));
-    w = tx_max64(w, asd_tx_wgrad_workspace(d.T, d.D, d.F));
-    w = tx_max64(w, asd_tx_wgrad_workspace(d.T, 3 * d.D, d.D));
-    w = tx_max64(w, asd_tx_wgrad_workspace(d.Tc, 2 * d.D, d.Dc));
-    w = tx_max64(w, asd_tx_wgrad_workspace(d.T, d.D, d.O));
-    w = tx_max64(w, asd_tx_attention_workspace(d.T, d.T, d.H));
-    w = tx_max64(w, asd_tx_attention_workspace(d.T, d.Tc, d.H));
-    return tx_al(w);
-}
-inline int64_t tx_stage_floats(const TxDims& d) {
-    int64_t w = (int64_t)d.F * d.D;
-    w = tx_max64(w, (int64_t)3 * d.D * d.D);
-    w = tx_max64(w, (int64_t)2 * d.D * d.Dc);
-    w = tx_max64(w, (int64_t)d.D * d.O);
-    return tx_al(w) + tx_al(tx_max64(d.F, 3 * d.D));
+inline int64_t tx_op_ws(const TxDims& d) {      // the largest workspace among the building blocks the two passes call
+    return std::max({tx_linear_ws(d.T, d.F, d.D).total, tx_linear_ws(d.T, d.D, d.F).total, tx_linear_ws(d.T, 3 * d.D, d.D).total, tx_linear_ws(d.T, d.D, 3 * d.D).total,
+                     tx_linear_ws(d.Tc, 2 * d.D, d.Dc).total, tx_wgrad_ws(d.T, d.F, d.D).total, tx_wgrad_ws(d.T, d.D, d.F).total, tx_wgrad_ws(d.T, 3 * d.D, d.D).total,
+                     tx_wgrad_ws(d.Tc, 2 * d.D, d.Dc).total, tx_wgrad_ws(d.T, d.D, d.O).total, tx_attn_ws(d.T, d.T, d.H).total, tx_attn_ws(d.T, d.Tc, d.H).total});
 }
 int tx_check_desc(const asd_tritx_desc* d) {
     ASD_CHECK_ARG(d && d->n_layers > 0 && d->heads > 0 && d->dim == d->heads * TX_HD, "tritx: dim must be heads * 48");
@@ -1362,14 +1349,11 @@ int tx_check_desc(const asd_tritx_desc* d) {
 
 int64_t asd_tritx_packed_floats(const asd_tritx_desc* desc) {
     if (tx_check_desc(desc) != ASD_OK) return -1;
-    const TxDims d(*desc);
-    const int64_t per_layer = tx_pack_layout(d, 0).end;
-    // + staging for the stacked q|k|v and k|v weights
-    return tx_pack_head(d, per_layer * d.layers).end + tx_al((int64_t)3 * d.D * d.D) + tx_al((int64_t)2 * d.D * d.Dc) + tx_al(d.F + d.D + d.Dc + 64);
+    return tx_packed_layout(TxDims(*desc)).total;
 }
 int64_t asd_tritx_save_floats(const asd_tritx_desc* desc, int32_t batch) {
     if (tx_check_desc(desc) != ASD_OK) return -1;
-    return tx_save_per_sample(TxDims(*desc)) * batch;
+    return tx_save_layout(TxDims(*desc)).per_sample * batch;
 }
 static int64_t tx_pool_words(const TxDims& d) {
     // per layer: two attention calls (forward or backward) + seven weight gradients (column-max cells of both operands)
@@ -1377,13 +1361,28 @@ static int64_t tx_pool_words(const TxDims& d) {
     return (int64_t)d.layers * (2 * tx_al(8 * d.H) + wg) + tx_al(d.D) + tx_al(d.O) + 4096;
 }
 
+// The workspace of asd_tritx_fwd and asd_tritx_bwd.  NOTHING in it is carried from the forward to the backward pass: the forward uses `op` and `pool`
+// only, each building block fills the part of `op` it reads (a LayerNorm leaves planes there for the Linear issued right after it, in the same pass), the
+// backward clears `pool` and rebuilds `cond_*` per batch element and writes every transient gradient before it reads it.  What the backward needs from
+// the forward is in `save` (and the text embedding).  op: the workspace of whichever building block runs (tx_op_ws); dxa .. dy: transient gradients of the
+// backward — dx ping-pong, dn, do [T, D], dqkv [T, 3D], dkv [Tc, 2D], du [T, F], dy [T, O]; cond_*: text tokens^T [Dc, 3 Tcp] with scales and column maxima
+// [Dc], one split for all layers; pool: tx_pool_words zeroed words per batch element (tx_zeroed), with 256 floats of slack behind them
+struct TxWs { int64_t op, dxa, dxb, dn, dob, dqkv, dkv, du, dy, cond_planes, cond_inv, cond_max, pool, total; };
+static TxWs tx_ws_layout(const TxDims& d) {
+    TxWs L;
+    asd_ws_cursor w;
+    const int64_t TD = (int64_t)d.T * d.D;
+    L.op = w.take(tx_op_ws(d));
+    L.dxa = w.take(TD); L.dxb = w.take(TD); L.dn = w.take(TD); L.dob = w.take(TD); L.dqkv = w.take(3 * TD);
+    L.dkv = w.take((int64_t)d.Tc * 2 * d.D); L.du = w.take((int64_t)d.T * d.F); L.dy = w.take((int64_t)d.T * d.O);
+    L.cond_planes = w.take(tx_plane_floats(d.Dc, tx_rp(d.Tc))); L.cond_inv = w.take(d.Dc); L.cond_max = w.take(d.Dc);
+    L.pool = w.take(tx_pool_words(d));
+    L.total = w.o + 256;
+    return L;
+}
 int64_t asd_tritx_workspace_floats(const asd_tritx_desc* desc) {
     if (tx_check_desc(desc) != ASD_OK) return -1;
-    const TxDims d(*desc);
-    // transient gradients of the backward pass: dx ping-pong (2), dn, do, dqkv (3), dkv, du, dy, the weight-gradient staging of batch
-    // elements > 0, + the op workspace
-    return tx_op_ws(d) + tx_al((int64_t)d.T * d.D) * 7 + tx_al((int64_t)d.Tc * 2 * d.D) + tx_al((int64_t)d.T * d.F) + tx_al((int64_t)d.T * d.O) +
-           tx_stage_floats(d) + tx_pool_words(d) + tx_al((int64_t)d.Dc * 3 * tx_rp(d.Tc) / 2 + 64) + 2 * tx_al(d.Dc) + 256;
+    return tx_ws_layout(TxDims(*desc)).total;
 }
 
 // params: 20 * n_layers + 4 device pointers (order: include/asd_hip.h) -> packed operand planes of every weight
@@ -1392,15 +1391,12 @@ int asd_tritx_pack(const asd_tritx_desc* desc, const float* const* params, float
     ASD_CHECK_ARG(params && packed, "null argument");
     const TxDims d(*desc);
     hipStream_t s = (hipStream_t)stream;
-    const int64_t per_layer = tx_pack_layout(d, 0).end;
-    const TxPackHead hd = tx_pack_head(d, per_layer * d.layers);
-    float* stage_qkv = packed + hd.end;
-    float* stage_kv = stage_qkv + tx_al((int64_t)3 * d.D * d.D);
-    float* cws = stage_kv + tx_al((int64_t)2 * d.D * d.Dc);
+    const TxPacked hd = tx_packed_layout(d);
+    float *stage_qkv = packed + hd.stage_qkv, *stage_kv = packed + hd.stage_kv, *cws = packed + hd.cws;
 #define PK(w, N, K, WP, IW, TP, IT) TXS(asd_tx_pack_weight(w, N, K, packed + (WP), packed + (IW), (TP) >= 0 ? (void*)(packed + (TP)) : nullptr, (TP) >= 0 ? packed + (IT) : nullptr, cws, stream))
     for (int l = 0; l < d.layers; ++l) {
         const float* const* P = params + 20 * l;
-        const TxPackLayer L = tx_pack_layout(d, per_layer * l);
+        const TxPackLayer L = tx_pack_layout(d, hd.per_layer * l);
         PK(P[2], d.D, d.D, L.caq_w, L.caq_iw, L.caq_t, L.caq_it);
         (void)hipMemcpyAsync(stage_kv, P[3], (size_t)d.D * d.Dc * 4, hipMemcpyDeviceToDevice, s);
         (void)hipMemcpyAsync(stage_kv + (size_t)d.D * d.Dc, P[4], (size_t)d.D * d.Dc * 4, hipMemcpyDeviceToDevice, s);
@@ -1431,54 +1427,55 @@ int asd_tritx_pack(const asd_tritx_desc* desc, const float* const* params, float
 
 // text_embed [batch, Tc, Dc] -> planes_cl [batch, 3, 2R, 2R, C] (channel-last); `save` keeps what asd_tritx_bwd needs
 int asd_tritx_fwd(const asd_tritx_desc* desc, const float* const* params, const float* packed, const float* text_embed, int32_t batch, float* planes_cl,
-                  float* save, float* ws, void* stream) {
+                  float* save, float* workspace, void* stream) {
     TXS(tx_check_desc(desc));
-    ASD_CHECK_ARG(params && packed && text_embed && planes_cl && save && ws && batch > 0, "null argument");
+    ASD_CHECK_ARG(params && packed && text_embed && planes_cl && save && workspace && batch > 0, "null argument");
     const TxDims d(*desc);
     hipStream_t s = (hipStream_t)stream;
-    const int64_t per_layer = tx_pack_layout(d, 0).end;
-    const TxPackHead hd = tx_pack_head(d, per_layer * d.layers);
+    const TxPacked hd = tx_packed_layout(d);
     const TxSave S = tx_save_layout(d);
+    const TxWs W = tx_ws_layout(d);
+    float* const ws = workspace + W.op;      // what every building block is handed
     const int64_t TD = (int64_t)d.T * d.D;
     const float eps = desc->eps;
     struct PoolGuard { ~PoolGuard() { tx_pool = {nullptr, 0, false}; } } pool_guard;
-    unsigned* pool = reinterpret_cast<unsigned*>(ws + (asd_tritx_workspace_floats(desc) - tx_pool_words(d) - 256));
+    unsigned* pool = reinterpret_cast<unsigned*>(workspace + W.pool);
+    const TxLinearWs LN = tx_linear_ws(d.T, d.D, d.D);      // where a Linear over [T, D] rows looks for its operand planes and row scales
+    h16* const lp = reinterpret_cast<h16*>(ws + LN.planes);
+    float* const li = ws + LN.inv;
     for (int n = 0; n < batch; ++n) {
         tx_memset0(pool, (size_t)tx_pool_words(d) * 4, s);
         tx_pool = {pool, (size_t)tx_pool_words(d), false};
-        float* sv = save + (int64_t)n * tx_save_per_sample(d);
+        float* sv = save + (int64_t)n * S.per_sample;
         const float* cond = text_embed + (int64_t)n * d.Tc * d.Dc;
         const float* x = params[20 * d.layers];        // pos_embed
         for (int l = 0; l < d.layers; ++l) {
             const float* const* P = params + 20 * l;
-            const TxPackLayer L = tx_pack_layout(d, per_layer * l);
+            const TxPackLayer L = tx_pack_layout(d, hd.per_layer * l);
             float* B = sv + (int64_t)l * S.end;
             if (x != B + S.x_in)     // layer 0: the position embedding; later layers found their input written in place by the layer before
                 hipLaunchKernelGGL(tx_add_kernel, dim3(asd_grid_for(TD / 4, 256)), dim3(256), 0, s, B + S.x_in, x, (size_t)(TD / 4), 0);
             x = B + S.x_in;
             // cross-attention
             // (every LayerNorm leaves the operand planes of its output where the Linear that consumes it looks for them)
-            TXS(tx_layernorm_fwd_core(x, d.T, d.D, P[0], P[1], eps, B + S.n1, B + S.st1, tx_linear_planes_of(ws), tx_linear_inv_of(ws, d.T, d.D), stream));
+            TXS(tx_layernorm_fwd_core(x, d.T, d.D, P[0], P[1], eps, B + S.n1, B + S.st1, lp, li, stream));
             TXS(tx_linear_core(B + S.n1, d.T, d.D, d.D, packed + L.caq_w, packed + L.caq_iw, d.D, nullptr, 0, nullptr, nullptr, 0, B + S.q_ca, d.D, ws, true, stream));
             TXS(asd_tx_linear(cond, d.Tc, d.Dc, d.Dc, packed + L.cakv_w, packed + L.cakv_iw, 2 * d.D, nullptr, 0, nullptr, nullptr, 0, B + S.kv_ca, 2 * d.D, ws, stream));
             TXS(asd_tx_attention_fwd(B + S.q_ca, d.D, B + S.kv_ca, 2 * d.D, B + S.kv_ca + d.D, 2 * d.D, d.T, d.Tc, d.H, B + S.o_ca, d.D, B + S.lse_ca, ws, stream));
             TXS(asd_tx_linear(B + S.o_ca, d.T, d.D, d.D, packed + L.cao_w, packed + L.cao_iw, d.D, P[6], 0, nullptr, x, d.D, B + S.x1, d.D, ws, stream));
             // self-attention
-            TXS(tx_layernorm_fwd_core(B + S.x1, d.T, d.D, P[7], P[8], eps, B + S.n2, B + S.st2, tx_linear_planes_of(ws), tx_linear_inv_of(ws, d.T, d.D), stream));
+            TXS(tx_layernorm_fwd_core(B + S.x1, d.T, d.D, P[7], P[8], eps, B + S.n2, B + S.st2, lp, li, stream));
             TXS(tx_linear_core(B + S.n2, d.T, d.D, d.D, packed + L.qkv_w, packed + L.qkv_iw, 3 * d.D, nullptr, 0, nullptr, nullptr, 0, B + S.qkv, 3 * d.D, ws, true, stream));
             TXS(asd_tx_attention_fwd(B + S.qkv, 3 * d.D, B + S.qkv + d.D, 3 * d.D, B + S.qkv + 2 * d.D, 3 * d.D, d.T, d.T, d.H, B + S.o_sa, d.D, B + S.lse_sa, ws, stream));
             TXS(asd_tx_linear(B + S.o_sa, d.T, d.D, d.D, packed + L.sao_w, packed + L.sao_iw, d.D, P[13], 0, nullptr, B + S.x1, d.D, B + S.x2, d.D, ws, stream));
             // MLP
-            TXS(tx_layernorm_fwd_core(B + S.x2, d.T, d.D, P[14], P[15], eps, B + S.n3, B + S.st3, tx_linear_planes_of(ws), tx_linear_inv_of(ws, d.T, d.D), stream));
+            TXS(tx_layernorm_fwd_core(B + S.x2, d.T, d.D, P[14], P[15], eps, B + S.n3, B + S.st3, lp, li, stream));
             TXS(tx_linear_core(B + S.n3, d.T, d.D, d.D, packed + L.fc1_w, packed + L.fc1_iw, d.F, P[17], 1, B + S.u, nullptr, 0, B + S.hmid, d.F, ws, true, stream));
-            float* xo = l + 1 < d.layers ? sv + (int64_t)(l + 1) * S.end + S.x_in : sv + (int64_t)d.layers * S.end;     // next layer's input slot / x_final
+            float* xo = l + 1 < d.layers ? sv + (int64_t)(l + 1) * S.end + S.x_in : sv + S.xf;     // next layer's input slot / x_final
             TXS(asd_tx_linear(B + S.hmid, d.T, d.F, d.F, packed + L.fc2_w, packed + L.fc2_iw, d.D, P[19], 0, nullptr, B + S.x2, d.D, xo, d.D, ws, stream));
             x = xo;
         }
-        float* xf = sv + (int64_t)d.layers * S.end;
-        float* stF = xf + tx_al(TD);
-        float* nF = stF + tx_al(2 * d.T);
-        float* y = nF + tx_al(TD);
+        float *xf = sv + S.xf, *stF = sv + S.stF, *nF = sv + S.nF, *y = sv + S.y;
         TXS(asd_tx_layernorm_fwd(xf, d.T, d.D, params[20 * d.layers + 1], params[20 * d.layers + 2], eps, nF, stF, stream));
         TXS(asd_tx_linear(nF, d.T, d.D, d.D, packed + hd.dc_w, packed + hd.dc_iw, d.O, nullptr, 0, nullptr, nullptr, 0, y, d.O, ws, stream));
         hipLaunchKernelGGL(tx_shuffle_kernel, dim3(asd_grid_for((int64_t)d.T * d.O, 256)), dim3(256), 0, s, y, d.R, d.Cc, planes_cl + (int64_t)n * d.T * d.O, 0);
@@ -1489,28 +1486,21 @@ int asd_tritx_fwd(const asd_tritx_desc* desc, const float* const* params, const 
 
 // grads: 17 * n_layers + 4 device pointers (order: include/asd_hip.h; q|k|v and k|v gradients stacked), WRITTEN (summed over the batch)
 int asd_tritx_bwd(const asd_tritx_desc* desc, const float* const* params, const float* packed, const float* text_embed, int32_t batch,
-                  const float* d_planes_cl, const float* save, float* const* grads, float* ws, void* stream) {
+                  const float* d_planes_cl, const float* save, float* const* grads, float* workspace, void* stream) {
     TXS(tx_check_desc(desc));
-    ASD_CHECK_ARG(params && packed && text_embed && d_planes_cl && save && grads && ws && batch > 0, "null argument");
+    ASD_CHECK_ARG(params && packed && text_embed && d_planes_cl && save && grads && workspace && batch > 0, "null argument");
     const TxDims d(*desc);
     hipStream_t s = (hipStream_t)stream;
-    const int64_t per_layer = tx_pack_layout(d, 0).end;
-    const TxPackHead hd = tx_pack_head(d, per_layer * d.layers);
+    const TxPacked hd = tx_packed_layout(d);
     const TxSave S = tx_save_layout(d);
+    const TxWs W = tx_ws_layout(d);
+    float* const ws = workspace + W.op;      // what every building block is handed
     const int64_t TD = (int64_t)d.T * d.D;
-    float* p = ws + tx_op_ws(d);
-    float* dxa = p; p += tx_al(TD);
-    float* dxb = p; p += tx_al(TD);
-    float* dn = p; p += tx_al(TD);
-    float* dob = p; p += tx_al(TD);
-    float* dqkv = p; p += 3 * tx_al(TD);
-    float* dkv = p; p += tx_al((int64_t)d.Tc * 2 * d.D);
-    float* du = p; p += tx_al((int64_t)d.T * d.F);
-    float* dy = p; p += tx_al((int64_t)d.T * d.O);
-    h16* cond_planes = reinterpret_cast<h16*>(p); p += tx_al((int64_t)d.Dc * 3 * tx_rp(d.Tc) / 2 + 64);      // text tokens^T [Dc, 3 Tcp]: one split for all layers
-    float* cond_inv = p; p += tx_al(d.Dc);
-    unsigned* cond_max = reinterpret_cast<unsigned*>(p); p += tx_al(d.Dc);
-    (void)p;      // (a staging area follows in the workspace layout: unused since the weight gradients accumulate in their epilogue)
+    float *dxa = workspace + W.dxa, *dxb = workspace + W.dxb, *dn = workspace + W.dn, *dob = workspace + W.dob;
+    float *dqkv = workspace + W.dqkv, *dkv = workspace + W.dkv, *du = workspace + W.du, *dy = workspace + W.dy;
+    h16* cond_planes = reinterpret_cast<h16*>(workspace + W.cond_planes);
+    float* cond_inv = workspace + W.cond_inv;
+    unsigned* cond_max = reinterpret_cast<unsigned*>(workspace + W.cond_max);
     // LayerNorm gradients accumulate over layers' rows and the batch, bias gradients are atomic column sums: zero them once — or take the
     // caller's word that it did (desc->grads_prezeroed: the Python side carves all of them out of one zeroed buffer)
     float* const* GH = grads + 17 * d.layers;       // pos_embed, norm.w, norm.b, deconv.w
@@ -1523,7 +1513,7 @@ int asd_tritx_bwd(const asd_tritx_desc* desc, const float* const* params, const 
         tx_memset0(GH[2], (size_t)d.D * 4, s);
     }
     struct PoolGuard { ~PoolGuard() { tx_pool = {nullptr, 0, false}; } } pool_guard;
-    unsigned* pool = reinterpret_cast<unsigned*>(ws + (asd_tritx_workspace_floats(desc) - tx_pool_words(d) - 256));
+    unsigned* pool = reinterpret_cast<unsigned*>(workspace + W.pool);
     // weight gradients of batch element n > 0 are added to those of the elements before it — in the product's own epilogue (residual = dw)
     const h16* xpl = nullptr;          // precomputed transposed planes of x (+ scales) / column bounds of x for the NEXT wgrad call
     const float* xinv = nullptr;
@@ -1536,13 +1526,11 @@ int asd_tritx_bwd(const asd_tritx_desc* desc, const float* const* params, const 
     for (int n = 0; n < batch; ++n) {
         const bool acc = n > 0;
         tx_memset0(pool, (size_t)tx_pool_words(d) * 4, s);
-        // bias gradients of the first batch element land in caller-zeroed cells; later elements go through the staging buffer (own memset)
+        // bias gradients of the first batch element land in caller-zeroed cells; later elements add to them
         tx_pool = {pool, (size_t)tx_pool_words(d), desc->grads_prezeroed != 0 && !acc};
-        const float* sv = save + (int64_t)n * tx_save_per_sample(d);
+        const float* sv = save + (int64_t)n * S.per_sample;
         const float* cond = text_embed + (int64_t)n * d.Tc * d.Dc;
-        const float* xf = sv + (int64_t)d.layers * S.end;
-        const float* stF = xf + tx_al(TD);
-        const float* nF = stF + tx_al(2 * d.T);
+        const float *xf = sv + S.xf, *stF = sv + S.stF, *nF = sv + S.nF;
         {   // the text tokens' transposed planes, once per batch element
             tx_memset0(cond_max, (size_t)d.Dc * 4, s);
             hipLaunchKernelGGL(tx_colstat_kernel, dim3(asd_div_up(d.Dc, 64), asd_div_up(d.Tc, 256)), dim3(256), 0, s, cond, d.Tc, d.Dc, d.Dc, 256, cond_max, (float*)nullptr);
@@ -1559,13 +1547,14 @@ int asd_tritx_bwd(const asd_tritx_desc* desc, const float* const* params, const 
         float* dx_other = dxb;
         // (every LayerNorm backward leaves the operand planes of its dx where the next input-gradient Linear looks for them: that Linear runs
         // BEFORE the weight gradient that shares dx with it, whose workspace would overwrite the planes)
-        h16* const lp = tx_linear_planes_of(ws);
-        float* const li = tx_linear_inv_of(ws, d.T, d.D);
+        const TxLinearWs LN = tx_linear_ws(d.T, d.D, d.D);
+        h16* const lp = reinterpret_cast<h16*>(ws + LN.planes);
+        float* const li = ws + LN.inv;
         TXS(tx_layernorm_bwd_core(dn, xf, stF, params[20 * d.layers + 1], d.T, d.D, nullptr, dx, GH[1], GH[2], lp, li, stream));
         for (int l = d.layers - 1; l >= 0; --l) {
             const float* const* P = params + 20 * l;
             float* const* G = grads + 17 * l;
-            const TxPackLayer L = tx_pack_layout(d, per_layer * l);
+            const TxPackLayer L = tx_pack_layout(d, hd.per_layer * l);
             const float* B = sv + (int64_t)l * S.end;
             // ---- MLP: x3 = x2 + fc2(gelu(fc1(n3)))
             TXS(tx_linear_core(dx, d.T, d.D, d.D, packed + L.fc2_t, packed + L.fc2_it, d.F, nullptr, 2, const_cast<float*>(B + S.u), nullptr, 0, du, d.F, ws, true, stream));

@@ -214,6 +214,127 @@ def test_conv3d_passes_stay_inside_their_buffers():
         assert torch.isfinite(out.view(torch.float32)).all()
 
 
+# ---- the tri-plane transformer (csrc/tritx.hip): every workspace is exactly what its size query returns, inside a sentinel allocation; every
+# output sits in a guarded allocation of its own ----
+def _guarded_f32(*shape):
+    n = int(np.prod(shape))
+    buf, v = _guarded(n * 4)
+    return buf, v.view(torch.float32).view(*shape), n * 4
+
+
+def _all_intact(bufs):
+    return all(_intact(b, nb) for b, _, nb in bufs)
+
+
+def _tx_pack(w):
+    """operand plane + scales of an nn.Linear weight [N, K]"""
+    from scaledreamer_amd import _lib
+
+    N, K = w.shape
+    plane, inv = torch.empty((N, 3 * K), device="cuda", dtype=torch.float16), torch.empty(N, device="cuda")
+    _lib.check(_lib.lib().asd_tx_pack_weight(_lib.ptr(w), _lib.i32(N), _lib.i32(K), _lib.ptr(plane), _lib.ptr(inv), None, None, None, _lib.stream()))
+    return plane, inv
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("M,K,N", [(3072, 3072, 768), (200, 64, 128)])      # split-K 3 in the plan table / outside it
+def test_tx_linear_stays_inside_its_buffers(M, K, N, mode):
+    from scaledreamer_amd import _lib
+
+    L = _lib.lib()
+    g = torch.Generator(device="cuda").manual_seed(M + N)
+    x = torch.randn(M, K, device="cuda", generator=g)
+    plane, inv = _tx_pack(torch.randn(N, K, device="cuda", generator=g) * K ** -0.5)
+    bias = torch.randn(N, device="cuda", generator=g)
+    ws, y, aux = _guarded_f32(L.asd_tx_linear_workspace(_lib.i32(M), _lib.i32(N), _lib.i32(K))), _guarded_f32(M, N), _guarded_f32(M, N)
+    _lib.check(L.asd_tx_linear(_lib.ptr(x), _lib.i32(M), _lib.i32(K), _lib.i32(K), _lib.ptr(plane), _lib.ptr(inv), _lib.i32(N), _lib.ptr(bias), _lib.i32(mode),
+                               _lib.ptr(aux[1]) if mode else None, None, _lib.i32(N), _lib.ptr(y[1]), _lib.i32(N), _lib.ptr(ws[1]), _lib.stream()))
+    torch.cuda.synchronize()
+    assert _all_intact((ws, y, aux)), "asd_tx_linear wrote outside its workspace or an output"
+    assert torch.isfinite(y[1]).all() and (mode == 0 or torch.isfinite(aux[1]).all())
+
+
+@pytest.mark.parametrize("M,N,K", [(3072, 768, 3072), (130, 64, 128)])      # split-K 3 in the plan table / outside it
+def test_tx_linear_wgrad_stays_inside_its_buffers(M, N, K):
+    from scaledreamer_amd import _lib
+
+    L = _lib.lib()
+    g = torch.Generator(device="cuda").manual_seed(M + K)
+    dy, x = torch.randn(M, N, device="cuda", generator=g), torch.randn(M, K, device="cuda", generator=g)
+    ws, dw, db = _guarded_f32(L.asd_tx_wgrad_workspace(_lib.i32(M), _lib.i32(N), _lib.i32(K))), _guarded_f32(N, K), _guarded_f32(N)
+    _lib.check(L.asd_tx_linear_wgrad(_lib.ptr(dy), _lib.i32(N), _lib.ptr(x), _lib.i32(K), _lib.i32(M), _lib.i32(N), _lib.i32(K), _lib.ptr(dw[1]), _lib.ptr(db[1]),
+                                     _lib.ptr(ws[1]), _lib.stream()))
+    torch.cuda.synchronize()
+    assert _all_intact((ws, dw, db)), "asd_tx_linear_wgrad wrote outside its workspace or an output"
+    assert torch.isfinite(dw[1]).all() and torch.isfinite(db[1]).all()
+
+
+# shapes of test_gpu_tritx.py: forward, dK / dV and dQ all split | only dK / dV split (16 pieces: the largest partials) | nothing split
+@pytest.mark.parametrize("Lq,Lk,H", [(3072, 3072, 16), (3072, 77, 16), (100, 50, 2)])
+def test_tx_attention_passes_stay_inside_their_buffers(Lq, Lk, H):
+    from scaledreamer_amd import _lib
+
+    L = _lib.lib()
+    g = torch.Generator(device="cuda").manual_seed(Lq + Lk)
+    D = H * 48
+    q, k, v = (torch.randn(n, D, device="cuda", generator=g) for n in (Lq, Lk, Lk))
+    d_o = torch.randn(Lq, D, device="cuda", generator=g) * 1e-3
+    nws = L.asd_tx_attention_workspace(_lib.i32(Lq), _lib.i32(Lk), _lib.i32(H))
+    ws, o, lse = _guarded_f32(nws), _guarded_f32(Lq, D), _guarded_f32(H, Lq)
+    ld = _lib.i32(D)
+    _lib.check(L.asd_tx_attention_fwd(_lib.ptr(q), ld, _lib.ptr(k), ld, _lib.ptr(v), ld, _lib.i32(Lq), _lib.i32(Lk), _lib.i32(H), _lib.ptr(o[1]), ld, _lib.ptr(lse[1]),
+                                      _lib.ptr(ws[1]), _lib.stream()))
+    torch.cuda.synchronize()
+    assert _all_intact((ws, o, lse)), "asd_tx_attention_fwd wrote outside its workspace or an output"
+    assert torch.isfinite(o[1]).all() and torch.isfinite(lse[1]).all()
+    ws, dq, dk, dv = _guarded_f32(nws), _guarded_f32(Lq, D), _guarded_f32(Lk, D), _guarded_f32(Lk, D)      # the same query serves the backward
+    _lib.check(L.asd_tx_attention_bwd(_lib.ptr(q), ld, _lib.ptr(k), ld, _lib.ptr(v), ld, _lib.ptr(o[1]), ld, _lib.ptr(d_o), ld, _lib.ptr(lse[1]), _lib.i32(Lq),
+                                      _lib.i32(Lk), _lib.i32(H), _lib.ptr(dq[1]), ld, _lib.ptr(dk[1]), ld, _lib.ptr(dv[1]), ld, _lib.ptr(ws[1]), _lib.stream()))
+    torch.cuda.synchronize()
+    assert _all_intact((ws, o, lse, dq, dk, dv)), "asd_tx_attention_bwd wrote outside its workspace or an output"
+    assert all(torch.isfinite(t[1]).all() for t in (dq, dk, dv))
+
+
+def test_tritx_generator_passes_stay_inside_their_buffers():
+    """asd_tritx_pack / _fwd / _bwd at the reduced shape of test_gpu_tritx.py (TRI_HD48: 2 layers x 192 wide, 4 heads, 3 x 8^2 tokens), batch 2: the
+    packed planes, the saved activations and the workspace are exactly what their queries return; the planes and each of the 38 gradients have a
+    guarded allocation of their own.  (The packed buffer holds fp16 planes and bit patterns: its contents are judged through the planes they produce.)"""
+    from scaledreamer_amd import _lib
+
+    L = _lib.lib()
+    nl, D, H, Dc, Tc, F, R, Cc, batch = 2, 192, 4, 128, 77, 768, 8, 32, 2
+    T = 3 * R * R
+    desc = _lib.TritxDesc(n_layers=nl, dim=D, heads=H, cond_dim=Dc, cond_tokens=Tc, hidden=F, low_res=R, out_channels=Cc, eps=1e-6)
+    g = torch.Generator(device="cuda").manual_seed(48)
+    layer = [(D,), (D,), (D, D), (D, Dc), (D, Dc), (D, D), (D,), (D,), (D,), (D, D), (D, D), (D, D), (D, D), (D,), (D,), (D,), (F, D), (F,), (D, F), (D,)]
+    shapes = layer * nl + [(T, D), (D,), (D,), (D, 4 * Cc)]
+    params = [torch.randn(*sh, device="cuda", generator=g) * (0.2 if len(sh) == 2 else 1.0) for sh in shapes]
+    table = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
+    text = torch.randn(batch, Tc, Dc, device="cuda", generator=g)
+    packed = _guarded_f32(L.asd_tritx_packed_floats(C.byref(desc)))
+    _lib.check(L.asd_tritx_pack(C.byref(desc), table, _lib.ptr(packed[1]), _lib.stream()))
+    torch.cuda.synchronize()
+    assert _all_intact((packed,)), "asd_tritx_pack wrote outside the packed buffer"
+    nws = L.asd_tritx_workspace_floats(C.byref(desc))
+    save, ws, planes = _guarded_f32(L.asd_tritx_save_floats(C.byref(desc), _lib.i32(batch))), _guarded_f32(nws), _guarded_f32(batch, 3, 2 * R, 2 * R, Cc)
+    _lib.check(L.asd_tritx_fwd(C.byref(desc), table, _lib.ptr(packed[1]), _lib.ptr(text), _lib.i32(batch), _lib.ptr(planes[1]), _lib.ptr(save[1]), _lib.ptr(ws[1]),
+                               _lib.stream()))
+    torch.cuda.synchronize()
+    assert _all_intact((packed, save, ws, planes)), "asd_tritx_fwd wrote outside a buffer"
+    assert torch.isfinite(planes[1]).all()
+    glayer = [(D,), (D,), (D, D), (2 * D, Dc), (D, D), (D,), (D,), (D,), (3 * D, D), (D, D), (D,), (D,), (D,), (F, D), (F,), (D, F), (D,)]
+    grads = [_guarded_f32(*sh) for sh in glayer * nl + [(T, D), (D,), (D,), (D, 4 * Cc)]]
+    gtable = (C.c_void_p * len(grads))(*[t[1].data_ptr() for t in grads])
+    d_planes = torch.randn(batch, 3, 2 * R, 2 * R, Cc, device="cuda", generator=g)
+    ws = _guarded_f32(nws)
+    _lib.check(L.asd_tritx_bwd(C.byref(desc), table, _lib.ptr(packed[1]), _lib.ptr(text), _lib.i32(batch), _lib.ptr(d_planes), _lib.ptr(save[1]), gtable,
+                               _lib.ptr(ws[1]), _lib.stream()))
+    torch.cuda.synchronize()
+    assert _all_intact([packed, save, ws, planes] + grads), "asd_tritx_bwd wrote outside a buffer"
+    for i, t in enumerate(grads):
+        assert torch.isfinite(t[1]).all(), i
+
+
 def test_passes_without_atomics_are_bit_identical_and_the_scatter_is_bounded():
     from scaledreamer_amd import ops
     from scaledreamer_amd.smoke import build_smoke_system

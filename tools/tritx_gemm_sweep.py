@@ -13,7 +13,13 @@ TILES = ["128x64", "128x128", "256x64", "256x128", "128x320", "256x256", "256x32
 BN = [64, 128, 64, 128, 320, 256, 320, 128]
 SHAPES = [(3072, 768, 2304), (3072, 2304, 2304), (3072, 3072, 2304), (3072, 768, 9216), (3072, 768, 6912), (77, 1536, 3072), (3072, 128, 2304), (3072, 768, 384),
           (768, 768, 9216), (2304, 768, 9216), (3072, 768, 9216), (768, 3072, 9216), (1536, 1024, 384), (768, 128, 9216)]
+NAMED = {"128x64", "128x128", "256x64", "256x128", "256x256", "320x128"}      # rows with an ASD_CFG_* name in csrc/gemm_tile.h
 zero = torch.zeros(64, device="cuda")
+
+
+def cfg_name(t):
+    """tile_cfg of row t as tx_plans[] spells it: the row's name + 1 (a row without a name needs one in gemm_tile.h first)"""
+    return f"ASD_CFG_{TILES[t]} + 1" if TILES[t] in NAMED else f"{t + 1} /* {TILES[t]}: name this row in gemm_tile.h */"
 
 
 def run(a, w, c, ws, M, N, K, cfg, sk):
@@ -50,7 +56,7 @@ for M, N, K in SHAPES:
                 continue
             us = timeit(lambda: run(a, w, c, ws, M, N, K, t, sk))
             if us is not None:
-                res.append((us, TILES[t], t + 1, sk))
+                res.append((us, TILES[t], cfg_name(t), sk))
     res.sort()
     fl = 2.0 * M * N * K
     print(f"M={M:5d} N={N:5d} K={K:5d}: " + "  ".join(f"{n} sk{sk} {us:6.1f}us ({fl / us / 1e6:5.0f}TF)" for us, n, _, sk in res[:4]) + f"   PLAN {{{M}, {N}, {K}, {res[0][2]}, {res[0][3]}}},")
