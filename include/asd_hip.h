@@ -816,6 +816,62 @@ int asd_comm_create(const void* id128, int32_t rank, int32_t world, asd_comm** c
 int asd_comm_destroy(asd_comm* comm);
 int asd_allreduce_mean_f32(asd_comm* comm, float* buf, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Mesh extraction (csrc/mesh.hip): marching tetrahedra, connected components, compaction.  Replaces
+ * MarchingTetrahedraHelper._forward (threestudio/models/isosurface.py:168-227) and trimesh's split / concatenate in Mesh.remove_outlier
+ * (threestudio/models/mesh.py:31-94).  The tetrahedral grid is given in one of two forms:
+ *   explicit (res = 0)  verts[n_grid,3], edges[n_edges,2] (unique, a < b, sorted as torch.unique sorts them: the reference's all_edges,
+ *                       isosurface.py:143-156), tet_verts[n_tets,4] (`indices` of load/tets/{res}_tets.npz), tet_edges[n_tets,6]: the rows of
+ *                       `edges` of every tet's edges 01 02 03 12 13 23 (base_tet_edges, isosurface.py:109-114).  int32 indices.
+ *   Kuhn (res >= 2)     vertices linspace(0,1,res)^3 in `ij` order (MarchingCubeCPUHelper.grid_vertices, isosurface.py:32-46), each cell split
+ *                       into the six tetrahedra around its main diagonal; edge and tet tables are closed-form and never materialised.
+ *                       The edge / tet / vertex arguments are ignored; `axis` [res] holds linspace(0,1,res), the coordinates of one axis.
+ * `level` [n_grid | res^3]: an edge crosses when exactly one end has level > 0; one vertex per crossing edge, in edge order; the faces of
+ * tet after tet, wound as the reference's triangle table winds them.  No atomics: the same bits every run.
+ * Sequence: asd_mt_count (flags, counts, both scans; the totals land in workspace[layout.counts .. +2] = n_verts, n_faces), ONE host read
+ * of those two, allocation, asd_mt_emit with the same workspace.  The workspace is int32; asd_mt_workspace and both passes derive every
+ * offset from the same layout function.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct asd_mt_layout {          /* offsets in int32 from the workspace start, every region on a 256-byte boundary */
+    int64_t n_edge_slots;               /* n_edges | 7 res^3: vertex v owns slots 7 v + d - 1, d = (di dj dk) the offset of the far end */
+    int64_t n_tet_slots;                /* n_tets  | 6 (res-1)^3: cell c owns slots 6 c + t */
+    int64_t edge_off;                   /* [n_edge_slots] crossing flags, then their exclusive scan: the vertex an edge produces */
+    int64_t tet_off;                    /* [n_tet_slots] triangle counts, then their exclusive scan: the first face of a tet */
+    int64_t scan;                       /* asd_scan_i32_blocks_workspace(max(n_edge_slots, n_tet_slots)) */
+    int64_t counts;                     /* [2] n_verts, n_faces */
+    int64_t total;
+} asd_mt_layout;
+/* [host] either output may be NULL */
+int asd_mt_workspace(int32_t res, int64_t n_edges, int64_t n_tets, asd_mt_layout* layout, int64_t* n_ints);
+int asd_mt_count(const float* level, int32_t res, int64_t n_grid, const int32_t* edges, int64_t n_edges, const int32_t* tet_verts,
+                 int64_t n_tets, int32_t* workspace, void* stream);
+/* v = p_a w_a + p_b w_b, w_a = -s_b / (s_a - s_b), w_b = s_a / (s_a - s_b) for edge (a, b), a < b (isosurface.py:195-202), IEEE division.
+ * out_verts [n_verts_out,3], out_faces [n_faces_out,3] int64 (a torch.long t_pos_idx); nothing is written past either size. */
+int asd_mt_emit(const float* level, int32_t res, const float* axis, const float* verts, int64_t n_grid, const int32_t* edges, int64_t n_edges,
+                const int32_t* tet_verts, const int32_t* tet_edges, int64_t n_tets, const int32_t* workspace, int64_t n_verts_out,
+                int64_t n_faces_out, float* out_verts, int64_t* out_faces, void* stream);
+/* [host] the 16 cases as table[16][7]: number of triangles, then the local edge ids (01 02 03 12 13 23 -> 0..5) of their corners, -1 behind
+ * them; case index: bit v set iff level[tet vertex v] > 0.  The table the kernels read; it is derived (mesh.hip), not copied. */
+int asd_mt_case_table(int32_t* table);
+/* Exclusive scan over any number of blocks: offset[i] = sum_{k<i} count[k], total[0] = the sum (asd_scan_i32 is one block and stays the
+ * marcher's).  n < 2^31, count 16-byte aligned, offset == count allowed; workspace: asd_scan_i32_blocks_workspace int32. */
+int asd_scan_i32_blocks_workspace(int64_t n, int64_t* n_ints);
+int asd_scan_i32_blocks(const int32_t* count, int64_t n, int32_t* offset, int32_t* total, int32_t* workspace, void* stream);
+/* Connected components by shared VERTEX (trimesh's split joins faces by shared edge: the two differ where components touch in one
+ * vertex).  One round = min-label hooking over the faces + pointer jumping; `first` != 0 starts from labels[v] = v.  changed[0] (device)
+ * is 1 if the round lowered a label, else 0: the caller repeats until it is 0, and then labels[v] is the smallest vertex of v's component. */
+int asd_mesh_cc_round(const int64_t* faces /*[n_faces,3]*/, int64_t n_faces, int64_t n_verts, int32_t first, int32_t* labels /*[n_verts]*/,
+                      int32_t* changed /*[1]*/, void* stream);
+/* counts[l] = faces whose first corner carries label l (0 for every other entry), [n_verts] */
+int asd_mesh_face_counts(const int64_t* faces, int64_t n_faces, int64_t n_verts, const int32_t* labels, int32_t* counts, void* stream);
+/* v_keep[v] = counts[labels[v]] >= threshold, f_keep[f] likewise by its first corner (mesh.py:71) */
+int asd_mesh_keep(const int64_t* faces, int64_t n_faces, int64_t n_verts, const int32_t* labels, const int32_t* counts, int32_t threshold,
+                  int32_t* v_keep /*[n_verts]*/, int32_t* f_keep /*[n_faces]*/, void* stream);
+/* order-preserving compaction: v_map / f_map are the exclusive scans of the keep flags, faces are re-indexed through v_map */
+int asd_mesh_compact(const float* v_pos, const int64_t* faces, int64_t n_verts, int64_t n_faces, const int32_t* v_keep, const int32_t* v_map,
+                     const int32_t* f_keep, const int32_t* f_map, int64_t n_verts_out, int64_t n_faces_out, float* v_out, int64_t* f_out,
+                     void* stream);
+
 /* library info */
 const char* asd_version(void);
 const char* asd_last_error(void);

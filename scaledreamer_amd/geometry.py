@@ -16,7 +16,7 @@ import torch.nn.functional as F
 from . import _lib, ops
 from .base import BaseModule
 from .networks import VanillaMLP, get_activation, get_encoding, get_mlp
-from .registry import register, warn
+from .registry import debug, info, register, warn
 
 
 def scale_tensor(dat, inp_scale, tgt_scale):
@@ -60,10 +60,86 @@ class BaseImplicitGeometry(BaseModule):
     def configure(self) -> None:
         r = self.cfg.radius
         self.register_buffer("bbox", torch.as_tensor([[-r, -r, -r], [r, r, r]], dtype=torch.float32))
+        self.isosurface_helper = None
         self.unbounded = False
 
+    # ---- mesh extraction (geometry/base.py:85-188) ------------------------------------------------
+    def _initilize_isosurface_helper(self):
+        if not self.cfg.isosurface or self.isosurface_helper is not None:
+            return
+        import os
+
+        from .isosurface import MarchingTetrahedraGridHelper, MarchingTetrahedraHelper
+
+        method, res = self.cfg.isosurface_method, self.cfg.isosurface_resolution
+        if method == "mt":
+            path = f"load/tets/{res}_tets.npz"
+            if not os.path.exists(path):
+                raise FileNotFoundError(f'isosurface_method "mt" needs the tetrahedral grid {path}, which is not there; '
+                                        'isosurface_method "mt-grid" runs marching tetrahedra over a regular grid and needs no file')
+            self.isosurface_helper = MarchingTetrahedraHelper(res, path).to(self.device)
+        elif method == "mt-grid":
+            self.isosurface_helper = MarchingTetrahedraGridHelper(res).to(self.device)
+        elif method == "mc-cpu":
+            raise NotImplementedError('isosurface_method "mc-cpu" needs PyMCubes, which this port does not use; '
+                                      '"mt-grid" is the method that needs no file')
+        else:
+            raise AttributeError(f"Unknown isosurface method {method}")
+
+    def forward_field(self, points):
+        raise NotImplementedError
+
+    def forward_level(self, field, threshold):
+        raise NotImplementedError
+
+    def _isosurface(self, bbox: torch.Tensor, fine_stage: bool = False):
+        helper = self.isosurface_helper
+        assert helper is not None
+        grid = helper.grid_vertices
+        chunk = self.cfg.isosurface_chunk if self.cfg.isosurface_chunk > 0 else grid.shape[0]
+        fields, deformations = [], []
+        for i in range(0, grid.shape[0], chunk):       # chunk_batch(batch_func, isosurface_chunk, grid_vertices), base.py:120-140
+            x = grid[i:i + chunk]
+            f, d = self.forward_field(scale_tensor(x.to(bbox.device), helper.points_range, bbox))
+            fields.append(f.to(x.device))
+            deformations.append(None if d is None else d.to(x.device))
+        field = torch.cat(fields, dim=0)
+        deformation = None if deformations[0] is None else torch.cat(deformations, dim=0)
+        if isinstance(self.cfg.isosurface_threshold, float):
+            threshold = self.cfg.isosurface_threshold
+        elif self.cfg.isosurface_threshold == "auto":
+            eps = 1.0e-5
+            threshold = field[field > eps].mean().item()
+            info(f"Automatically determined isosurface threshold: {threshold}")
+        else:
+            raise TypeError(f"Unknown isosurface_threshold {self.cfg.isosurface_threshold}")
+        level = self.forward_level(field, threshold)
+        mesh = helper(level, deformation=deformation)
+        mesh.v_pos = scale_tensor(mesh.v_pos, helper.points_range, bbox)
+        mesh.add_extra("bbox", bbox)
+        if self.cfg.isosurface_remove_outliers:
+            mesh = mesh.remove_outlier(self.cfg.isosurface_outlier_n_faces_threshold)
+        return mesh
+
     def isosurface(self):
-        raise NotImplementedError("mesh extraction is post-training asset export (SURVEY.md §2.1 #17): out of scope")
+        if not self.cfg.isosurface:
+            raise NotImplementedError("Isosurface is not enabled in the current configuration")
+        self._initilize_isosurface_helper()
+        if self.cfg.isosurface_coarse_to_fine:
+            debug("First run isosurface to get a tight bounding box ...")
+            with torch.no_grad():
+                mesh_coarse = self._isosurface(self.bbox)
+            if mesh_coarse.v_pos.shape[0] == 0:
+                raise ValueError("the coarse isosurface pass found no surface: no grid edge crosses isosurface_threshold "
+                                 f"{self.cfg.isosurface_threshold!r}")
+            vmin, vmax = mesh_coarse.v_pos.amin(dim=0), mesh_coarse.v_pos.amax(dim=0)
+            vmin_ = (vmin - (vmax - vmin) * 0.1).max(self.bbox[0])
+            vmax_ = (vmax + (vmax - vmin) * 0.1).min(self.bbox[1])
+            debug("Run isosurface again with the tight bounding box ...")
+            with torch.no_grad():       # the extracted mesh is not differentiable here (no DMTet stage): no graph over the grid's field values
+                return self._isosurface(torch.stack([vmin_, vmax_], dim=0), fine_stage=True)
+        with torch.no_grad():
+            return self._isosurface(self.bbox)
 
 
 class _FieldFn(torch.autograd.Function):

@@ -8,7 +8,7 @@ import torch
 
 from .base import BaseModule
 from .networks import get_activation, get_mlp
-from .registry import register
+from .registry import register, warn
 
 
 class BaseMaterial(BaseModule):
@@ -63,3 +63,11 @@ class NoMaterial(BaseMaterial):
             return get_activation(self.cfg.color_activation)(features)
         color = self.network(features.view(-1, features.shape[-1])).view(*features.shape[:-1], self.cfg.n_output_dims)
         return get_activation(self.cfg.color_activation)(color)
+
+    def export(self, features: torch.Tensor, **kwargs):
+        """no_material.py:56-65: the colour as `albedo`, clamped; only three-channel colours can be exported"""
+        color = self(features, **kwargs).clamp(0, 1)
+        assert color.shape[-1] >= 3, "Output color must have at least 3 channels"
+        if color.shape[-1] > 3:
+            warn("Output color has >3 channels, treating the first 3 as RGB")
+        return {"albedo": color[..., :3]}

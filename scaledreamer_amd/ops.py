@@ -674,3 +674,91 @@ def trifield_bwd(planes_cl, cfg: FieldCfg, weights6, points, sdf, d_sdf, d_featu
     check(lib().asd_trifield_bwd(ptr(planes_cl), i32(H), i32(W), i32(Cc), C.byref(cfg), _ptr6(weights6), ptr(points), ptr(sdf), i32(n), k(d_sdf),
                                  k(d_features), k(d_normal), k(d_fd_grad), ptr(d_planes), _ptr6(dws), ptr(ws), stream()))
     return dws
+
+
+# ---- mesh extraction (csrc/mesh.hip) --------------------------------------------------------------
+def mt_layout(res: int, n_edges: int = 0, n_tets: int = 0) -> L.MtLayout:
+    lay = L.MtLayout()
+    check(lib().asd_mt_workspace(i32(res), C.c_int64(n_edges), C.c_int64(n_tets), C.byref(lay), None))
+    return lay
+
+
+def scan_i32_blocks(count: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """exclusive scan of an int32 vector of any length -> (offset, total[1])"""
+    _need_cuda(count)
+    count = _c(count, torch.int32)
+    n = count.shape[0]
+    ni = C.c_int64(0)
+    check(lib().asd_scan_i32_blocks_workspace(C.c_int64(n), C.byref(ni)))
+    ws = torch.empty(max(ni.value, 1), device=count.device, dtype=torch.int32)
+    offset = torch.empty_like(count)
+    total = torch.empty(1, device=count.device, dtype=torch.int32)
+    check(lib().asd_scan_i32_blocks(ptr(count), C.c_int64(n), ptr(offset), ptr(total), ptr(ws), stream()))
+    return offset, total
+
+
+def marching_tetrahedra(level: torch.Tensor, res: int = 0, axis: Optional[torch.Tensor] = None, verts: Optional[torch.Tensor] = None,
+                        edges: Optional[torch.Tensor] = None, tet_verts: Optional[torch.Tensor] = None,
+                        tet_edges: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (v_pos [Nv,3] fp32, t_pos_idx [Nf,3] int64).  res > 0: the Kuhn grid over linspace(0,1,res)^3 (`axis`); res == 0: the explicit
+    grid (int32 tables).  One host read (the two totals) between the count and the emit passes."""
+    _need_cuda(level)
+    level = _c(level).reshape(-1)
+    dev = level.device
+    if res > 0:
+        if level.shape[0] != res**3:
+            raise L.AsdError(f"level has {level.shape[0]} entries, the grid {res}^3")
+        axis = _c(axis if axis is not None else torch.linspace(0, 1, res, device=dev))
+        n_grid, n_edges, n_tets = res**3, 0, 0
+    else:
+        verts, edges, tet_verts, tet_edges = _c(verts), _c(edges, torch.int32), _c(tet_verts, torch.int32), _c(tet_edges, torch.int32)
+        n_grid, n_edges, n_tets = verts.shape[0], edges.shape[0], tet_verts.shape[0]
+        if level.shape[0] != n_grid or tet_edges.shape[0] != n_tets:
+            raise L.AsdError("level / verts / tet tables of different lengths")
+    lay = mt_layout(res, n_edges, n_tets)
+    ws = torch.empty(lay.total, device=dev, dtype=torch.int32)
+    check(lib().asd_mt_count(ptr(level), i32(res), C.c_int64(n_grid), ptr(edges), C.c_int64(n_edges), ptr(tet_verts), C.c_int64(n_tets),
+                             ptr(ws), stream()))
+    n_v, n_f = ws[lay.counts:lay.counts + 2].tolist()       # the one host read of an extraction
+    v_pos = torch.empty((n_v, 3), device=dev, dtype=torch.float32)
+    faces = torch.empty((n_f, 3), device=dev, dtype=torch.int64)
+    check(lib().asd_mt_emit(ptr(level), i32(res), ptr(axis), ptr(verts), C.c_int64(n_grid), ptr(edges), C.c_int64(n_edges), ptr(tet_verts),
+                            ptr(tet_edges), C.c_int64(n_tets), ptr(ws), C.c_int64(n_v), C.c_int64(n_f), ptr(v_pos), ptr(faces), stream()))
+    return v_pos, faces
+
+
+def mesh_components(faces: torch.Tensor, n_verts: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (labels [n_verts] int32: the smallest vertex of every vertex's component, counts [n_verts] int32: faces per label)"""
+    _need_cuda(faces)
+    faces = _c(faces, torch.int64)
+    dev, nf = faces.device, faces.shape[0]
+    labels = torch.empty(n_verts, device=dev, dtype=torch.int32)
+    counts = torch.empty(n_verts, device=dev, dtype=torch.int32)
+    changed = torch.zeros(1, device=dev, dtype=torch.int32)
+    first = 1
+    while True:         # every round lowers at least one label or is the last: at most n_verts rounds, in practice a handful
+        check(lib().asd_mesh_cc_round(ptr(faces), C.c_int64(nf), C.c_int64(n_verts), i32(first), ptr(labels), ptr(changed), stream()))
+        first = 0
+        if int(changed.item()) == 0:
+            break
+    check(lib().asd_mesh_face_counts(ptr(faces), C.c_int64(nf), C.c_int64(n_verts), ptr(labels), ptr(counts), stream()))
+    return labels, counts
+
+
+def mesh_keep_components(v_pos: torch.Tensor, faces: torch.Tensor, labels: torch.Tensor, counts: torch.Tensor, threshold: int):
+    """drop the components with fewer than `threshold` faces; vertex and face order are kept, faces re-indexed -> (v_pos, faces)"""
+    _need_cuda(v_pos, faces)
+    v_pos, faces = _c(v_pos), _c(faces, torch.int64)
+    dev, nv, nf = v_pos.device, v_pos.shape[0], faces.shape[0]
+    v_keep = torch.empty(nv, device=dev, dtype=torch.int32)
+    f_keep = torch.empty(nf, device=dev, dtype=torch.int32)
+    check(lib().asd_mesh_keep(ptr(faces), C.c_int64(nf), C.c_int64(nv), ptr(labels), ptr(counts), i32(threshold), ptr(v_keep), ptr(f_keep),
+                              stream()))
+    v_map, v_total = scan_i32_blocks(v_keep)
+    f_map, f_total = scan_i32_blocks(f_keep)
+    n_v, n_f = torch.cat([v_total, f_total]).tolist()
+    v_out = torch.empty((n_v, 3), device=dev, dtype=torch.float32)
+    f_out = torch.empty((n_f, 3), device=dev, dtype=torch.int64)
+    check(lib().asd_mesh_compact(ptr(v_pos), ptr(faces), C.c_int64(nv), C.c_int64(nf), ptr(v_keep), ptr(v_map), ptr(f_keep), ptr(f_map),
+                                 C.c_int64(n_v), C.c_int64(n_f), ptr(v_out), ptr(f_out), stream()))
+    return v_out, f_out

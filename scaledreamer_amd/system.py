@@ -282,6 +282,22 @@ class StableDreamer(nn.Module, Updateable):
             terms = terms + self._guidance_terms(normal_img, batch, "shape_", self.GEOMETRY_PASS_WEIGHT)
         return {"loss": self._assemble_loss(terms, out, lams, fused)}
 
+    def export(self, save_dir: str):
+        """`launch.py --export` (systems/base.py:327-340 on_predict_epoch_end -> SaverMixin.save_obj): build the exporter named by
+        cfg.exporter_type over this system's geometry / material / background, write what it returns under save_dir, return the paths."""
+        from .mesh import save_obj
+
+        exporter = find(self.cfg.exporter_type)(self.cfg.exporter, geometry=self.geometry, material=self.material, background=self.background)
+        paths = []
+        with torch.no_grad():
+            for out in exporter():
+                if out.save_type != "obj":
+                    raise NotImplementedError(f"exporter output of type {out.save_type!r}: only 'obj' is written")
+                p = out.params
+                paths.append(save_obj(os.path.join(save_dir, out.save_name), p["mesh"], save_normal=p["save_normal"],
+                                      save_vertex_color=p["save_vertex_color"]))
+        return paths
+
     def gradient_exchange(self):
         """the DP exchange object of this system (None on a single process): created on first use, after the process group."""
         if not asd_dist.is_distributed():
