@@ -872,6 +872,34 @@ int asd_mesh_compact(const float* v_pos, const int64_t* faces, int64_t n_verts, 
                      const int32_t* f_keep, const int32_t* f_map, int64_t n_verts_out, int64_t n_faces_out, float* v_out, int64_t* f_out,
                      void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Per-face UV atlas and its bake (csrc/atlas.hip): the texture route of the mesh exporter (threestudio/models/exporters/
+ * mesh_exporter.py:53-137) without xatlas, nvdiffrast or cv2.inpaint.  NOT xatlas's atlas: one cell per pair of faces, so the texture
+ * resolution per face is uniform rather than area-proportional, and there are 3 F texture vertices.
+ *   P = ceil(F / 2) cells, n = ceil(sqrt(P)) per row, cell side c = floor(T / n), leg L = c - 3 g - 1; cell k starts at texel
+ *   ((k % n) c, (k / n) c).  Cell-local, texel (i, j) centred at (i + 1/2, j + 1/2): face 2k is (g, g) (g + L, g) (g, g + L), face 2k + 1
+ *   is (c - g, c - g) (c - g - L, c - g) (c - g, c - g - L), corners 0 1 2 of the face.  Texel (i, j) belongs to the lower face when
+ *   i + j + 1 < c, to the upper one when i + j + 1 > c, to nobody when equal, when its (half-)cell has no face, or beyond n c.
+ *   v_tex = texel coordinate / T; texture[j, i] is sampled at ((i + 1/2) / T, (j + 1/2) / T).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct AsdAtlasLayout {
+    int32_t n_faces, texture_size, gutter;      /* what it was asked for */
+    int32_t n, c, L;                            /* cells per row, cell side, leg; all 0 when n_faces = 0 */
+} AsdAtlasLayout;
+/* [host] the one definition of the layout.  Refused (asd_last_error names F, T, g and the smallest texture_size that fits) when L < 1;
+ * texture_size in [1, 8192]; n_faces = 0 is accepted whatever the rest. */
+int asd_atlas_layout(int64_t n_faces, int32_t texture_size, int32_t gutter, AsdAtlasLayout* out);
+/* three texture vertices of its own per face: v_tex [3 n_faces, 2], t_tex_idx [n_faces, 3] = 3 f + corner */
+int asd_atlas_uv(const AsdAtlasLayout* layout, int64_t n_faces, float* v_tex, int64_t* t_tex_idx, void* stream);
+/* one thread per texel.  face_id [T,T]: the owning face, -1 = unowned (also a face with a corner outside [0, n_verts)); gb_pos [T,T,3]:
+ * the point of the owner's UV triangle nearest to the texel centre, mapped to 3-D by pos = (p0 b0 + p1 b1) + p2 b2, b_k = w_k fl(1 / L),
+ * no contraction (0 where unowned); covered [T,T]: 1 where the centre lies in the closed triangle.  gb_pos 16-byte, covered 4-byte aligned. */
+int asd_atlas_bake(const AsdAtlasLayout* layout, const float* v_pos, const int64_t* faces /*[n_faces,3]*/, int64_t n_verts, int64_t n_faces,
+                   float* gb_pos, int32_t* face_id, uint8_t* covered, void* stream);
+/* image[texel_index[k], ch] = (uint8) trunc(clip(values[k, ch], 0, 1) * 255) (get_rgb_image_, threestudio/utils/saving.py:82-86: truncation,
+ * not rounding); values [n_owned, C], C in [1, 4], image [n_texels, C] zeroed by the caller; an index outside [0, n_texels) writes nothing */
+int asd_atlas_pack_u8(const float* values, const int64_t* texel_index, int64_t n_owned, int32_t C, uint8_t* image, int64_t n_texels, void* stream);
+
 /* library info */
 const char* asd_version(void);
 const char* asd_last_error(void);

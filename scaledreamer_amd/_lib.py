@@ -144,6 +144,10 @@ class MtLayout(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("n_edge_slots", "n_tet_slots", "edge_off", "tet_off", "scan", "counts", "total")]
 
 
+class AtlasLayout(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_faces", "texture_size", "gutter", "n", "c", "L")]
+
+
 _lib: Optional[C.CDLL] = None
 
 # every symbol include/asd_hip.h declares (tests/test_abi.py checks the header against this list)
@@ -175,6 +179,7 @@ SYMBOLS = [
     "asd_tritx_packed_floats", "asd_tritx_save_floats", "asd_tritx_workspace_floats", "asd_tritx_pack", "asd_tritx_fwd", "asd_tritx_bwd",
     "asd_mt_workspace", "asd_mt_count", "asd_mt_emit", "asd_mt_case_table", "asd_scan_i32_blocks_workspace", "asd_scan_i32_blocks",
     "asd_mesh_cc_round", "asd_mesh_face_counts", "asd_mesh_keep", "asd_mesh_compact",
+    "asd_atlas_layout", "asd_atlas_uv", "asd_atlas_bake", "asd_atlas_pack_u8",
     "asd_comm_unique_id", "asd_comm_create", "asd_comm_destroy", "asd_allreduce_mean_f32",
     "asd_version", "asd_last_error", "asd_modulated_weights_fwd", "asd_modulated_weights_bwd", "asd_timestep_plus", "asd_loss_tail_fwd", "asd_loss_tail_bwd", "asd_probe_events", "asd_probe_mark",
 ]

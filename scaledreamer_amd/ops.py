@@ -762,3 +762,50 @@ def mesh_keep_components(v_pos: torch.Tensor, faces: torch.Tensor, labels: torch
     check(lib().asd_mesh_compact(ptr(v_pos), ptr(faces), C.c_int64(nv), C.c_int64(nf), ptr(v_keep), ptr(v_map), ptr(f_keep), ptr(f_map),
                                  C.c_int64(n_v), C.c_int64(n_f), ptr(v_out), ptr(f_out), stream()))
     return v_out, f_out
+
+
+# ---- per-face UV atlas (csrc/atlas.hip) -----------------------------------------------------------
+def atlas_layout(n_faces: int, texture_size: int, gutter: int = 1) -> L.AtlasLayout:
+    """the one definition of the atlas (cells per row n, cell side c, leg L); refuses through AsdError when the faces do not fit"""
+    lay = L.AtlasLayout()
+    check(lib().asd_atlas_layout(C.c_int64(n_faces), i32(texture_size), i32(gutter), C.byref(lay)))
+    return lay
+
+
+def atlas_uv(layout: L.AtlasLayout, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (v_tex [3F,2] fp32, t_tex_idx [F,3] int64): three texture vertices of its own per face"""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise L.AsdError("the HIP path needs a device (there is no CPU fallback)")
+    nf = layout.n_faces
+    v_tex = torch.empty((3 * nf, 2), device=dev, dtype=torch.float32)
+    t_tex_idx = torch.empty((nf, 3), device=dev, dtype=torch.int64)
+    check(lib().asd_atlas_uv(C.byref(layout), C.c_int64(nf), ptr(v_tex), ptr(t_tex_idx), stream()))
+    return v_tex, t_tex_idx
+
+
+def atlas_bake(layout: L.AtlasLayout, v_pos: torch.Tensor, faces: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (gb_pos [T,T,3] fp32, face_id [T,T] int32 with -1 = unowned, covered [T,T] uint8); one thread per texel"""
+    _need_cuda(v_pos, faces)
+    v_pos, faces = _c(v_pos), _c(faces, torch.int64)
+    dev, T = v_pos.device, layout.texture_size
+    if faces.shape[0] != layout.n_faces:
+        raise L.AsdError(f"the layout is for {layout.n_faces} faces, the mesh has {faces.shape[0]}")
+    gb_pos = torch.empty((T, T, 3), device=dev, dtype=torch.float32)
+    face_id = torch.empty((T, T), device=dev, dtype=torch.int32)
+    covered = torch.empty((T, T), device=dev, dtype=torch.uint8)
+    check(lib().asd_atlas_bake(C.byref(layout), ptr(v_pos), ptr(faces), C.c_int64(v_pos.shape[0]), C.c_int64(faces.shape[0]), ptr(gb_pos),
+                               ptr(face_id), ptr(covered), stream()))
+    return gb_pos, face_id, covered
+
+
+def atlas_pack_u8(values: torch.Tensor, texel_index: torch.Tensor, image: torch.Tensor) -> torch.Tensor:
+    """image.view(-1, C)[texel_index[k]] = uint8(trunc(clip(values[k], 0, 1) * 255)), in place; image [T,T,C] uint8, zeroed by the caller"""
+    _need_cuda(values, texel_index, image)
+    values, texel_index = _c(values), _c(texel_index, torch.int64)
+    if values.dim() != 2 or image.dtype != torch.uint8 or image.shape[-1] != values.shape[1] or texel_index.shape[0] != values.shape[0]:
+        raise L.AsdError(f"values {tuple(values.shape)}, texel_index {tuple(texel_index.shape)} and image {tuple(image.shape)} {image.dtype} do not fit")
+    n_texels = image.numel() // image.shape[-1]
+    check(lib().asd_atlas_pack_u8(ptr(values), ptr(texel_index), C.c_int64(values.shape[0]), i32(values.shape[1]), ptr(image), C.c_int64(n_texels),
+                                  stream()))
+    return image

@@ -294,8 +294,10 @@ class StableDreamer(nn.Module, Updateable):
                 if out.save_type != "obj":
                     raise NotImplementedError(f"exporter output of type {out.save_type!r}: only 'obj' is written")
                 p = out.params
-                paths.append(save_obj(os.path.join(save_dir, out.save_name), p["mesh"], save_normal=p["save_normal"],
-                                      save_vertex_color=p["save_vertex_color"]))
+                written = save_obj(os.path.join(save_dir, out.save_name), p["mesh"], save_normal=p["save_normal"],
+                                   save_vertex_color=p["save_vertex_color"], save_uv=p["save_uv"], save_mat=p["save_mat"], map_Kd=p["map_Kd"],
+                                   map_Ks=p["map_Ks"], map_Bump=p["map_Bump"], map_Pm=p["map_Pm"], map_Pr=p["map_Pr"], map_format=p["map_format"])
+                paths += written if isinstance(written, list) else [written]     # with a material: MTL and textures first, the OBJ last
         return paths
 
     def gradient_exchange(self):
