@@ -118,9 +118,7 @@ __global__ __launch_bounds__(256) void voxel_sample_fwd_kernel(const float* __re
 // group therefore walks RUN = 8 consecutive points, keeps the 8 corner sums of the current cell in registers and issues its
 // atomics only when the cell changes: the kernel is bound by the fp32 atomic rate, and this divides the atomic count by the
 // average run length (3-6 on the amortized configs).
-#ifndef SCATTER_RUN
 #define SCATTER_RUN 8
-#endif
 // Request-coalesced scatter (tools/atomic_probe2.hip: the atomic units retire ~21 G REQUESTS/s, and the lanes of one instruction that
 // fall into the same 64-byte block are one request): LPP lanes share a point and lane `sub` owns the channels sub, sub + LPP,
 // sub + 2 LPP ...  — so one atomic instruction of the group covers LPP CONSECUTIVE floats of a corner's channel-last feature row

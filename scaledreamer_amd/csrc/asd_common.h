@@ -240,9 +240,7 @@ __device__ __forceinline__ void asd_scatter(const asd_grid_meta& m, float* __res
 //   * levels < NPRIV (the coarsest, a few thousand entries that EVERY sample of the step updates: ~1 % of the atomics but ~10 % of
 //     the kernel's time — same-line serialisation, tools/field_bwd_ab.py): each XCD adds into its own copy `priv + xcd * priv_stride`
 //     (ASD_PRIV_COPIES copies, that many times fewer collisions per line); asd_priv_reduce_kernel folds the copies into dparams afterwards.
-#ifndef ASD_PRIV_COPIES
 #define ASD_PRIV_COPIES 8
-#endif
 template <int L, int NAGG, int NPRIV = 0, bool FINE = true>
 __device__ __forceinline__ void asd_scatter_runs(const asd_grid_meta& m, float* __restrict__ dparams, float x, float y,
                                                  float z, const float (&denc)[2 * L], bool active, float* __restrict__ priv = nullptr,
@@ -254,11 +252,7 @@ __device__ __forceinline__ void asd_scatter_runs(const asd_grid_meta& m, float* 
         unsigned xcc, copy;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
         copy = xcc & 7u;
-        if (ASD_PRIV_COPIES > 8) {   // more copies: the XCD's CUs are split by the low bits of their id (HW_ID[11:8])
-            unsigned hwid;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-            copy = copy * (ASD_PRIV_COPIES / 8) + ((hwid >> 8) & (ASD_PRIV_COPIES / 8 - 1));
-        }
+        static_assert(ASD_PRIV_COPIES == 8, "one copy per XCD");
         priv += (size_t)copy * priv_stride;
     }
 #pragma unroll

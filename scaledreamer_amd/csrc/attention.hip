@@ -44,24 +44,10 @@ __device__ __forceinline__ float rows_max(float v) {
     t = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     return max3f(__uint_as_float(t[0]), __uint_as_float(t[1]), -3.0e38f);
 }
-__device__ __forceinline__ float rows_sum(float v) {
-    auto t = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(t[0]) + __uint_as_float(t[1]);
-    t = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(t[0]) + __uint_as_float(t[1]);
-}
 
 #define HD 64      // head dim
-#ifndef ATTN_DEFER_LOG2
-#define ATTN_DEFER_LOG2 8.0f   // 0: rescale whenever a maximum moves (the first form)
-#endif
+#define ATTN_DEFER_LOG2 8.0f   // 0 would rescale whenever a maximum moves (the first form)
 #define KT 64      // keys per tile
-#ifndef ATTN_SCALAR_FMA
-#define ATTN_SCALAR_FMA 1
-#endif
-#ifndef ATTN_SUM_MFMA
-#define ATTN_SUM_MFMA 1   // 0: row sums on the vector pipe (the first form; A/B partner)
-#endif
 // queries per wave = 16 * QS, per block = 64 * QS (4 waves).  QS = 2: 128 registers, four waves per SIMD.  QS = 4 (self-attention
 // over >= 2048 keys): every K / V^T fragment read from LDS and every tile brought from L2 serves twice the MFMAs, half the barriers
 // per flop; 218 registers, two waves per SIMD: 210 -> 196 us at L = 4096 (same-box A/B), nothing at L = 1024, slower below.
@@ -141,7 +127,6 @@ __global__ __launch_bounds__(256, QS == 2 ? 4 : 2) void attention_fwd_kernel(con
     float m_run[QS];
 #pragma unroll
     for (int qs = 0; qs < QS; ++qs) m_run[qs] = -1e30f;
-#if ATTN_SUM_MFMA
     // Row sums on the matrix pipe: one more V^T fragment whose row 0 is all ones makes sum_k P[q][k] row 0 of a fifth output tile — the loop issues
     // ~112 vector slots per 16 scores (64 of them the exponentials) against 64 MFMAs per tile, and the matrix pipe is a third busy: 13 slots per query
     // group and tile (pairwise adds, the cross-lane sum, the running-sum update) become two MFMAs.  The sum is then the sum of the fp16-rounded
@@ -156,11 +141,6 @@ __global__ __launch_bounds__(256, QS == 2 ? 4 : 2) void attention_fwd_kernel(con
     for (int qs = 0; qs < QS; ++qs) lacc[qs] = floatx4{0.f, 0.f, 0.f, 0.f};
     const half_t one_or_zero = lq16 == 0 ? (half_t)1.f : (half_t)0.f;
     const half8 ones_row0 = {one_or_zero, one_or_zero, one_or_zero, one_or_zero, one_or_zero, one_or_zero, one_or_zero, one_or_zero};
-#else
-    float l_run[QS];
-#pragma unroll
-    for (int qs = 0; qs < QS; ++qs) l_run[qs] = 0.f;
-#endif
 
     const int n_tiles = (p.lk + KT - 1) / KT;
     const float sl2 = p.scale * 1.44269504088896340736f;   // softmax in the log2 domain
@@ -223,16 +203,13 @@ __global__ __launch_bounds__(256, QS == 2 ? 4 : 2) void attention_fwd_kernel(con
             const float m_new = grow ? max3f(m_run[qs], cand, -3.0e38f) : m_run[qs];
             const float alpha = grow ? __builtin_amdgcn_exp2f(m_run[qs] - m_new) : 1.f;
             const float2_ sl2v = {sl2, sl2}, nm = {-m_new, -m_new};
-#if !ATTN_SUM_MFMA
-            float2_ sum2 = {0.f, 0.f};
-#endif
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt) {
                 // wide form: single v_fma_f32 (asm: -O3 would pack neighbours into v_pk_fma_f32 again, which costs more than two plain FMAs beside
                 // MFMAs: MI355X_MICROARCH.md, per-instruction cycle constants — L = 4096: 179 -> 171 us); narrow form (four waves per SIMD at 128
                 // registers): v_pk_fma_f32, two exponents per instruction (with single FMAs L = 1024 goes 31 -> 38 us)
                 float2_ x01, x23;
-                if constexpr (QS == 4 && ATTN_SCALAR_FMA) {
+                if constexpr (QS == 4) {
                     x01 = float2_{fma1(s[kt][qs][0], sl2, -m_new), fma1(s[kt][qs][1], sl2, -m_new)};
                     x23 = float2_{fma1(s[kt][qs][2], sl2, -m_new), fma1(s[kt][qs][3], sl2, -m_new)};
                 } else {
@@ -241,25 +218,16 @@ __global__ __launch_bounds__(256, QS == 2 ? 4 : 2) void attention_fwd_kernel(con
                 }
                 const float2_ e01 = {__builtin_amdgcn_exp2f(x01[0]), __builtin_amdgcn_exp2f(x01[1])};
                 const float2_ e23 = {__builtin_amdgcn_exp2f(x23[0]), __builtin_amdgcn_exp2f(x23[1])};
-#if !ATTN_SUM_MFMA
-                sum2 += e01 + e23;
-#endif
                 half8& dst = pb[kt >> 1][qs];                              // v_cvt_pk_f16_f32 (RNE) x2, written in place
                 dst[(kt & 1) * 4 + 0] = (half_t)e01[0]; dst[(kt & 1) * 4 + 1] = (half_t)e01[1];
                 dst[(kt & 1) * 4 + 2] = (half_t)e23[0]; dst[(kt & 1) * 4 + 3] = (half_t)e23[1];
             }
-#if !ATTN_SUM_MFMA
-            const float sum = rows_sum(sum2[0] + sum2[1]);
-            l_run[qs] = l_run[qs] * alpha + sum;
-#endif
             if (grow) {   // wave-uniform: some query's maximum moved by more than the deferral
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt) {
                     oacc[qs][dt][0] *= alpha; oacc[qs][dt][1] *= alpha; oacc[qs][dt][2] *= alpha; oacc[qs][dt][3] *= alpha;
                 }
-#if ATTN_SUM_MFMA
                 lacc[qs][0] *= alpha;
-#endif
             }
             m_run[qs] = m_new;
         }
@@ -280,10 +248,8 @@ __global__ __launch_bounds__(256, QS == 2 ? 4 : 2) void attention_fwd_kernel(con
 #pragma unroll
                 for (int qs = 0; qs < QS; ++qs) oacc[qs][dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pb[j][qs], oacc[qs][dt], 0, 0, 0);
             }
-#if ATTN_SUM_MFMA
 #pragma unroll
             for (int qs = 0; qs < QS; ++qs) lacc[qs] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ones_row0, pb[j][qs], lacc[qs], 0, 0, 0);
-#endif
         }
         __syncthreads();  // next tile landed (vmcnt(0)) and everyone is done with this buffer
     }
@@ -292,11 +258,7 @@ __global__ __launch_bounds__(256, QS == 2 ? 4 : 2) void attention_fwd_kernel(con
 #pragma unroll
     for (int qs = 0; qs < QS; ++qs) {
         const int qi = q0 + qs * 16 + lq16;
-#if ATTN_SUM_MFMA
         const float inv = 1.f / __shfl(lacc[qs][0], lq16, 64);          // lane (q, lg = 0) = lane q holds the query's sum (all lanes take part)
-#else
-        const float inv = 1.f / l_run[qs];
-#endif
         if (qi >= p.lq) continue;
         half_t* dst = p.o + ((size_t)b * p.lq + qi) * p.ldo + h * HD;
 #pragma unroll
@@ -319,8 +281,7 @@ int asd_attention_f16(const void* q, int32_t ldq, const void* k, int32_t ldk, co
                   "leading dimensions / key stride must keep 16-byte alignment");
     AttnArgs a{(const half_t*)q, ldq, (const half_t*)k, ldk, (const half_t*)vT, ldv, (half_t*)o, ldo,
                batch, heads, lq, lk, lk_stride, scale, (const char*)zero_page};
-    static const int qs_env = getenv("ASD_ATTN_QS") ? atoi(getenv("ASD_ATTN_QS")) : 0;     // A/B switch (tools): force 2 or 4
-    const bool wide = qs_env ? qs_env == 4 : (lk >= 2048 && lq >= 2048);
+    const bool wide = lk >= 2048 && lq >= 2048;
     if (wide) {
         const dim3 grid(8 * asd_div_up(asd_div_up(lq, 256) * heads * batch, 8));
         hipLaunchKernelGGL(attention_fwd_kernel<4>, grid, dim3(256), 4 * KT * HD * 2, (hipStream_t)stream, a);

@@ -989,8 +989,7 @@ int asd_conv3d_wgrad(const asd_conv3d_desc* d, const float* x, const float* dy, 
         a.C = slabs;        // unused (partials_only) but must be non-null
         a.W = yh;
         // launch 1: X_hi . [dY_hi | dY_lo]
-        static const int tile_env = getenv("ASD_C3_WGRAD_TILE") ? atoi(getenv("ASD_C3_WGRAD_TILE")) : 0;       // A/B hook (tools): 1-based tile configuration
-        a.A = xh; a.N = 2 * N; a.ldc = 2 * N; a.split_k = L.split1; a.workspace = slabs; a.tile_cfg = tile_env ? tile_env : ASD_CFG_320x128 + 1;      // 320 x 128 (6 Cout % 128 == 0): 4.24 vs 4.49 ms with 128 x 128 on 64 -> 64 @128^3 (tools/c3_wgrad_ab.py)
+        a.A = xh; a.N = 2 * N; a.ldc = 2 * N; a.split_k = L.split1; a.workspace = slabs; a.tile_cfg = ASD_CFG_320x128 + 1;      // 320 x 128 (6 Cout % 128 == 0): 4.24 vs 4.49 ms with 128 x 128 on 64 -> 64 @128^3
         ASD_PROBE_START(s);
         int rc = asd_gemm_f16(&a, stream);
         ASD_PROBE_STOP(s);

@@ -278,33 +278,18 @@ __global__ __launch_bounds__(256, 4) void field_fwd_kernel(const asd_grid_meta m
 //      slab_reduce_kernel in a fixed order.
 // DA costs 512 B/row of HBM write+read (288 GB of HBM3E: materialise instead of re-synchronising).
 // ---------------------------------------------------------------------------------------------------
-#ifndef ASD_FIELD_BWD_BLOCKS
 #define ASD_FIELD_BWD_BLOCKS 2   // blocks per CU the sample pass is compiled for (213 VGPRs; 3 was measured: see DESIGN.md)
-#endif
-#ifndef ASD_FIELD_W2_COPIES
-#define ASD_FIELD_W2_COPIES 16
-#endif
-#ifndef ASD_FIELD_W2_ROWSUM
-#define ASD_FIELD_W2_ROWSUM 1   // 1: second-layer weight-gradient terms are summed over each row of 16 lanes with four DPP adds and the row's
+#define ASD_FIELD_W2_COPIES 16  // second-layer weight-gradient terms are summed over each row of 16 lanes with four DPP adds and the row's
                                 // last lane adds the sum to the row's OWN copy with a plain LDS read-modify-write (16 rows per block = the 16
-                                // copies).  0: every lane issues an LDS float atomic — 256 per sample; LDS float atomics retire ~0.3 lanes per
-                                // clock and CU on gfx950, which made them, not the arithmetic, the bound of this kernel (round 5).
-#endif
-#ifndef ASD_FIELD_NAGG
+                                // copies).  The first form had every lane issue an LDS float atomic — 256 per sample; LDS float atomics retire
+                                // ~0.3 lanes per clock and CU on gfx950, which made them, not the arithmetic, the bound of this kernel (round 5).
 #define ASD_FIELD_NAGG 5   // levels scattered with wave-level run aggregation (asd_scatter_runs): the dense ones.  Level 5 (102^3 cells in a 2^19-entry
                            // hashed table) was the bulk of this kernel's atomic requests (runs of ~2.5 samples); it is paged with the finer ones
-#endif
-#ifndef ASD_FIELD_NPRIV
 #define ASD_FIELD_NPRIV 3   // levels whose gradient is accumulated in per-XCD copies first (asd_scatter_runs)
-#endif
-#ifndef ASD_FIELD_PRIV_CAP
 #define ASD_FIELD_PRIV_CAP (1 << 17)   // floats per copy reserved in the workspace (levels 0-2 of the 16-level grid: 106 034)
-#endif
-#ifndef WG_ROWS
 #define WG_ROWS 512    // rows per wgrad block.  2048 (rounds 1-2) gave the headline step 212 blocks of four waves for 256 CUs — one wave per
                        // SIMD with nobody to hide the LDS latency; 512: 846 blocks, three to four per CU, wgrad + slab reduction 0.24 -> 0.09 ms
-                       // (tools/wgrad_ab.sh, same box: 1024 -> 0.13, 256 -> 0.10)
-#endif
+                       // (same box: 1024 -> 0.13, 256 -> 0.10)
 #define WG_TILE 64     // rows per LDS tile
 
 // PRE: the MLP half already ran on the matrix pipe (csrc/field_mfma.hip: asd_field_bwd_mlp_mfma left the weight gradients and the encoding
@@ -325,14 +310,12 @@ __global__ __launch_bounds__(256, ASD_FIELD_BWD_BLOCKS) void field_bwd_sample_ke
     float* __restrict__ pg_pos = nullptr /* ... and the rows' unit-cube positions [n_pts * n, 3] */,
     const float* __restrict__ denc_pre = nullptr /* PRE: [n, 2L] */) {
     constexpr int NIN = 2 * L;
-    // second-layer weight-gradient sums of the block.  ASD_FIELD_W2_COPIES > 1: no wave-level reduction — every lane adds its own
-    // term with an LDS atomic into copy (lane & 15) of the accumulator (row stride W2N + 1: the 16 copies of one h sit in 16 banks, the
-    // four lanes of a copy serialise), the copies are summed at the end.  1: six DPP adds + readlane + one LDS atomic per sum.
-    constexpr int W2N = (C > 0 ? C : 1) * H + H, W2S = ASD_FIELD_W2_COPIES > 1 ? W2N + 1 : W2N;
+    // second-layer weight-gradient sums of the block: no wave-level reduction — each row of 16 lanes adds its sum into its own copy of the
+    // accumulator (row stride W2N + 1: the 16 copies of one h sit in 16 banks), the copies are summed at the end.
+    constexpr int W2N = (C > 0 ? C : 1) * H + H, W2S = W2N + 1;
     __shared__ float w2_acc[ASD_FIELD_W2_COPIES * W2S];
-    static_assert(!ASD_FIELD_W2_ROWSUM || ASD_FIELD_W2_COPIES == 16, "row sums: one copy per row of 16 lanes of the 256-thread block");
-    const int w2c = ASD_FIELD_W2_ROWSUM ? (threadIdx.x >> 4) * W2S
-                                        : (ASD_FIELD_W2_COPIES > 1 ? (threadIdx.x & (ASD_FIELD_W2_COPIES - 1)) * W2S : 0);
+    static_assert(ASD_FIELD_W2_COPIES == 16, "row sums: one copy per row of 16 lanes of the 256-thread block");
+    const int w2c = (threadIdx.x >> 4) * W2S;
     const bool row_last = (threadIdx.x & 15) == 15;
     const int nn = n_dev ? min(*n_dev, n) : n;
     if (n_dev && (int)blockIdx.x * 256 >= nn) return;       // capacity-sized launch (device-side count): nothing lives in this block
@@ -341,7 +324,6 @@ __global__ __launch_bounds__(256, ASD_FIELD_BWD_BLOCKS) void field_bwd_sample_ke
     __syncthreads();
     const int i = blockIdx.x * 256 + tid;
     const bool active = i < nn;
-    const bool lead = (tid & 63) == 0;
     float px = 0.f, py = 0.f, pz = 0.f, s = 0.f, ds = 0.f;
     float enc[NIN];
 #pragma unroll
@@ -461,18 +443,8 @@ __global__ __launch_bounds__(256, ASD_FIELD_BWD_BLOCKS) void field_bwd_sample_ke
                 float a = 0.f;
 #pragma unroll
                 for (int k = 0; k < NIN; ++k) a = fmaf(w1d[h * NIN + k], e[k], a);
-                if (ASD_FIELD_W2_ROWSUM) {
-#ifndef ASD_FIELD_ABL_NOW2
-                    const float v = asd_row_sum15(active ? draw * fmaxf(a, 0.f) : 0.f);
-                    if (row_last) w2_acc[w2c + h] += v;
-#endif
-                } else if (ASD_FIELD_W2_COPIES > 1) {
-                    const float v = active ? draw * fmaxf(a, 0.f) : 0.f;
-                    if (v != 0.f) atomicAdd(&w2_acc[w2c + h], v);
-                } else {
-                    const float v = asd_wave_sum(active ? draw * fmaxf(a, 0.f) : 0.f);
-                    if (lead) atomicAdd(&w2_acc[h], v);
-                }
+                const float v = asd_row_sum15(active ? draw * fmaxf(a, 0.f) : 0.f);
+                if (row_last) w2_acc[w2c + h] += v;
                 const float da = (active && a > 0.f) ? draw * w2d[h] : 0.f;
                 dav[j] = da;
 #pragma unroll
@@ -502,18 +474,8 @@ __global__ __launch_bounds__(256, ASD_FIELD_BWD_BLOCKS) void field_bwd_sample_ke
 #pragma unroll
                         for (int o = 0; o < C; ++o) {
                             dh = fmaf(df[o], w2f[o * H + h], dh);
-                            if (ASD_FIELD_W2_ROWSUM) {
-#ifndef ASD_FIELD_ABL_NOW2
-                                const float v = asd_row_sum15(df[o] * hv);
-                                if (row_last) w2_acc[w2c + H + o * H + h] += v;
-#endif
-                            } else if (ASD_FIELD_W2_COPIES > 1) {
-                                const float v = df[o] * hv;
-                                if (v != 0.f) atomicAdd(&w2_acc[w2c + H + o * H + h], v);
-                            } else {
-                                const float v = asd_wave_sum(df[o] * hv);
-                                if (lead) atomicAdd(&w2_acc[H + o * H + h], v);
-                            }
+                            const float v = asd_row_sum15(df[o] * hv);
+                            if (row_last) w2_acc[w2c + H + o * H + h] += v;
                         }
                         da = a > 0.f ? dh : 0.f;
 #pragma unroll
@@ -541,9 +503,7 @@ __global__ __launch_bounds__(256, ASD_FIELD_BWD_BLOCKS) void field_bwd_sample_ke
             const float ux = (qx - c.bbox_min[0]) / bx, uy = (qy - c.bbox_min[1]) / by, uz = (qz - c.bbox_min[2]) / bz;
             if (pg_g) {
                 // coarse levels as before (run-aggregated atomics, per-XCD copies); the fine levels' rows go to the paged scatter
-#ifndef ASD_FIELD_ABL_NOCOARSE      // (timing-only ablation, tools/r5_field_abl.sh: what the coarse levels' atomics cost inside this kernel)
                 asd_scatter_runs<L, ASD_FIELD_NAGG, ASD_FIELD_NPRIV, false>(m, d_grid, ux, uy, uz, denc, active, priv, priv_stride);
-#endif
                 if (active) {
                     constexpr int NFINE = L - ASD_FIELD_NAGG;
                     const size_t rr = (size_t)pt * n + i;
@@ -564,15 +524,13 @@ __global__ __launch_bounds__(256, ASD_FIELD_BWD_BLOCKS) void field_bwd_sample_ke
         }
     }
     __syncthreads();
-    if (ASD_FIELD_W2_COPIES > 1) {
-        for (int q = tid; q < W2N; q += 256) {
-            float a = 0.f;
+    for (int q = tid; q < W2N; q += 256) {
+        float a = 0.f;
 #pragma unroll
-            for (int cpy = 0; cpy < ASD_FIELD_W2_COPIES; ++cpy) a += w2_acc[cpy * W2S + q];
-            w2_acc[q] = a;       // copy 0's slot q is only read by this thread
-        }
-        __syncthreads();
+        for (int cpy = 0; cpy < ASD_FIELD_W2_COPIES; ++cpy) a += w2_acc[cpy * W2S + q];
+        w2_acc[q] = a;       // copy 0's slot q is only read by this thread
     }
+    __syncthreads();
     if constexpr (PRE) return;
     for (int q = tid; q < H; q += 256) atomicAdd(&dw2d[q], w2_acc[q]);
     if (C > 0 && dw2f)
@@ -987,7 +945,7 @@ static field_bwd_layout field_bwd_layout_init(const asd_field_cfg* cfg, int64_t 
     L.da = L.mfma ? -1 : w.take(rows * 128);
     L.enc_fd = with_normal ? w.take(3 * n * 32) : -1;
     L.slabs = w.take((int64_t)L.n_slabs * 128 * 32);
-    L.priv = !voxel && ASD_FIELD_NPRIV > 0 ? w.take((int64_t)ASD_PRIV_COPIES * ASD_FIELD_PRIV_CAP) : -1;
+    L.priv = !voxel ? w.take((int64_t)ASD_PRIV_COPIES * ASD_FIELD_PRIV_CAP) : -1;
     L.pg_g = paged ? w.take(rows * (2 * ASD_PG_NF_PAD)) : -1;
     L.pg_pos = paged ? w.take(rows * 3) : -1;
     L.pg_ws = paged ? w.take(asd_paged_workspace_floats(rows)) : -1;
@@ -1022,7 +980,7 @@ int asd_field_bwd(const asd_grid_meta* meta, const asd_field_cfg* cfg, const flo
     const field_bwd_layout L = field_bwd_layout_init(cfg, n, with_normal, false);
     auto at = [&](int64_t off) { return off < 0 ? (float*)nullptr : workspace + off; };
     float *const da = at(L.da), *const enc_fd = at(L.enc_fd), *const slabs = at(L.slabs), *priv = at(L.priv);
-    uint32_t priv_stride = ASD_FIELD_NPRIV > 0 ? 2u * meta->offset[ASD_FIELD_NPRIV] : 0u;   // floats per copy
+    uint32_t priv_stride = 2u * meta->offset[ASD_FIELD_NPRIV];   // floats per copy
     if (priv_stride > (uint32_t)ASD_FIELD_PRIV_CAP) priv_stride = 0;    // a grid with larger coarse levels: straight into the table
     if (priv_stride > 0) {
         if (hipMemsetAsync(priv, 0, (size_t)ASD_PRIV_COPIES * priv_stride * sizeof(float), s) != hipSuccess) {

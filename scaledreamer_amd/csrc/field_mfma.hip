@@ -257,11 +257,7 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
 #pragma unroll
                     for (int r = 0; r < 16; ++r) { pos |= (z[r] > 0.f ? 1u : 0u) << r; zmin = fminf(zmin, fabsf(z[r])); }
                     const int si = s0 + 32 * nt + l31;
-#ifdef FM_ABL_NOSLOW
-                    const bool unsure = false;
-#else
                     const bool unsure = zmin < 4096.f && si < nn;
-#endif
                     if (__builtin_amdgcn_ballot_w64(unsure) != 0) {
                         if (unsure) {
                             const float* erow = a.enc + (size_t)si * FM_K;
@@ -339,7 +335,6 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
             }
             // ---- Z = E W1^T (hidden units are lanes, samples registers): second-layer weight gradients as in-lane sums; dA in this layout is
             //      the B operand of dW1^T = E^T dA ------------------------------------------------------------------------------------------------
-#ifndef FM_ABL_NOZ
 #pragma unroll
             for (int ht = 0; ht < 2; ++ht) {
                 float daz[2][16];
@@ -410,7 +405,6 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
                     for (int r = 0; r < 16; ++r) dw1b[ht][r] = fmaf(d[r], inv, dw1b[ht][r]);
                 }
             }
-#endif
         }
         // ---- dE rows --------------------------------------------------------------------------------------------------------------------------------
 #pragma unroll

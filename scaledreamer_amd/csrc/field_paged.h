@@ -19,9 +19,7 @@
 #define ASD_PG_SHIFT 13                    // log2(entries per page): 8192 entries x 2 floats = 64 KB of LDS
 #define ASD_PG_ENTRIES (1 << ASD_PG_SHIFT)
 #define ASD_PG_MAX_BINS 1024               // levels x pages per level (one block scans them)
-#ifndef ASD_PG_NF
 #define ASD_PG_NF 11                       // hashed levels of the 16-level grid (levels >= ASD_FIELD_NAGG = 5: all of them have 2^19 entries)
-#endif
 #define ASD_PG_NF_PAD ((ASD_PG_NF + 1) / 2 * 2)   // levels per row of `g` (24 floats: 16-byte aligned rows; the pad pair is zero)
 #define ASD_PG_CHUNK_ROWS (2 << 20)        // rows binned per pass (item slots: 800 B per row)
 

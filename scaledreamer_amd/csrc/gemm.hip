@@ -721,31 +721,18 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv3x3_win2_kernel(const asd
     const int fb0 = (wn * (BN / WN) + frow) * RB;
     const int fswb[2] = {((fq) ^ (frow & 7)) * 16, ((4 + fq) ^ (frow & 7)) * 16};
 
-#ifdef ASD_WIN_PROFILE     // tools/win_profile.py: where a wave's cycles go (s_memtime), written to p.workspace (split_k == 1 only)
-    unsigned long long pt_start = __builtin_amdgcn_s_memtime(), pt_wait = 0, pt_first = 0, pt_reload = 0, pt_loop_end = 0;
-#define PT_NOW() __builtin_amdgcn_s_memtime()
-#endif
     if (steps > 0) {
         for (int slab = wave; slab < WIN_SLABS; slab += NW) load_window_slab(slab, c0, a_buf);
         load_w_tile(0, w_buf);
 #pragma unroll 1
         for (int s = 0; s < steps; ++s) {
             const int cl = s / 9, tap = s - cl * 9;
-#ifdef ASD_WIN_PROFILE
-            const unsigned long long pt_a = PT_NOW();
-#endif
             if (tap == 0 && s > 0) {   // chunk switch: everyone is done with the old window, reload it (exposed; the co-resident block covers)
                 __builtin_amdgcn_s_barrier();
                 for (int slab = wave; slab < WIN_SLABS; slab += NW) load_window_slab(slab, c0 + cl, a_buf);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
-#ifdef ASD_WIN_PROFILE
-            {
-                const unsigned long long pt_b = PT_NOW();
-                if (s == 0) pt_first = pt_b - pt_a; else if (tap == 0) pt_reload += pt_b - pt_a; else pt_wait += pt_b - pt_a;
-            }
-#endif
             if (s + 1 < steps) load_w_tile(s + 1, w_buf + ((s + 1) & 1) * W_BYTES);
             const char* Wt = w_buf + (s & 1) * W_BYTES;
             const int ky = tap / 3, kx = tap - ky * 3;
@@ -793,25 +780,12 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv3x3_win2_kernel(const asd
     }
 
     // acc[i][j][r] = C[pixel (y0 + wm*4 + i, x0 + (lane&15))][n0 + wn*BN/2 + j*16 + (lane>>4)*4 + r]
-#ifdef ASD_WIN_PROFILE
-    pt_loop_end = PT_NOW();
-#endif
     const bool gn = p.gn_partials != nullptr && p.split_k == 1;     // block-uniform
     float* gn_lds = (float*)smem;
     if (gn) gn_tile_begin(gn_lds);
     tile_epilogue<TM, TN>(p, acc, n0 + wn * (BN / WN), kz, b * p.Hout * p.Wout,
                           [&](int i) { return (b * p.Hout + y0 + wm * 4 + i) * p.Wout + x0 + frow; }, gn, gn_lds);
     if (gn) gn_tile_end(p, gn_lds, tm * tiles_n + tn_);
-#ifdef ASD_WIN_PROFILE
-    if (p.split_k == 1 && p.workspace && lane == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned long long* o = (unsigned long long*)p.workspace + ((size_t)item * NW + wave) * 8;
-        o[0] = pt_start; o[1] = PT_NOW(); o[2] = pt_first; o[3] = pt_wait; o[4] = pt_reload; o[5] = pt_loop_end;
-        unsigned hwid; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        unsigned xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        o[6] = hwid; o[7] = xcc;
-    }
-#endif
 }
 
 // sums the split-K slabs and applies the same epilogue (4 outputs per thread)
@@ -1022,7 +996,6 @@ __global__ __launch_bounds__(GNA_THREADS) void splitk_epilogue_gnapply_kernel(co
     }
 }
 
-#define ASD_GNAPPLY_MAX_NV 5
 // float4 items per thread of splitk_epilogue_gnapply_kernel for this (plan-resolved) launch; 0 = the fused form does not apply
 static int asd_gemm_gn_apply_nv(const asd_gemm_args* a) {
     if (!a->gn_apply || a->split_k <= 1 || a->partials_only || a->out_f32 || a->act == 2 || a->gn_bwd_x) return 0;
@@ -1031,9 +1004,7 @@ static int asd_gemm_gn_apply_nv(const asd_gemm_args* a) {
     const int need = (a->gn_rows * (a->gn_cg / 4) + GNA_THREADS - 1) / GNA_THREADS;
     // rows x group of 1024 x 20 and more (the 32x32 level) stay on the records path: 160 blocks of that size took 32 us where the records
     // epilogue + apply launch take ~20 (gpurun_out/r6m_on/step_breakdown.txt: 9 launches, 0.29 ms)
-    static const int max_nv = getenv("ASD_GNAPPLY_MAX_NV") ? atoi(getenv("ASD_GNAPPLY_MAX_NV")) : 3;
-    if (need > max_nv) return 0;
-    return need <= 1 ? 1 : need <= 3 ? 3 : need <= ASD_GNAPPLY_MAX_NV ? ASD_GNAPPLY_MAX_NV : 0;
+    return need <= 1 ? 1 : need <= 3 ? 3 : 0;
 }
 
 // the reduction launch behind a split-K main kernel
@@ -1043,8 +1014,7 @@ static void asd_launch_splitk_epilogue(const asd_gemm_args* a, hipStream_t s) {
         const dim3 grid((a->M / a->gn_rows) * 32);
         const float inv_cnt = 1.f / ((float)a->gn_rows * (float)a->gn_cg);
         if (nv == 1) hipLaunchKernelGGL(splitk_epilogue_gnapply_kernel<1>, grid, dim3(GNA_THREADS), 0, s, *a, a->split_k, inv_cnt);
-        else if (nv == 3) hipLaunchKernelGGL(splitk_epilogue_gnapply_kernel<3>, grid, dim3(GNA_THREADS), 0, s, *a, a->split_k, inv_cnt);
-        else hipLaunchKernelGGL(splitk_epilogue_gnapply_kernel<ASD_GNAPPLY_MAX_NV>, grid, dim3(GNA_THREADS), 0, s, *a, a->split_k, inv_cnt);
+        else hipLaunchKernelGGL(splitk_epilogue_gnapply_kernel<3>, grid, dim3(GNA_THREADS), 0, s, *a, a->split_k, inv_cnt);
         return;
     }
     const size_t total4 = (size_t)a->M * a->N / 4;
@@ -1404,10 +1374,9 @@ int asd_gemm_f16(const asd_gemm_args* a_in, void* stream) {
                   "tile configuration does not divide N");
     if (asd_gemm_gn_records_cfg(a, cfg, true) == 0) a->gn_partials = nullptr;
     {   // wide-row epilogue (tile_epilogue): whole 32-channel groups per wave, 16-byte aligned rows everywhere
-        static const bool wide_on = !(getenv("ASD_WIDE_ROWS") && getenv("ASD_WIDE_ROWS")[0] == '0');     // A/B switch (tools)
         auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
         const int wave_n = asd_cfg_wave_n(cfg);
-        a->wide_rows = wide_on && wave_n % 32 == 0 && a->act != 2 && a->N % 8 == 0 && a->ldc % 8 == 0 && al16(a->C) && (!a->bias || al16(a->bias)) &&
+        a->wide_rows = wave_n % 32 == 0 && a->act != 2 && a->N % 8 == 0 && a->ldc % 8 == 0 && al16(a->C) && (!a->bias || al16(a->bias)) &&
                        (!a->row_bias || (al16(a->row_bias) && a->ld_row_bias % 8 == 0)) && (!a->residual || (al16(a->residual) && a->ldr % 8 == 0)) &&
                        !(a->gn_partials && a->gn_bwd_x);
     }

@@ -44,18 +44,7 @@ __device__ __forceinline__ void pp_vm_wait_n(int n) {
 __device__ __forceinline__ void pp_mfma(floatx4& c, const half8& w, const half8& x) {
     asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(w), "v"(x));
 }
-// A/B switches of tools/pp_variants.sh (results unchanged): -DASD_PP_NO_STAGGER runs the two halves of the block in lockstep (all eight
-// waves read / load together, then multiply together), -DASD_PP_NO_PRIO drops the s_setprio around the MFMA segments
-#ifdef ASD_PP_NO_PRIO
-#define PP_PRIO(x) do { } while (0)
-#else
 #define PP_PRIO(x) __builtin_amdgcn_s_setprio(x)
-#endif
-#ifdef ASD_PP_NO_STAGGER
-#define PP_STAGGER 0
-#else
-#define PP_STAGGER 1
-#endif
 #define PP_PIN() __builtin_amdgcn_sched_barrier(0)
 #define PP_BARRIER()                    \
     do {                                \
@@ -63,15 +52,6 @@ __device__ __forceinline__ void pp_mfma(floatx4& c, const half8& w, const half8&
         __builtin_amdgcn_s_barrier();   \
         PP_PIN();                       \
     } while (0)
-
-// -DASD_PP_PROFILE (tools/pp_profile.py): s_memtime accounting per wave — prologue, load/read segments, waits at the two barriers of a
-// phase, MFMA segments, epilogue — written to p.workspace (split_k == 1 launches only)
-#ifdef ASD_PP_PROFILE
-#define PT_NOW() __builtin_amdgcn_s_memtime()
-#define PT_ADD(acc) do { const unsigned long long n__ = PT_NOW(); acc += n__ - pt_last; pt_last = n__; } while (0)
-#else
-#define PT_ADD(acc) do { } while (0)
-#endif
 
 template <int TM, int TN>
 __global__ __launch_bounds__(512) void conv3x3_pp_kernel(const asd_gemm_args p) {
@@ -180,10 +160,6 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(const asd_gemm_args p) 
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
 
-#ifdef ASD_PP_PROFILE
-    const unsigned long long pt_start = PT_NOW(), pt_wall0 = wall_clock64();     // wall_clock64: constant 100 MHz
-    unsigned long long pt_last = pt_start, pt_pro = 0, pt_l = 0, pt_b1 = 0, pt_m = 0, pt_b2 = 0, pt_epi = 0;
-#endif
     if (c0 < c1) {
         // ---- prologue: the first window, weight tiles of K-steps 0 and 1 ------------------------------------------------------------
         for (int pc = wave; pc < NPIECE; pc += 8) {
@@ -194,8 +170,7 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(const asd_gemm_args p) 
         load_w(c0, 1, 1);
         pp_vm_wait<0>();
         PP_BARRIER();
-        if (PP_STAGGER && grp == 1) PP_BARRIER();      // the second group runs one barrier behind
-        PT_ADD(pt_pro);
+        if (grp == 1) PP_BARRIER();      // the second group runs one barrier behind
 
 #pragma unroll 1
         for (int c = c0; c < c1; ++c) {
@@ -236,9 +211,7 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(const asd_gemm_args p) 
                     pp_vm_wait<0>();
                 }
                 if (NPH == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // reads retired before the partner may refill the slot
-                PT_ADD(pt_l);
                 PP_BARRIER();
-                PT_ADD(pt_b1);
                 PP_PRIO(1);
 #pragma unroll
                 for (int a = 0; a < NA; ++a)
@@ -246,9 +219,7 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(const asd_gemm_args p) 
                     for (int j = 0; j < NB; ++j)
                         pp_mfma(acc[a][j], B[j], A[a]);
                 PP_PRIO(0);
-                PT_ADD(pt_m);
                 PP_BARRIER();
-                PT_ADD(pt_b2);
                 // ---------------- phase 2: the other half of the long side ------------------------------------------------------
                 if constexpr (NPH == 2) {
                     if constexpr (SPLIT_N) {
@@ -266,9 +237,7 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(const asd_gemm_args p) 
                             if (pc < NPIECE) { load_piece(pc, c + 1, wnext); ++nwin; }
                         }
                     }
-                    PT_ADD(pt_l);
                     PP_BARRIER();
-                    PT_ADD(pt_b1);
                     PP_PRIO(1);
 #pragma unroll
                     for (int a = 0; a < NA; ++a)
@@ -277,14 +246,12 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(const asd_gemm_args p) 
                             pp_mfma(SPLIT_N ? acc[a][NB + j] : acc[NA + a][j], B[j], A[a]);
                         }
                     PP_PRIO(0);
-                    PT_ADD(pt_m);
                     PP_BARRIER();
-                    PT_ADD(pt_b2);
                 }
                 nwin_prev = nwin;
             }
         }
-        if (PP_STAGGER && grp == 0) PP_BARRIER();      // the first group waits for the second one's last segment
+        if (grp == 0) PP_BARRIER();      // the first group waits for the second one's last segment
     }
 
     // acc[i][j][r] = C[pixel (y0 + wm*TM + i, x0 + (lane&15))][n0 + wn*TN*16 + j*16 + (lane>>4)*4 + r]
@@ -294,15 +261,6 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(const asd_gemm_args p) 
     tile_epilogue<TM, TN>(p, acc, n0 + wn * TN * 16, kz, b * H * Wd,
                           [&](int i) { return (b * H + y0 + wm * TM + i) * Wd + x0 + fi; }, gn, gn_lds);
     if (gn) gn_tile_end(p, gn_lds, tm * tiles_n + tn_);
-#ifdef ASD_PP_PROFILE
-    if (p.split_k == 1 && p.workspace && lane == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        PT_ADD(pt_epi);
-        unsigned long long* o = (unsigned long long*)p.workspace + ((size_t)item * 8 + wave) * 16;
-        o[0] = pt_start; o[1] = pt_last; o[2] = pt_pro; o[3] = pt_l; o[4] = pt_b1; o[5] = pt_m; o[6] = pt_b2; o[7] = pt_epi;
-        o[8] = pt_wall0; o[9] = wall_clock64();
-    }
-#endif
 }
 
 // ---- host side: launch (a row of the tile table of gemm.hip names its instantiation) ------------------------------------------------

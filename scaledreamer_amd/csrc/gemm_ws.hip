@@ -62,9 +62,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_ws_kernel(const asd_gemm_args 
 
     auto issue_w = [&](int chunk) {           // 18 loads
         char* W_s = w_base + (chunk % 3) * W_BYTES;
-#ifdef WS_ABL_NOW
-        if (chunk >= 0) return;
-#endif
 #pragma unroll
         for (int j = 0; j < 18; ++j) {
             const int t = wave * 18 + j;
@@ -74,9 +71,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_ws_kernel(const asd_gemm_args 
     };
     auto issue_a = [&](int chunk) {
         char* A_s = a_base + (chunk & 1) * A_BYTES;
-#ifdef WS_ABL_NOA
-        if (chunk >= 0) return;
-#endif
 #pragma unroll
         for (int j = 0; j < A_PER_WAVE; ++j) {
             const int q = (wave - 2) * A_PER_WAVE + j;
@@ -160,11 +154,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_ws_kernel(const asd_gemm_args 
                     const unsigned m = (i & 1) ? m1 : m0;
                     f.a[i][0] &= m; f.a[i][1] &= m; f.a[i][2] &= m; f.a[i][3] &= m;
                 }
-#ifdef WS_ABL_NOMMA
-                acc[i][0] += __uint_as_float(f.a[i][0]) * __uint_as_float(f.w[0]);
-#else
                 acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, f.a[i]), __builtin_bit_cast(half8, f.w), acc[i], 0, 0, 0);
-#endif
             }
         };
         auto wait_frags = [&](Frag& f, auto pending_c) {      // wait until at most `pending` LDS reads are outstanding; the fragment registers order the MFMAs behind it
@@ -206,11 +196,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_ws_kernel(const asd_gemm_args 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int m = mt * 32 + q * 8 + kh * 4 + r;
-#ifdef WS_ABL_NOSTORE
-                if (acc[i][q * 4 + r] == 12345.678f) slab[(size_t)m * p.N] = acc[i][q * 4 + r];
-#else
                 slab[(size_t)m * p.N] = acc[i][q * 4 + r];            // M == 64 NB: every row tile is whole
-#endif
             }
     }
 }

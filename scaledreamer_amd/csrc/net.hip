@@ -123,20 +123,17 @@ void launch_gemm(Run& r, asd_gemm_args& g, Act* gn_out = nullptr, bool gn_bwd_fo
     }
     const size_t need = (size_t)asd_gemm_workspace_bytes(&g);
     if (need > r.scratch_need) r.scratch_need = need;
-    static const bool gn_epilogue = !(getenv("ASD_GN_EPILOGUE") && getenv("ASD_GN_EPILOGUE")[0] == '0');    // A/B switch (tools)
-    // The backward form of the records (the two reductions of the GroupNorm input gradient from the dgrad launch's epilogue) is OFF by
-    // default since round 3: on the ping-pong kernel the epilogue's silu'(z) over the whole tile is not hidden behind another block's
-    // main loop — the VAE's eleven dgrad launches grew by 22-53 us each (0.39 ms per step) for 0.33 ms of statistics passes saved; same-box
-    // A/B 15.58 vs 15.64 ms per step (gpurun_out/gnb).  ASD_GN_BWD_EPILOGUE=1 switches it back on.
-    // Re-decided when silu' lost its IEEE division (asd_silu_grad_fast: ~10 VALU instead of ~25 per element): still OFF.
+    // The backward form of the records (the two reductions of the GroupNorm input gradient from the dgrad launch's epilogue) is NOT used by
+    // the schedules since round 3 (the GEMM still offers it: asd_gemm_args.gn_bwd_*): on the ping-pong kernel the epilogue's silu'(z) over
+    // the whole tile is not hidden behind another block's main loop — the VAE's eleven dgrad launches grew by 22-53 us each (0.39 ms per step) for 0.33 ms of statistics passes saved; same-box
+    // A/B 15.58 vs 15.64 ms per step.
+    // Re-decided when silu' lost its IEEE division (asd_silu_grad_fast: ~10 VALU instead of ~25 per element): still not used.
     // Same box, four alternating runs of 300 steps: stand-alone statistics passes 13.748 / 13.700 / 13.698 / 13.690 ms per step, reductions in
     // the dgrad epilogue 13.894 / 13.874 / 13.881 / 13.888 ms (+0.175 ms, every pair the same sign; the parent commit on that box 13.92 ms).
     // The statistics passes got cheaper by the same change (statistics + apply at 512^2 x 128: 83 -> 70 us), the un-hidden epilogue
     // arithmetic of the eleven ping-pong launches (x reload, two FMAs, v_exp, v_rcp per output and the tile reduction) did not become free.
-    static const bool gn_bwd_epilogue = getenv("ASD_GN_BWD_EPILOGUE") && getenv("ASD_GN_BWD_EPILOGUE")[0] == '1';
-    if (gn_bwd_form && !gn_bwd_epilogue) { gn_out = nullptr; g.gn_bwd_x = nullptr; g.gn_bwd_fstats = nullptr; g.gn_bwd_gamma = nullptr; g.gn_bwd_beta = nullptr; }
-    static const bool gn_fused_apply = !(getenv("ASD_GN_FUSED_APPLY") && getenv("ASD_GN_FUSED_APPLY")[0] == '0');          // A/B switch (tools)
-    if (gn_fused_apply && gn_epilogue && gn_next && gn_next->gamma && gn_out && !gn_bwd_form && g.gn_rows > 0 && g.N % 32 == 0 && !r.rec_replay && !r.rec_log) {
+    if (gn_bwd_form) { gn_out = nullptr; g.gn_bwd_x = nullptr; g.gn_bwd_fstats = nullptr; g.gn_bwd_gamma = nullptr; g.gn_bwd_beta = nullptr; }
+    if (gn_next && gn_next->gamma && gn_out && g.gn_rows > 0 && g.N % 32 == 0 && !r.rec_replay && !r.rec_log) {
         // GroupNorm applied by the producer: decided by shape and plan only (dry passes carry null pointers)
         asd_gemm_args q = g;
         q.gn_cg = g.N / 32; q.gn_apply = 1;
@@ -151,7 +148,7 @@ void launch_gemm(Run& r, asd_gemm_args& g, Act* gn_out = nullptr, bool gn_bwd_fo
             gn_out = nullptr;           // no records: nothing else reads this tensor's statistics
         }
     }
-    if (gn_epilogue && gn_out && g.gn_rows > 0 && g.N % 32 == 0) {     // statistics records of the output, produced in the epilogue when the plan allows
+    if (gn_out && g.gn_rows > 0 && g.N % 32 == 0) {     // statistics records of the output, produced in the epilogue when the plan allows
         g.gn_cg = g.N / 32;
         const int batch = g.M / g.gn_rows;
         int nrec;
@@ -160,11 +157,6 @@ void launch_gemm(Run& r, asd_gemm_args& g, Act* gn_out = nullptr, bool gn_bwd_fo
             asd_gemm_args q = g;             // the answer depends on shape, plan and form only (dry passes carry null pointers)
             q.gn_bwd_x = nullptr;
             nrec = asd_gemm_gn_records(&q);
-            if (gn_bwd_form && q.split_k == 0) {        // the backward form has no split-K variant (splitk_epilogue_gn_kernel is forward only)
-                int32_t t = 0, sk = 1;
-                asd_gemm_plan_get(&q, &t, &sk);
-                if (sk > 1) nrec = 0;
-            }
         }
         // while tuning, the plan (and with it the record count) of this shape may still change between the sizing pass and the
         // launch: reserve the upper bound (64 x 64 tiles)
@@ -1079,8 +1071,7 @@ int asd_vae_enc_fwd(asd_vae_enc* h, const void* x_nhwc32, int32_t batch, int32_t
     // size check against the forward + backward plan, so that the backward can never overrun what the forward accepted
     const uint64_t gen = asd_gemm_plan_generation();
     Vae::Sized& z = n->sized;
-    static const bool cache_on = !(getenv("ASD_VAE_SIZING_CACHE") && getenv("ASD_VAE_SIZING_CACHE")[0] == '0');       // A/B switch (tools)
-    const bool known = cache_on && z.gen == gen && z.batch == batch && z.H == H && z.W == W && z.tune == tune && workspace_bytes >= z.need;
+    const bool known = z.gen == gen && z.batch == batch && z.H == H && z.W == W && z.tune == tune && workspace_bytes >= z.need;
     const int64_t need = known ? z.need : asd_vae_enc_workspace_bytes(h, batch, H, W, tune);
     if (need < 0 || need > workspace_bytes) { asd_set_error("workspace of %lld bytes is too small (need %lld)", (long long)workspace_bytes, (long long)need); return ASD_ERR_ARG; }
     // the scratch region is sized for both passes (the dry pass walks the backward as well) and remembered per workspace

@@ -18,16 +18,10 @@ __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff
 // C > 2048) and walks the rows of its chunk with stride 256/slots, accumulating per-channel sums in registers;
 // only at the end are they folded into 32 per-group LDS cells and from there into global memory (one atomic
 // pair per block and group).
-#ifndef GN_UNR
 #define GN_UNR 4      // rows in flight per thread (16-B loads)
-#endif
-#ifndef GN_CAP_A
 #define GN_CAP_A 512  // apply blocks per launch
-#endif
-#ifndef GN_FOLD_RECORDS
 #define GN_FOLD_RECORDS 96   // up to this many epilogue records per batch element are summed by every apply block itself (24 KB of L2
                              // reads, four loads in flight per thread); above it a reduce launch (~5 us) runs first
-#endif
 
 __global__ __launch_bounds__(256) void gn_stats_kernel(const half_t* __restrict__ x1, int c1, const half_t* __restrict__ x2,
                                                        int c2, int hw, int rows_per_block, float* __restrict__ stats) {
@@ -208,13 +202,9 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const half_t* __restrict_
 // is scarce here? no: 288 GB — but x must be kept for the convolution-free recompute anyway).
 __device__ __forceinline__ float silu_grad(float z) { return asd_silu_grad_fast(z); }   // v_exp + v_rcp + 2 FMA (asd_common.h)
 
-#ifndef GN_BWD_UNR
 #define GN_BWD_UNR 4  // rows in flight per thread in the two backward passes (two or three 16-B loads each): once the arithmetic was
                       // light, bytes in flight per CU were what held the large tensors back (2 -> 4 rows: 83 -> 70 us for the pair at 512^2 x 128)
-#endif
-#ifndef GN_BWD_WIDE_NT
 #define GN_BWD_WIDE_NT 512  // threads per block of the backward statistics pass on the large tensors
-#endif
 
 // NT threads per block: 256, or 512 for the large tensors — the grid is capped at 256 blocks (every apply block sums all their
 // partials), and with four waves per CU the silu' arithmetic of a wave was not hidden behind anybody's loads: 2.6 TB/s on the VAE's

@@ -601,30 +601,20 @@ int asd_render_fwd(const asd_render_params* p, void* workspace, void* stream) {
     STEP(asd_march_write(&p->march, p->rays_o, p->rays_d, nr, p->occ_bits, p->jitter, AT(int32_t, offset), AT(int32_t, c_ray_idx), AT(float, c_t0), AT(float, c_t1),
                          AT(float, c_pts), stream));
     const int32_t *k_off, *k_cnt, *n_kept;
-    // ASD_RENDER_CANDIDATE_FIELD=0 (A/B): densities of the candidates, then the whole field again at the kept samples (the reference's order:
-    // nerfacc's sigma_fn inside the sampling, then geometry(positions)).  Default: the field ONCE, on the candidates — the hash-grid gathers
-    // are what a sample costs, the feature head on the pruned candidates is cheap beside a second encode of the kept ones — and the
-    // compaction carries sigma / features / encoding rows along (bit-identical values: same function of the same positions).
-    static const bool candidate_field = !(getenv("ASD_RENDER_CANDIDATE_FIELD") && getenv("ASD_RENDER_CANDIDATE_FIELD")[0] == '0');
-    const bool fused = p->prune && candidate_field;
+    // The reference's order is densities of the candidates, then the whole field again at the kept samples (nerfacc's sigma_fn inside the
+    // sampling, then geometry(positions)).  Here, with pruning: the field ONCE, on the candidates — the hash-grid gathers are what a sample
+    // costs, the feature head on the pruned candidates is cheap beside a second encode of the kept ones — and the compaction carries
+    // sigma / features / encoding rows along (bit-identical values: same function of the same positions).
     if (p->prune) {
-        if (fused)
-            STEP(asd_field_fwd(p->meta, p->field, p->grid, p->w1d, p->w2d, p->w1f, p->w2f, AT(float, c_pts), cap, AT(int32_t, total), AT(float, c_sigma),
-                               AT(float, c_feats), nullptr, nullptr, AT(float, c_enc), stream));
-        else
-            STEP(asd_field_density(p->meta, p->field, p->grid, p->w1d, p->w2d, AT(float, c_pts), cap, AT(int32_t, total), AT(float, c_sigma), stream));
+        STEP(asd_field_fwd(p->meta, p->field, p->grid, p->w1d, p->w2d, p->w1f, p->w2f, AT(float, c_pts), cap, AT(int32_t, total), AT(float, c_sigma),
+                           AT(float, c_feats), nullptr, nullptr, AT(float, c_enc), stream));
         STEP(asd_prune_count(AT(float, c_sigma), AT(float, c_t0), AT(float, c_t1), AT(int32_t, offset), AT(int32_t, count), nr, p->early_stop_eps, p->alpha_thre,
                              AT(uint8_t, keep), AT(int32_t, kept), stream));
         STEP(asd_scan_i32(AT(int32_t, kept), nr, AT(int32_t, koff), AT(int32_t, n_kept), stream));
-        if (fused) {
-            hipLaunchKernelGGL(compact_kernel, dim3(asd_div_up(nr, RAYS_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream, p->rays_o, p->rays_d, nr, AT(int32_t, offset),
-                               AT(int32_t, count), AT(uint8_t, keep), AT(float, c_t0), AT(float, c_t1), AT(int32_t, koff), AT(int64_t, ray_idx), AT(float, t0),
-                               AT(float, t1), AT(float, pts), AT(float, dirs), AT(float, c_sigma), AT(float, c_feats), AT(float, c_enc), AT(float, sigma),
-                               AT(float, feats), AT(float, enc));
-        } else {
-            STEP(asd_compact(p->rays_o, p->rays_d, nr, AT(int32_t, offset), AT(int32_t, count), AT(uint8_t, keep), AT(float, c_t0), AT(float, c_t1), AT(int32_t, koff),
-                             AT(int64_t, ray_idx), AT(float, t0), AT(float, t1), AT(float, pts), AT(float, dirs), stream));
-        }
+        hipLaunchKernelGGL(compact_kernel, dim3(asd_div_up(nr, RAYS_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream, p->rays_o, p->rays_d, nr, AT(int32_t, offset),
+                           AT(int32_t, count), AT(uint8_t, keep), AT(float, c_t0), AT(float, c_t1), AT(int32_t, koff), AT(int64_t, ray_idx), AT(float, t0),
+                           AT(float, t1), AT(float, pts), AT(float, dirs), AT(float, c_sigma), AT(float, c_feats), AT(float, c_enc), AT(float, sigma),
+                           AT(float, feats), AT(float, enc));
         k_off = AT(int32_t, koff); k_cnt = AT(int32_t, kept); n_kept = AT(int32_t, n_kept);
     } else {
         STEP(asd_compact(p->rays_o, p->rays_d, nr, AT(int32_t, offset), AT(int32_t, count), nullptr, AT(float, c_t0), AT(float, c_t1), AT(int32_t, offset),
@@ -633,10 +623,9 @@ int asd_render_fwd(const asd_render_params* p, void* workspace, void* stream) {
         (void)hipMemcpyAsync(AT(int32_t, kept), AT(int32_t, count), (size_t)nr * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
         (void)hipMemcpyAsync(AT(int32_t, n_kept), AT(int32_t, total), 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
         k_off = AT(int32_t, koff); k_cnt = AT(int32_t, kept); n_kept = AT(int32_t, n_kept);
-    }
-    if (!fused)
         STEP(asd_field_fwd(p->meta, p->field, p->grid, p->w1d, p->w2d, p->w1f, p->w2f, AT(float, pts), cap, n_kept, AT(float, sigma), AT(float, feats), nullptr,
                            nullptr, AT(float, enc), stream));
+    }
     hipLaunchKernelGGL((composite_fwd_kernel<0>), dim3(asd_div_up(nr, RAYS_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream, AT(float, sigma), AT(float, t0), AT(float, t1),
                        AT(float, feats), k_off, k_cnt, nr, p->bg, AT(float, weights), AT(float, opacity), AT(float, depth), AT(float, rgb_fg), AT(float, z_var),
                        AT(float, comp_rgb), p->color_act);

@@ -748,9 +748,8 @@ __global__ __launch_bounds__(256, 2) void tfm_bwd_data_kernel(const tfm_bwd_args
 // numbers).  The rows' G spans many orders of magnitude across a chunk: a wave keeps a RUNNING power-of-two scale S >= every |G| it has seen
 // (operands carry G / S, the accumulators are rescaled when S grows — exact), so the fp16 operands stay in range without a pass over the
 // gradients.  One wave per SIMD (176 accumulator registers + the chain); per-wave LDS: the lookup fragments of the tile (24 KB), the rows' G.
-#ifndef TFM_W_DEEP
 #define TFM_W_DEEP false    // lookup pipeline of this kernel one unit deep (two in the forward / data kernels): same-box A/B of C5 at the 256 x 256 render
-#endif                      // 267.7 vs 271.6 ms per step (tools/r5_tfm_ab.sh)
+                            // 267.7 vs 271.6 ms per step
 template <int O, bool FD>
 __global__ __launch_bounds__(256, 1) void tfm_bwd_weights_kernel(const tfm_bwd_args a) {
     constexpr int head = O == 3;

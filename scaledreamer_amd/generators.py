@@ -198,9 +198,6 @@ class _ToRGBFn(torch.autograd.Function):
         return dx, dw, db, (dy if ctx.has_add else None)
 
 
-_FUSED_MODULATION = os.environ.get("ASD_FUSED_MODULATION", "1") != "0"      # =0: the tensor-op form (same-box A/B, tools/)
-
-
 class _ModWeightsFn(torch.autograd.Function):
     """the per-sample weights of modulated_conv3d (stylegan_3dconv_modules.py:64-82): weight * styles * gain, demodulated — one launch
     forward, two backward (asd_modulated_weights_fwd / _bwd) instead of six / a dozen tensor ops over [N, Cout, Cin, 27] floats"""
@@ -260,12 +257,8 @@ class SynthesisLayer(nn.Module):
     def forward_cl(self, x, ax, w, noise_mode, gain=1, add=None):
         """the same layer on a channel-last volume x [N, D, H, W, Cin] through the HIP nodes -> (y, ay); ax / ay: max|.| words (or None);
         add: a volume added to the result (the block's const_bias, which the reference adds right after this layer)"""
-        n, cin = x.shape[0], x.shape[4]
-        if _FUSED_MODULATION:
-            wm = _ModWeightsFn.apply(self.weight, self.affine(w), 1.0, True)
-        else:
-            wm = self.weight.unsqueeze(0) * self.affine(w).reshape(n, 1, cin, 1, 1, 1)
-            wm = wm * (wm.square().sum(dim=[2, 3, 4, 5]) + 1e-8).rsqrt().reshape(n, -1, 1, 1, 1, 1)
+        n = x.shape[0]
+        wm = _ModWeightsFn.apply(self.weight, self.affine(w), 1.0, True)
         r = self.resolution
         if noise_mode == "random":
             noise = torch.randn([n, 1, r, r, r], device=x.device).reshape(n, r, r, r)       # (the reference's draw: same shape, same stream position)
@@ -295,10 +288,7 @@ class ToRGBLayer(nn.Module):
     def forward_cl(self, x, w):
         """channel-last: the 1x1x1 modulated convolution (no demodulation) is a per-sample matrix product on the [voxels, C] view"""
         n, cin = x.shape[0], x.shape[4]
-        if _FUSED_MODULATION:
-            wm = _ModWeightsFn.apply(self.weight.reshape(-1, cin), self.affine(w), self.weight_gain, False)      # [N, Cout, Cin]
-        else:
-            wm = self.weight.reshape(1, -1, cin) * (self.affine(w) * self.weight_gain).reshape(n, 1, cin)
+        wm = _ModWeightsFn.apply(self.weight.reshape(-1, cin), self.affine(w), self.weight_gain, False)      # [N, Cout, Cin]
         if wm.shape[1] == 32 and cin % 64 == 0:
             return _ToRGBFn.apply(x, wm, self.bias, None)
         y = torch.baddbmm(self.bias.reshape(1, 1, -1), x.reshape(n, -1, cin), wm.transpose(1, 2))       # other widths: library product

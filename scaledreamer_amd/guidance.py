@@ -11,7 +11,6 @@ and encode_images (:171-178).
 """
 from __future__ import annotations
 
-import os
 
 from dataclasses import dataclass, field
 from typing import Any, Callable, Dict, List, Optional, Tuple
@@ -218,8 +217,7 @@ class _ScoreDistillation(torch.autograd.Function):
         moments, saved = backend.vae_forward(x)
         n_rep, n_neg = job["n_rep"], job["n_neg"]
         # the first n_rep * B entries repeat the same noised latents / timesteps / cameras under different prompts (asd_latents_fwd below)
-        share = n_rep if os.environ.get("ASD_UNET_SHARED", "1") != "0" else 0          # 0: A/B switch (tools)
-        io = backend.unet_buffers((n_rep + 1) * B, hl, hl, job["n_ctx"], job["frames"], shared_reps=share)
+        io = backend.unet_buffers((n_rep + 1) * B, hl, hl, job["n_ctx"], job["frames"], shared_reps=n_rep)
         neg_w = job["neg_w"]
         if job.get("context_fill") is not None:
             neg_w = job["context_fill"](io)          # asd_prompt_context: prompt selection written into io.context on the device

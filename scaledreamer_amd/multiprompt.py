@@ -72,7 +72,7 @@ class MultiPromptUtils:
         assert view_dependent_prompting, "Perp-Neg only works with view-dependent prompting"
         B = len(self.global_text_embeddings)
         gs = -1 if guidance_scale_neg is None else guidance_scale_neg
-        if elevation.is_cuda and os.environ.get("ASD_PERP_NEG_ON_DEVICE", "1") != "0":      # =0: the branching form (same-box A/B)
+        if elevation.is_cuda:
             return self._perp_neg_on_device(elevation, azimuth, gs)
         idx = self.direction_idx(elevation, azimuth, camera_distances)
         pos, neg, uncond, weights = [], [], [], []

@@ -477,7 +477,7 @@ class NeRFVolumeRenderer(VolumeRenderer):
         sigmoid(features) | features, no normal consumer inside the call (the conditions of the sync-free path, narrowed)"""
         geo, mat = self.geometry, self.material
         fc = getattr(geo, "_fcfg", None)
-        return (os.environ.get("ASD_RENDER_ENTRY", "1") != "0" and fc is not None and hasattr(geo, "_weights") and hasattr(geo, "_meta")
+        return (fc is not None and hasattr(geo, "_weights") and hasattr(geo, "_meta")
                 and getattr(geo.cfg, "n_feature_dims", 0) == 3 and fc.field_mode == _lib.ASD_FIELD_DENSITY
                 and getattr(mat.cfg, "color_activation", "?") in self._COLOR_ACTS and torch.is_grad_enabled()
                 and geo.encoding.encoding.encoding.params.requires_grad

@@ -240,7 +240,7 @@ class StableDreamer(nn.Module, Updateable):
 
     def _assemble_loss(self, terms, out, lams, fused: bool):
         """sum of weight * value over `terms` plus the fused per-ray regularisers `lams`; in the reference's order of additions (tensor
-        ops) when `fused` is off — CPU tensors, ASD_LOSS_TAIL=0, no fp32 device opacity, more terms than one launch takes"""
+        ops) when `fused` is off — CPU tensors, no fp32 device opacity, more terms than one launch takes"""
         ASD_LOSS_MAX_TERMS = 8                     # csrc/asd_glue.hip: the term table of one asd_loss_tail launch
 
         opacity = out.get("opacity") if fused else None
@@ -273,8 +273,7 @@ class StableDreamer(nn.Module, Updateable):
             raise ValueError(f"stage {stage!r}: only the NeRF stages 'coarse' and 'coarse+geometry' are implemented")
         out = self(batch)
         terms = self._guidance_terms(out["comp_rgb"], batch, "", 1.0, self._rgb_as_latents())
-        fused = ("opacity" in out and torch.is_tensor(out["opacity"]) and out["opacity"].is_cuda and out["opacity"].dtype == torch.float32
-                 and os.environ.get("ASD_LOSS_TAIL", "1") != "0")        # =0: the tensor-op form (A/B, tools/r5_ab_env.sh)
+        fused = "opacity" in out and torch.is_tensor(out["opacity"]) and out["opacity"].is_cuda and out["opacity"].dtype == torch.float32
         reg_terms, lams = self._regulariser_terms(out, fused)
         terms = terms + reg_terms
         if stage == "coarse+geometry":   # second guidance pass on the normal image

@@ -176,3 +176,20 @@ def test_gemm_tile_table_is_the_one_python_and_the_plans_use():
             assert cin % 32 == 0 and N % bn == 0 and hin % (bm // 16) == 0, where
         else:
             assert cin % 64 == 0, where
+
+
+def test_environment_variables_are_the_ones_integration_md_lists():
+    """the names the library passes to getenv and the ASD_* names the package reads from os.environ are exactly the rows of the
+    'Environment variables' table of INTEGRATION.md: a new switch is documented there or it does not exist"""
+    import glob
+
+    read = set()
+    csrc = os.path.join(ROOT, "scaledreamer_amd", "csrc")
+    for path in glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")):
+        read |= set(re.findall(r'getenv\(\s*"(\w+)"', open(path).read()))
+    for path in glob.glob(os.path.join(ROOT, "scaledreamer_amd", "**", "*.py"), recursive=True):
+        read |= set(re.findall(r'os\.environ(?:\.get\(|\[)\s*["\'](ASD_\w+)["\']', open(path).read()))
+    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    table = text[text.index("Environment variables"):]
+    listed = set(re.findall(r"^\|\s*`(\w+)`\s*\|", table, re.M))
+    assert read and read == listed, (sorted(read - listed), sorted(listed - read))

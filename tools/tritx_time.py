@@ -61,4 +61,4 @@ y, stats, dx = torch.empty_like(x), torch.empty(M, 2, device="cuda"), torch.empt
 dg, db = torch.zeros(Dm, device="cuda"), torch.zeros(Dm, device="cuda")
 lnf = lambda: L.check(L.lib().asd_tx_layernorm_fwd(L.ptr(x), L.i32(M), L.i32(Dm), L.ptr(gamma), L.ptr(beta), L.f32(1e-6), L.ptr(y), L.ptr(stats), L.stream()))
 lnb = lambda: L.check(L.lib().asd_tx_layernorm_bwd(L.ptr(dy), L.ptr(x), L.ptr(stats), L.ptr(gamma), L.i32(M), L.i32(Dm), L.ptr(dres), L.ptr(dx), L.ptr(dg), L.ptr(db), L.stream()))
-print(f"layernorm {M}x{Dm}: fwd {timed(lnf):6.1f} us  bwd {timed(lnb):6.1f} us  (ASD_TX_LN_ROWS={os.environ.get('ASD_TX_LN_ROWS', '2')})")
+print(f"layernorm {M}x{Dm}: fwd {timed(lnf):6.1f} us  bwd {timed(lnb):6.1f} us")
