@@ -900,6 +900,37 @@ int asd_atlas_bake(const AsdAtlasLayout* layout, const float* v_pos, const int64
  * not rounding); values [n_owned, C], C in [1, 4], image [n_texels, C] zeroed by the caller; an index outside [0, n_texels) writes nothing */
 int asd_atlas_pack_u8(const float* values, const int64_t* texel_index, int64_t n_owned, int32_t C, uint8_t* image, int64_t n_texels, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Float images to bytes (csrc/image.hip): the image grids of the validation / test passes (threestudio/systems/scaledreamer.py:172-315,
+ * custom/amortized/systems/multiprompt_radience_field_generator.py:218-394) without numpy or cv2 on the host.
+ * ------------------------------------------------------------------------------------------------ */
+/* per-image extrema of x [n_images, n_per_image] -> minmax [n_images, 2] = (min, max): the depth normalisation of validation_step /
+ * test_step (scaledreamer.py:176-178,256-258) and `data_range=None` of get_grayscale_image_ (threestudio/utils/saving.py:182-183).
+ * torch.min / torch.max semantics: exact, and a NaN anywhere in an image makes both of its results NaN.  Deterministic, no atomics: an
+ * image of more than 16384 values is reduced by several blocks through `workspace` (the bytes of the size query, which shares its layout
+ * function with the pass; 0 bytes and a null pointer for smaller images).  n_per_image >= 1; x and minmax 4-byte aligned. */
+int64_t asd_image_minmax_workspace(int64_t n_images, int64_t n_per_image);      /* bytes; -1 on error */
+int asd_image_minmax_f32(const float* x, int64_t n_images, int64_t n_per_image, float* minmax, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+#define ASD_PANEL_RGB 0         /* src [B, H, W, 3] */
+#define ASD_PANEL_GRAYSCALE 1   /* src [B, H, W], the byte replicated to three channels (cmap None) */
+typedef struct {
+    const float* src;
+    const float* minmax;        /* [B, 2] of asd_image_minmax_f32 over src; read only when normalize != 0 */
+    int32_t kind;
+    int32_t normalize;          /* grayscale only: v = (v - min_b) / (max_b - min_b) first */
+    float lo, hi;               /* data_range: finite, lo < hi */
+} AsdImagePanel;
+/* get_image_grid_ (threestudio/utils/saving.py:255-299) for n_panels <= 8 equal-sized panels over the same [B, H, W] pixels, in one launch:
+ * out [B, H, n_panels W, 3] uint8, panels side by side, RGB order (the reference holds BGR only because cv2.imwrite takes BGR: the file
+ * is the same).  Per value, in fp32 without contraction and with IEEE division:
+ *   grayscale: normalize (if set), then nan_to_num (NaN -> 0, +-inf -> +-FLT_MAX: a constant image normalises to NaN and becomes 0);
+ *   both kinds: v = min(max(v, lo), hi), byte = (uint8) trunc((v - lo) / (hi - lo) * 255.0f)  — truncation, as in asd_atlas_pack_u8.
+ * An rgb panel gets no nan_to_num, as in get_rgb_image_ (:82-86); there numpy's cast of NaN to uint8 is undefined, here max(NaN, lo) = lo
+ * and a NaN of an rgb panel is written as 0.  Every source is read once; out is written in whole dwords (out 4-byte aligned, sources
+ * 4-byte aligned, B H n_panels W < 2^31).  `panels` is a host array. */
+int asd_image_grid_u8(const AsdImagePanel* panels, int32_t n_panels, int64_t B, int32_t H, int32_t W, uint8_t* out, void* stream);
+
 /* library info */
 const char* asd_version(void);
 const char* asd_last_error(void);

@@ -148,6 +148,12 @@ class AtlasLayout(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("n_faces", "texture_size", "gutter", "n", "c", "L")]
 
 
+class ImagePanel(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("minmax", C.c_void_p), ("kind", C.c_int32), ("normalize", C.c_int32), ("lo", C.c_float), ("hi", C.c_float)]
+
+
+ASD_PANEL_RGB, ASD_PANEL_GRAYSCALE = 0, 1
+
 _lib: Optional[C.CDLL] = None
 
 # every symbol include/asd_hip.h declares (tests/test_abi.py checks the header against this list)
@@ -180,6 +186,7 @@ SYMBOLS = [
     "asd_mt_workspace", "asd_mt_count", "asd_mt_emit", "asd_mt_case_table", "asd_scan_i32_blocks_workspace", "asd_scan_i32_blocks",
     "asd_mesh_cc_round", "asd_mesh_face_counts", "asd_mesh_keep", "asd_mesh_compact",
     "asd_atlas_layout", "asd_atlas_uv", "asd_atlas_bake", "asd_atlas_pack_u8",
+    "asd_image_minmax_workspace", "asd_image_minmax_f32", "asd_image_grid_u8",
     "asd_comm_unique_id", "asd_comm_create", "asd_comm_destroy", "asd_allreduce_mean_f32",
     "asd_version", "asd_last_error", "asd_modulated_weights_fwd", "asd_modulated_weights_bwd", "asd_timestep_plus", "asd_loss_tail_fwd", "asd_loss_tail_bwd", "asd_probe_events", "asd_probe_mark",
 ]
@@ -201,7 +208,7 @@ def lib() -> C.CDLL:
         l.asd_grid_meta_init.argtypes = [C.POINTER(GridMeta), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double]
         for fn in ("asd_gemm_workspace_bytes", "asd_unet_workspace_bytes", "asd_unet_workspace_bytes_shared", "asd_vae_enc_workspace_bytes",
                    "asd_conv3d_workspace_bytes", "asd_tx_linear_workspace", "asd_tx_wgrad_workspace", "asd_tx_attention_workspace",
-                   "asd_tritx_packed_floats", "asd_tritx_save_floats", "asd_tritx_workspace_floats"):
+                   "asd_tritx_packed_floats", "asd_tritx_save_floats", "asd_tritx_workspace_floats", "asd_image_minmax_workspace"):
             getattr(l, fn).restype = C.c_int64
         l.asd_unet_destroy.restype = None
         l.asd_vae_enc_destroy.restype = None

@@ -236,6 +236,13 @@ class RandomCameraIterableDataset(Updateable):
                                                          self.cfg.rays_d_normalize, device=self.ray_device)
         return out
 
+    # ---- evaluation: the val / test datasets of the reference's datamodule (uncond.py:478-484, uncond_multiview.py:266-272) -------
+    def val_dataset(self) -> "RandomCameraDataset":
+        return RandomCameraDataset(self.cfg, "val", ray_device=self.ray_device)
+
+    def test_dataset(self) -> "RandomCameraDataset":
+        return RandomCameraDataset(self.cfg, "test", ray_device=self.ray_device)
+
 
 @register("mvdream-random-multiview-camera-datamodule")
 class RandomMultiviewCameraIterableDataset(RandomCameraIterableDataset):
@@ -281,3 +288,64 @@ class RandomMultiviewCameraIterableDataset(RandomCameraIterableDataset):
 
     def _fovy_keys(self, f32, fovy, fovy_deg, proj):
         return {"fovy": f32(fovy_deg)}                                   # degrees (uncond_multiview.py:254)
+
+
+class RandomCameraDataset:
+    """threestudio/data/uncond.py:347-467: the orbit of evaluation cameras — n views at the fixed eval_* elevation, distance and
+    fovy, up +z, the light at the camera, near / far 0.01 / 100 (hard-coded there for both datamodules, as is fovy in radians).
+    `val` spreads n azimuths over [0, 360) so that the first and last view differ; `test` over [0, 360] with both ends.
+    The camera scalars are computed once on the host (float64, emitted as float32); rays are generated per batch on the device
+    (asd_generate_rays) instead of the reference's table for all views — 755 MB at 120 x 512^2.  Iterating yields the batches of the
+    reference's DataLoader (batch_size 1)."""
+
+    HOST_KEYS = ("mvp_mtx", "c2w", "camera_positions", "light_positions", "elevation", "azimuth", "camera_distances", "fovy", "proj_mtx")
+
+    def __init__(self, cfg: Any, split: str, ray_device: Optional[torch.device] = None) -> None:
+        self.cfg = parse_structured(RandomCameraDataModuleConfig, cfg) if isinstance(cfg, dict) else cfg
+        self.split = split
+        c = self.cfg
+        if c.eval_batch_size != 1:
+            raise ValueError(f"eval_batch_size must be 1 (got {c.eval_batch_size}): the reference's `up` vector is repeated eval_batch_size "
+                             "times and only broadcasts against the views for 1 (uncond.py:389-391)")
+        self.n_views = n = c.n_val_views if split == "val" else c.n_test_views
+        self.ray_device = ray_device
+        azimuth_deg = np.linspace(0.0, 360.0, n + 1)[:n] if split == "val" else np.linspace(0.0, 360.0, n)
+        elevation_deg = np.full(n, float(c.eval_elevation_deg))
+        distance = np.full(n, float(c.eval_camera_distance))
+        fovy = np.radians(np.full(n, float(c.eval_fovy_deg)))
+        positions = _spherical(distance, np.radians(elevation_deg), np.radians(azimuth_deg))
+        c2w = look_at(positions, np.zeros_like(positions), np.array([0.0, 0.0, 1.0])[None])
+        proj = projection(fovy, c.eval_width / c.eval_height, 0.01, 100.0)
+        f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+        self.host = {"mvp_mtx": f32(mvp(c2w, proj)), "c2w": f32(c2w), "camera_positions": f32(positions), "light_positions": f32(positions),
+                     "elevation": f32(elevation_deg), "azimuth": f32(azimuth_deg), "camera_distances": f32(distance), "fovy": f32(fovy),
+                     "proj_mtx": f32(proj)}
+        self.focal_length = f32(0.5 * c.eval_height / np.tan(0.5 * fovy))
+
+    def __len__(self) -> int:
+        return self.n_views
+
+    def cameras(self, indices) -> Dict[str, Any]:
+        """the collated batch of these views without the rays (host tensors), plus focal_length"""
+        idx = torch.as_tensor(list(indices), dtype=torch.int64)
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= self.n_views):
+            raise IndexError(f"view index outside [0, {self.n_views})")
+        out: Dict[str, Any] = {"index": idx}
+        out.update({k: self.host[k][idx] for k in self.HOST_KEYS})
+        out.update({"height": self.cfg.eval_height, "width": self.cfg.eval_width, "focal_length": self.focal_length[idx]})
+        return out
+
+    def collate(self, batch) -> Dict[str, Any]:
+        """batch: view indices, or items of __getitem__ (their `index`)"""
+        out = self.cameras([b["index"] if isinstance(b, dict) else b for b in batch])
+        out["rays_o"], out["rays_d"] = rays_from_cameras(out["c2w"], out.pop("focal_length"), self.cfg.eval_height, self.cfg.eval_width,
+                                                         self.cfg.rays_d_normalize, device=self.ray_device)
+        return out
+
+    def __getitem__(self, index: int) -> Dict[str, Any]:
+        b = self.collate([index])
+        return {k: (v[0] if torch.is_tensor(v) else v) for k, v in b.items()} | {"index": int(index)}
+
+    def __iter__(self):
+        for i in range(self.n_views):
+            yield self.collate([i])

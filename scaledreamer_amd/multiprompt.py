@@ -19,9 +19,10 @@ import torch
 
 from .base import get_rank
 from .config import parse_structured
-from .data import RandomCameraDataModuleConfig, RandomCameraIterableDataset, RandomMultiviewCameraIterableDataset
+from .data import RandomCameraDataModuleConfig, RandomCameraDataset, RandomCameraIterableDataset, RandomMultiviewCameraIterableDataset
 from .guidance import shift_azimuth_deg, shifted_expotional_decay
-from .registry import find, register
+from .registry import find, info, register
+from .saving import compose, panels_of, write_png
 from .system import StableDreamer, binary_cross_entropy, dot
 
 
@@ -151,6 +152,84 @@ class SyntheticMultiPromptProcessor:
                                 [self.table[p][2] for p in prompt], self.uncond_vd, **self.kw)
 
 
+class MultipromptRandomCameraDataset4Test:
+    """custom/amortized/data/multiprompt.py:85-122: one batch per prompt of the rank's shard of `split` (of "val" when the library has no
+    such split), holding ALL n_views cameras of the orbit; the noise is the first of n_views interpolated vectors, drawn here."""
+
+    def __init__(self, cfg: Any, split: str, prompt_library: Dict[str, List[str]], ray_device=None) -> None:
+        self.dataset = RandomCameraDataset(cfg, split, ray_device=ray_device)
+        self.cfg, self.n_views = self.dataset.cfg, self.dataset.n_views
+        start_point = torch.randn(self.cfg.dim_gaussian)
+        end_point = torch.randn(self.cfg.dim_gaussian)
+        self.noises = torch.stack([start_point + (end_point - start_point) * i / self.n_views for i in range(self.n_views)])
+        self.prompt_library = list(prompt_library[split] if split in prompt_library else prompt_library["val"])
+
+    def __len__(self) -> int:
+        return len(self.prompt_library)
+
+    def collate(self, batch: Dict[str, Any]) -> Dict[str, Any]:
+        out = self.dataset.collate(range(self.n_views))
+        out["noise"] = self.noises[0][None, :]
+        out.update(batch)
+        return out
+
+    def __iter__(self):
+        for prompt in self.prompt_library:
+            yield self.collate({"prompt": [prompt]})
+
+
+class MultipromptRandomCameraDataset4FixPrompt:
+    """custom/amortized/data/multiprompt.py:125-164: one view per batch for the fixed `eval_prompt`, zero noise; with `target_prompt` the
+    batch carries it and the interpolation ratio linspace(0, 1, n)[idx]; `eval_fix_camera` pins the camera to that view (a value of 0 is
+    falsy there and pins nothing).  Iterating yields the batches of the reference's DataLoader (batch_size 1, default collate)."""
+
+    def __init__(self, cfg: Any, split: str, ray_device=None) -> None:
+        self.dataset = RandomCameraDataset(cfg, split, ray_device=ray_device)
+        self.cfg, self.n_views = self.dataset.cfg, self.dataset.n_views
+        self.noise = torch.zeros(self.cfg.dim_gaussian)
+        self.eval_prompt, self.target_prompt = self.cfg.eval_prompt, self.cfg.target_prompt
+        self.ratios = torch.linspace(0, 1, self.n_views)
+        self.fix_camera = self.cfg.eval_fix_camera
+
+    def __len__(self) -> int:
+        return self.n_views
+
+    def _extras(self, idx: int) -> Dict[str, Any]:
+        out: Dict[str, Any] = {"noise": self.noise, "prompt": self.eval_prompt, "index": idx}
+        if self.target_prompt is not None:
+            out["prompt_target"] = self.target_prompt
+            out["ratio"] = self.ratios[idx]
+        out["name"] = "_to_".join([self.eval_prompt, self.target_prompt]) if self.target_prompt is not None else self.eval_prompt
+        return out
+
+    def host_item(self, idx: int) -> Dict[str, Any]:
+        """__getitem__ without the rays (host tensors)"""
+        cam = self.dataset.cameras([self.fix_camera if self.fix_camera else idx])
+        out = {k: (v[0] if torch.is_tensor(v) else v) for k, v in cam.items() if k != "focal_length"}
+        out.update(self._extras(idx))
+        return out
+
+    def __getitem__(self, idx: int) -> Dict[str, Any]:
+        out = self.dataset[self.fix_camera if self.fix_camera else idx]
+        out.update(self._extras(idx))
+        return out
+
+    def __iter__(self):
+        for idx in range(self.n_views):
+            out = self.dataset.collate([self.fix_camera if self.fix_camera else idx])
+            for k, v in self._extras(idx).items():
+                out[k] = v[None] if torch.is_tensor(v) else (torch.tensor([v]) if isinstance(v, int) else [v])
+            yield out
+
+
+def _eval_dataset(cfg, split: str, prompt_splits, ray_device):
+    """setup() of the reference's multi-prompt datamodules (multiprompt.py:189-201): validation runs the prompts of the split, testing the
+    fixed `eval_prompt` when one is set"""
+    if split == "test" and cfg.eval_prompt is not None:
+        return MultipromptRandomCameraDataset4FixPrompt(cfg, "test", ray_device=ray_device)
+    return MultipromptRandomCameraDataset4Test(cfg, split, prompt_splits, ray_device=ray_device)
+
+
 @dataclass
 class MultipromptRandomCameraDataModuleConfig(RandomCameraDataModuleConfig):
     dim_gaussian: int = 512
@@ -180,6 +259,13 @@ class MultipromptRandomCameraIterableDataset(RandomCameraIterableDataset):
         n_ranks = int(os.environ.get("WORLD_SIZE", max(1, torch.cuda.device_count()))) if n_ranks is None else n_ranks
         assert "train" in prompt_library, "prompt library must contain train split"
         self.prompt_library = list(prompt_library["train"])[rank::n_ranks]     # multiprompt.py:177-186
+        self.prompt_splits = {k: list(v)[rank::n_ranks] for k, v in prompt_library.items()}      # every split is sharded there
+
+    def val_dataset(self):
+        return _eval_dataset(self.cfg, "val", self.prompt_splits, self.ray_device)
+
+    def test_dataset(self):
+        return _eval_dataset(self.cfg, "test", self.prompt_splits, self.ray_device)
 
     def cameras(self) -> Dict[str, Any]:
         """camera draws, then the generator noise and the prompt choice (custom/amortized/data/multiprompt.py:62-83); collate() adds
@@ -229,6 +315,13 @@ class MultiviewMultipromptRandomCameraIterableDataset(RandomMultiviewCameraItera
         n_ranks = int(os.environ.get("WORLD_SIZE", max(1, torch.cuda.device_count()))) if n_ranks is None else n_ranks
         assert "train" in prompt_library, "prompt library must contain train split"
         self.prompt_library = list(prompt_library["train"])[rank::n_ranks]
+        self.prompt_splits = {k: list(v)[rank::n_ranks] for k, v in prompt_library.items()}
+
+    def val_dataset(self):
+        return _eval_dataset(self.mp_cfg, "val", self.prompt_splits, self.ray_device)
+
+    def test_dataset(self):
+        return _eval_dataset(self.mp_cfg, "test", self.prompt_splits, self.ray_device)
 
     def cameras(self) -> Dict[str, Any]:
         groups = self.batch_size // self.n_view
@@ -273,3 +366,65 @@ class MultipromptRadienceFieldGeneratorSystem(StableDreamer):
 
     def _rgb_as_latents(self) -> bool:
         return self.cfg.rgb_as_latents
+
+    # ---- validation / test passes (multiprompt_radience_field_generator.py:218-394) ---------------------------------------------------
+    EVAL_VIEWS_PER_CALL = 16        # views rendered per eval forward: the renderer keeps every per-sample output of a call alive
+
+    @staticmethod
+    def _eval_name(batch) -> str:
+        name = batch["name"][0] if "name" in batch else batch["prompt"][0]
+        return name.replace(",", "").replace(".", "").replace(" ", "_")
+
+    def _eval_outputs(self, batch) -> Dict[str, torch.Tensor]:
+        """the panel outputs of all V views of the batch.  More than EVAL_VIEWS_PER_CALL views are rendered in slices of views — eval mode
+        draws nothing, and the renderer goes view by view against the one prompt anyway, so the images are those of one call."""
+        V = batch["rays_o"].shape[0]
+        K = self.EVAL_VIEWS_PER_CALL
+        if V <= K:
+            out = self(dict(batch))
+            return {k: out[k] for k in self.EVAL_PANEL_KEYS if k in out}
+        per_view = [k for k, v in batch.items() if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == V and k not in ("noise", "ratio")]
+        parts = []
+        for v0 in range(0, V, K):
+            out = self({k: (v[v0:v0 + K] if k in per_view else v) for k, v in batch.items()})
+            parts.append({k: out[k] for k in self.EVAL_PANEL_KEYS if k in out})
+        return {k: torch.cat([p[k] for p in parts], dim=0) for k in parts[0]}
+
+    def _eval_step(self, batch, stem: str):
+        if self.cfg.rgb_as_latents:
+            raise NotImplementedError("rgb_as_latents: the image grid shows decoded_rgb, which needs the guidance's decode_latents "
+                                      "(the VAE decoder); this port has the encoder only")
+        out = self._eval_outputs(batch)
+        grids = compose(panels_of(self._grid_columns(out, select=lambda t: t), batched=True))        # one launch for all views
+        name = self._eval_name(batch)
+        for b in range(grids.shape[0]):
+            self._record(write_png(self.get_save_path(f"{stem}/{name}/{int(batch['index'][b])}.png"), grids[b]))
+
+    def validation_step(self, batch, batch_idx: int = 0):
+        self._eval_step(batch, f"it{self.true_global_step}-val" if self.cfg.validation_via_video else f"it{self.true_global_step}")
+        if self.cfg.visualize_samples:
+            raise NotImplementedError
+
+    def test_step(self, batch, batch_idx: int = 0):
+        self._eval_step(batch, f"it{self.true_global_step}-test")
+
+    def _prompt_videos(self, filestem: str, fps: int, name: str):
+        """one sequence per prompt directory; a prompt that fails is reported and the loop goes on, as there (:297-309)"""
+        if get_rank() != 0:
+            return
+        root = os.path.join(self.get_save_dir(), filestem)
+        for prompt in sorted(os.listdir(root)):
+            if not os.path.isdir(os.path.join(root, prompt)):
+                continue
+            try:
+                self._record(self.save_img_sequence(os.path.join(filestem, prompt), os.path.join(filestem, prompt), r"(\d+)\.png",
+                                                    save_format="mp4", fps=fps, name=name, step=self.true_global_step, multithreaded=True))
+            except Exception:
+                info("cannot save {} at step {}".format(prompt, self.true_global_step))
+
+    def on_validation_epoch_end(self):
+        if self.cfg.validation_via_video:
+            self._prompt_videos(f"it{self.true_global_step}-val", 10, "validation_epoch_end")
+
+    def on_test_epoch_end(self):
+        self._prompt_videos(f"it{self.true_global_step}-test", 30, "test")

@@ -809,3 +809,58 @@ def atlas_pack_u8(values: torch.Tensor, texel_index: torch.Tensor, image: torch.
     check(lib().asd_atlas_pack_u8(ptr(values), ptr(texel_index), C.c_int64(values.shape[0]), i32(values.shape[1]), ptr(image), C.c_int64(n_texels),
                                   stream()))
     return image
+
+
+# ---- float images to bytes (csrc/image.hip) ---------------------------------------------------
+def image_minmax(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [n_images, ...] -> [n_images, 2] = (min, max) over everything but the first dimension, with torch.min / torch.max semantics (a
+    NaN makes both NaN): the depth normalisation of threestudio/systems/scaledreamer.py:176-178 (asd_image_minmax_f32)"""
+    _need_cuda(x)
+    x = _c(x)
+    n_images = x.shape[0]
+    n_per_image = x.numel() // n_images if n_images else 1
+    if out is None:
+        out = torch.empty((n_images, 2), device=x.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n_images, 2) or not out.is_cuda or not out.is_contiguous():
+        raise L.AsdError(f"out must be a contiguous device float32 tensor of shape {(n_images, 2)}")
+    nbytes = lib().asd_image_minmax_workspace(C.c_int64(n_images), C.c_int64(n_per_image))
+    if nbytes < 0:
+        raise L.AsdError(lib().asd_last_error().decode())
+    ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32) if nbytes else None
+    check(lib().asd_image_minmax_f32(ptr(x), C.c_int64(n_images), C.c_int64(n_per_image), ptr(out), ptr(ws), C.c_int64(nbytes), stream()))
+    return out
+
+
+def image_grid(panels, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """panels: up to 8 of (kind "rgb" | "grayscale", src, lo, hi, normalize) over the same [B, H, W] pixels — src [B,H,W,3] for rgb,
+    [B,H,W] for grayscale -> uint8 [B, H, P W, 3], the panels side by side in RGB order (asd_image_grid_u8: get_image_grid_,
+    threestudio/utils/saving.py:255-299, for equal-sized panels).  `normalize` (grayscale) maps the panel to its own per-image range
+    first, from asd_image_minmax_f32 of its source."""
+    if not 1 <= len(panels) <= 8:
+        raise L.AsdError(f"an image grid takes 1 to 8 panels (got {len(panels)})")
+    table = (L.ImagePanel * len(panels))()
+    keep, shape = [], None
+    for j, (kind, src, lo, hi, normalize) in enumerate(panels):
+        _need_cuda(src)
+        if kind not in ("rgb", "grayscale"):
+            raise L.AsdError(f"panel {j}: kind {kind!r} is neither 'rgb' nor 'grayscale'")
+        src = _c(src)
+        want = 4 if kind == "rgb" else 3
+        if src.dim() != want or (kind == "rgb" and src.shape[-1] != 3):
+            raise L.AsdError(f"panel {j}: a {kind} panel is [B,H,W{',3' if kind == 'rgb' else ''}] (got {tuple(src.shape)})")
+        if shape is None:
+            shape = tuple(src.shape[:3])
+        elif tuple(src.shape[:3]) != shape:
+            raise L.AsdError(f"panel {j}: {tuple(src.shape[:3])} pixels, the first panel has {shape}: panels of unequal size are not resized")
+        mm = image_minmax(src) if normalize else None
+        keep += [src, mm]
+        table[j] = L.ImagePanel(src.data_ptr(), mm.data_ptr() if mm is not None else None, L.ASD_PANEL_RGB if kind == "rgb" else L.ASD_PANEL_GRAYSCALE,
+                                int(bool(normalize)), float(lo), float(hi))
+    B, H, W = shape
+    P = len(panels)
+    if out is None:
+        out = torch.empty((B, H, P * W, 3), device=keep[0].device, dtype=torch.uint8)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, H, P * W, 3) or not out.is_cuda or not out.is_contiguous():
+        raise L.AsdError(f"out must be a contiguous device uint8 tensor of shape {(B, H, P * W, 3)}")
+    check(lib().asd_image_grid_u8(table, i32(P), C.c_int64(B), i32(H), i32(W), ptr(out), stream()))
+    return out

@@ -9,6 +9,7 @@ all-reduced once per optimizer step over RCCL (what Lightning's DDP does in the 
 from __future__ import annotations
 
 import os
+import shutil
 from dataclasses import dataclass, field
 from typing import Any, Dict, Optional
 
@@ -18,7 +19,8 @@ import torch.nn as nn
 from . import dist as asd_dist
 from .base import Updateable, get_device
 from .config import C, ConfigDict, parse_structured
-from .registry import find, register
+from .registry import find, info, register
+from .saving import SaverMixin
 
 
 def dot(x, y):
@@ -113,7 +115,7 @@ def parse_optimizer(config, model) -> torch.optim.Optimizer:
 
 
 @register("scaledreamer-system")
-class StableDreamer(nn.Module, Updateable):
+class StableDreamer(nn.Module, Updateable, SaverMixin):
     @dataclass
     class Config:
         loggers: dict = field(default_factory=dict)
@@ -298,6 +300,89 @@ class StableDreamer(nn.Module, Updateable):
                                    map_Ks=p["map_Ks"], map_Bump=p["map_Bump"], map_Pm=p["map_Pm"], map_Pr=p["map_Pr"], map_format=p["map_format"])
                 paths += written if isinstance(written, list) else [written]     # with a material: MTL and textures first, the OBJ last
         return paths
+
+    # ---- validation / test passes (scaledreamer.py:172-315) -------------------------------------------------------------------------
+    # The reference's Lightning loops are the two drivers at the end; each step renders one batch of the orbit in eval mode and writes one
+    # image grid: comp_rgb | comp_normal (if rendered) | opacity | depth mapped to its own per-image range.  Float panels become bytes on
+    # the device (saving.compose -> asd_image_minmax_f32, asd_image_grid_u8); the depth normalisation the reference does with torch
+    # before it hands the panel over (:176-178) is the kernel's `normalize`, asked for with data_range None.
+    EVAL_PANEL_KEYS = ("comp_rgb", "comp_normal", "opacity", "depth")
+
+    @staticmethod
+    def _grid_columns(out, select=lambda t: t[0]):
+        """the reference's list of panel dicts; `select` takes what a panel shows from the [B, H, W, C] output"""
+        cols = []
+        if "comp_rgb" in out:
+            cols.append({"type": "rgb", "img": select(out["comp_rgb"]), "kwargs": {"data_format": "HWC"}})
+        if "comp_normal" in out:
+            cols.append({"type": "rgb", "img": select(out["comp_normal"]), "kwargs": {"data_format": "HWC", "data_range": (0, 1)}})
+        cols.append({"type": "grayscale", "img": select(out["opacity"])[..., 0], "kwargs": {"cmap": None, "data_range": (0, 1)}})
+        if "depth" in out:
+            cols.append({"type": "grayscale", "img": select(out["depth"])[..., 0], "kwargs": {"cmap": None, "data_range": None}})
+        return cols
+
+    def _record(self, path: str) -> str:
+        if getattr(self, "_written", None) is not None:
+            self._written.append(path)
+        return path
+
+    def validation_step(self, batch, batch_idx: int = 0):
+        out = self(batch)
+        index = int(batch["index"][0])
+        via_video = self.cfg.validation_via_video
+        self._record(self.save_image_grid(f"it{self.true_global_step}-val/{index}.png" if via_video else f"it{self.true_global_step}-{index}.png",
+                                          self._grid_columns(out), name=f"validation_step_batchidx_{batch_idx}" if via_video else "validation_step",
+                                          step=self.true_global_step))
+        if self.cfg.visualize_samples:
+            raise NotImplementedError
+
+    def on_validation_epoch_end(self):
+        if not self.cfg.validation_via_video:
+            return
+        filestem = f"it{self.true_global_step}-val"
+        self._record(self.save_img_sequence(filestem, filestem, r"(\d+)\.png", save_format="mp4", fps=30, name="validation_epoch_end",
+                                            step=self.true_global_step))
+        frames = os.path.join(self.get_save_dir(), filestem)
+        shutil.rmtree(frames)
+        if getattr(self, "_written", None) is not None:
+            self._written = [p for p in self._written if not p.startswith(frames + os.sep)]
+
+    def test_step(self, batch, batch_idx: int = 0):
+        out = self(batch)
+        self._record(self.save_image_grid(f"it{self.true_global_step}-test/{int(batch['index'][0])}.png", self._grid_columns(out), name="test_step",
+                                          step=self.true_global_step))
+
+    def on_test_epoch_end(self):
+        filestem = f"it{self.true_global_step}-test"
+        self._record(self.save_img_sequence(filestem, filestem, r"(\d+)\.png", save_format="mp4", fps=30, name="test", step=self.true_global_step))
+
+    def _batch_to_device(self, batch: Dict[str, Any]) -> Dict[str, Any]:
+        return {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in batch.items()}
+
+    def _run_eval(self, dataset, save_dir: str, step, epoch_end):
+        """what Lightning's validate / test loop does around the hooks: eval mode, no gradients, every batch through `step`, then
+        `epoch_end`; no update hooks.  Returns the paths that exist afterwards."""
+        was_training = self.training
+        self.set_save_dir(save_dir)
+        self._written = []
+        self.eval()
+        try:
+            with torch.no_grad():
+                for batch_idx, batch in enumerate(dataset):
+                    step(self._batch_to_device(batch), batch_idx)
+                epoch_end()
+            return list(self._written)
+        finally:
+            self._written = None
+            self.train(was_training)
+
+    def validate(self, dataset, save_dir: str):
+        """`launch.py --validate`: dataset is what `val_dataset()` of the datamodule returns"""
+        return self._run_eval(dataset, save_dir, self.validation_step, self.on_validation_epoch_end)
+
+    def test(self, dataset, save_dir: str):
+        """`launch.py --test`: dataset is what `test_dataset()` of the datamodule returns"""
+        return self._run_eval(dataset, save_dir, self.test_step, self.on_test_epoch_end)
 
     def gradient_exchange(self):
         """the DP exchange object of this system (None on a single process): created on first use, after the process group."""
