@@ -287,6 +287,48 @@ int asd_compact(const float* rays_o, const float* rays_d, int32_t n_rays,
                 int64_t* ray_idx_out, float* t_start_out, float* t_end_out,
                 float* points_out /*[.,3]*/, float* dirs_out /*[.,3]*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * NeuS opacity model on packed, ragged rays: what `neus-volume-renderer` (threestudio/models/renderers/neus_volume_renderer.py)
+ * does between the occupancy-grid marcher above and the image that is not a field, material or background call.  Ray r owns the
+ * samples [offset[r], offset[r] + count[r]) of every per-sample array.  `inv_std_param` is a DEVICE pointer to the one raw float of
+ * LearnedVariance._inv_std (:26-37), as in asd_volsdf_*: every kernel forms a = clamp(exp(10 p), 1e-6, 1e6), and with `use_volsdf`
+ * clamps it to [0, 80] on top (volsdf_density, :19-23).
+ * ---------------------------------------------------------------------------------------------- */
+/* alpha_fn (:139-166) and occ_eval_fn (:364-377), elementwise: NeuS prev = sigmoid((sdf + step/2) a), next = sigmoid((sdf - step/2) a),
+ * alpha = clip((prev - next + 1e-5) / (prev + 1e-5), 0, 1); VolSDF alpha = step * volsdf_density(sdf, a).
+ * If n_dev != NULL the live count is read on the device and n is the launch bound (as asd_field_density). */
+int asd_neus_step_alpha(const float* sdf /*[n]*/, int32_t n, const int32_t* n_dev, const float* inv_std_param /*[1]*/, float step,
+                        int32_t use_volsdf, float* alpha /*[n]*/, void* stream);
+/* asd_prune_count with the alpha above formed in place (nerfacc render_visibility_from_alpha behind estimator.sampling(alpha_fn=...),
+ * :183-194): keep[i] = T_i >= early_stop_eps && alpha_i >= alpha_thre, T_i = prod_{k<i} (1 - alpha_k) per ray; kept_count[r]. */
+int asd_neus_prune_count(const float* sdf, const int32_t* offset, const int32_t* count, int32_t n_rays, const float* inv_std_param,
+                         float step, int32_t use_volsdf, float early_stop_eps, float alpha_thre, uint8_t* keep, int32_t* kept_count,
+                         void* stream);
+/* One pass per ray (:286-313).  Alpha is get_alpha (:93-117): true_cos = dirs . normal, iter_cos = -(relu(0.5 - 0.5 true_cos) (1 - k) +
+ * relu(-true_cos) k) with k = cos_anneal_ratio, prev / next = sigmoid((sdf -/+ iter_cos dt / 2) a), alpha = clip((prev - next + 1e-5) /
+ * (prev + 1e-5), 0, 1); with use_volsdf alpha = |dt| volsdf_density(sdf, a), not clipped.  dt = t_end - t_start, t = (t_start + t_end) / 2.
+ * T_i = prod_{k<i} (1 - alpha_k); weights = T alpha; opacity = sum w; depth = sum w t; rgb_fg = sum w c with c = features (color_act 0) or
+ * sigmoid(features) (color_act 1); comp_rgb = rgb_fg + bg (1 - opacity); comp_normal (NULL: skipped) is the evaluation image
+ * (normalize(sum w n, eps 1e-12) + 1) / 2 * opacity (:337-344).  count[r] == 0: zeros and comp_rgb = bg. */
+int asd_neus_composite_fwd(const float* sdf /*[n]*/, const float* normal /*[n,3]*/, const float* dirs /*[n,3]*/, const float* t_start /*[n]*/,
+                           const float* t_end /*[n]*/, const float* features /*[n,3]*/, int32_t color_act, const float* inv_std_param /*[1]*/,
+                           float cos_anneal_ratio, int32_t use_volsdf, const float* bg /*[n_rays,3]*/, const int32_t* offset,
+                           const int32_t* count, int32_t n_rays, float* weights /*[n]*/, float* opacity /*[n_rays]*/, float* depth /*[n_rays]*/,
+                           float* rgb_fg /*[n_rays,3]*/, float* comp_rgb /*[n_rays,3]*/, float* comp_normal /*[n_rays,3] or NULL*/, void* stream);
+/* The autograd backward of the pass above.  Upstream gradients: any may be NULL.  d_sdf, d_normal (or NULL; through true_cos, zero for
+ * VolSDF), d_features, d_bg (or NULL) are written (=), not accumulated; nothing flows to dirs or the interval ends.  Alpha and the
+ * transmittance are formed again (only weights and opacity are read from the forward pass) and nothing is divided by 1 - alpha: the NeuS
+ * alpha reaches 1 exactly.  Derivative conventions are torch's: relu'(0) = 0, clip / clamp pass the gradient on the closed interval,
+ * sign(0) = 0.  d_inv_std_param [1] (NULL: the variance is frozen) needs `dp_partial`, [n_rays] floats of scratch: one partial per ray,
+ * added in a fixed order by a second small launch — no atomics, the same bits every run. */
+int asd_neus_composite_bwd(const float* sdf, const float* normal, const float* dirs, const float* t_start, const float* t_end,
+                           const float* features, int32_t color_act, const float* inv_std_param, float cos_anneal_ratio, int32_t use_volsdf,
+                           const float* bg, const int32_t* offset, const int32_t* count, int32_t n_rays,
+                           const float* weights, const float* opacity /* forward outputs */,
+                           const float* d_comp_rgb, const float* d_rgb_fg, const float* d_opacity, const float* d_depth, const float* d_weights,
+                           float* d_sdf /*[n]*/, float* d_normal /*[n,3] or NULL*/, float* d_features /*[n,3]*/, float* d_bg /*[n_rays,3] or NULL*/,
+                           float* d_inv_std_param /*[1] or NULL*/, float* dp_partial /*[n_rays] or NULL*/, void* stream);
+
 /* Camera rays on the device (replaces the CPU tensor code of get_ray_directions / get_rays, threestudio/utils/ops.py:183-269, called
  * from RandomCameraIterableDataset.collate, threestudio/data/uncond.py:326-337, and the H2D copy of the [B,H,W,3] ray tensors):
  * d = ((i + 0.5 - W/2) / focal, -(j + 0.5 - H/2) / focal, -1), rays_d = R d (normalised when `normalize`), rays_o = c2w[:3,3].

@@ -164,6 +164,7 @@ SYMBOLS = [
     "asd_importance_resample", "asd_transmittance_cdf", "asd_merge_sorted", "asd_voxel_sample_fwd", "asd_voxel_sample_bwd", "asd_voxel_sample_bwd_rows",
     "asd_triplane_sample_fwd", "asd_triplane_sample_bwd", "asd_triplane_sample_bwd_rows", "asd_relayout_f32",
     "asd_volsdf_edges", "asd_volsdf_samples", "asd_volsdf_proposal_cdf", "asd_volsdf_composite_fwd", "asd_volsdf_composite_bwd",
+    "asd_neus_step_alpha", "asd_neus_prune_count", "asd_neus_composite_fwd", "asd_neus_composite_bwd",
     "asd_generate_rays", "asd_march_count", "asd_scan_i32", "asd_march_write", "asd_prune_count", "asd_compact",
     "asd_occgrid_update", "asd_composite_fwd", "asd_composite_bwd",
     "asd_gemm_f16", "asd_gemm_force_tile", "asd_groupnorm_f16", "asd_groupnorm_bwd_f16", "asd_transpose_f16", "asd_layernorm_f16", "asd_softmax_f16", "asd_softmax_bwd_f16", "asd_geglu_f16", "asd_silu_f16",
@@ -214,6 +215,11 @@ def lib() -> C.CDLL:
         l.asd_vae_enc_destroy.restype = None
         l.asd_unet_destroy.argtypes = [C.c_void_p]
         l.asd_vae_enc_destroy.argtypes = [C.c_void_p]
+        vp, i, f = C.c_void_p, C.c_int32, C.c_float
+        l.asd_neus_step_alpha.argtypes = [vp, i, vp, vp, f, i, vp, vp]
+        l.asd_neus_prune_count.argtypes = [vp, vp, vp, i, vp, f, i, f, f, vp, vp, vp]
+        l.asd_neus_composite_fwd.argtypes = [vp] * 6 + [i, vp, f, i, vp, vp, vp, i] + [vp] * 7
+        l.asd_neus_composite_bwd.argtypes = [vp] * 6 + [i, vp, f, i, vp, vp, vp, i] + [vp] * 14
         _lib = l
     return _lib
 

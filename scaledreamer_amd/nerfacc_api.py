@@ -150,8 +150,8 @@ class OccGridEstimator(nn.Module):
             raise NotImplementedError("cone_angle != 0 is not used by the reference renderer")
         if t_min is not None or t_max is not None:
             raise NotImplementedError("per-ray t_min/t_max")
-        if alpha_fn is not None:
-            raise NotImplementedError("alpha_fn (the reference passes sigma_fn)")
+        if alpha_fn is not None and sigma_fn is not None:
+            raise ValueError("Only one of sigma_fn and alpha_fn can be specified.")
         rays_o, rays_d = rays_o.contiguous().float(), rays_d.contiguous().float()
         n_rays = rays_o.shape[0]
         if stratified and jitter is None:
@@ -159,15 +159,20 @@ class OccGridEstimator(nn.Module):
         cfg = self.march_cfg(near_plane, far_plane, render_step_size)
         bits = self._bits()
         count, offset, total, ray_idx, t0, t1, pts = ops.march(cfg, rays_o, rays_d, bits, jitter)
-        if sigma_fn is not None and (early_stop_eps > 0 or alpha_thre > 0):
+        prune_fn = sigma_fn if sigma_fn is not None else alpha_fn
+        if prune_fn is not None and (early_stop_eps > 0 or alpha_thre > 0):
             alpha_thre = min(alpha_thre, self._occ_mean)
             n_cand = ray_idx.shape[0]
             if n_cand > 0:
-                sigmas = sigma_fn(t0, t1, ray_idx.long()).reshape(-1).contiguous().float()
-                assert sigmas.shape[0] == n_cand, f"sigmas must have shape of (N,)! Got {sigmas.shape}"
+                vals = prune_fn(t0, t1, ray_idx.long()).reshape(-1).contiguous().float()
+                assert vals.shape[0] == n_cand, f"{'sigmas' if sigma_fn is not None else 'alphas'} must have shape of (N,)! Got {vals.shape}"
             else:
-                sigmas = t0.new_zeros(0)
-            keep, kept = ops.prune(sigmas, t0, t1, offset, count, early_stop_eps, alpha_thre)
+                vals = t0.new_zeros(0)
+            if sigma_fn is None:
+                # neus_volume_renderer.py:183-194: the same pruning pass on opacities; asd_prune_count takes densities, and
+                # 1 - exp(-sigma dt) with sigma = -log(1 - alpha) / dt is alpha again (alpha >= 1: sigma = inf, T = 0 behind it)
+                vals = (-torch.log1p(-vals.clamp(max=1.0)) / (t1 - t0)).contiguous()
+            keep, kept = ops.prune(vals, t0, t1, offset, count, early_stop_eps, alpha_thre)
             koff, ktot = ops.scan_i32(kept)
             n_out = int(ktot.item())
             ri, k0, k1, _, _ = ops.compact(rays_o, rays_d, offset, count, keep, t0, t1, koff, n_out)

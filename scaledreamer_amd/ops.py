@@ -350,6 +350,63 @@ def volsdf_composite_bwd(sdf, features, normal, t_edges, inv_std_param, bg, colo
     return d_sdf, d_feat, d_bg, d_p
 
 
+# ---- NeuS opacity model on packed rays (include/asd_hip.h: asd_neus_*) -----------------------------------------------
+def neus_step_alpha(sdf: torch.Tensor, inv_std_param: torch.Tensor, step: float, use_volsdf: bool, n_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """alpha of a sample of length `step` around every sdf value, in the shape of `sdf` (alpha_fn / occ_eval_fn of the NeuS renderer)"""
+    _need_cuda(sdf, inv_std_param)
+    k = _Keep()
+    alpha = torch.empty(sdf.shape, device=sdf.device, dtype=torch.float32)
+    check(lib().asd_neus_step_alpha(k(sdf), i32(sdf.numel()), ptr(n_dev), k(inv_std_param), f32(step), i32(int(use_volsdf)), ptr(alpha), stream()))
+    return alpha
+
+
+def neus_prune(sdf, offset, count, inv_std_param, step: float, use_volsdf: bool, early_stop_eps: float, alpha_thre: float):
+    """-> (keep uint8 [n], kept int32 [n_rays]) of the packed candidates, alpha formed in the kernel"""
+    _need_cuda(sdf, offset, count, inv_std_param)
+    k = _Keep()
+    nr = count.shape[0]
+    keep = torch.empty(sdf.numel(), device=sdf.device, dtype=torch.uint8)
+    kept = torch.empty(nr, device=sdf.device, dtype=torch.int32)
+    check(lib().asd_neus_prune_count(k(sdf), ptr(offset), ptr(count), i32(nr), k(inv_std_param), f32(step), i32(int(use_volsdf)),
+                                     f32(early_stop_eps), f32(alpha_thre), ptr(keep), ptr(kept), stream()))
+    return keep, kept
+
+
+def neus_composite_fwd(sdf, normal, dirs, t0, t1, features, color_act: int, inv_std_param, cos_anneal_ratio: float, use_volsdf: bool, bg,
+                       offset, count, want_comp_normal: bool = False):
+    """the whole compositing pass of the NeuS renderer over packed rays"""
+    _need_cuda(sdf, normal, dirs, t0, t1, features, inv_std_param, bg, offset, count)
+    k = _Keep()
+    nr, n, dev = count.shape[0], sdf.numel(), sdf.device
+    new = lambda *sh: torch.empty(sh, device=dev, dtype=torch.float32)
+    out = dict(weights=new(n), opacity=new(nr), depth=new(nr), rgb_fg=new(nr, 3), comp_rgb=new(nr, 3),
+               comp_normal=new(nr, 3) if want_comp_normal else None)
+    check(lib().asd_neus_composite_fwd(k(sdf), k(normal), k(dirs), k(t0), k(t1), k(features), i32(color_act), k(inv_std_param),
+                                       f32(cos_anneal_ratio), i32(int(use_volsdf)), k(bg), ptr(offset), ptr(count), i32(nr), ptr(out["weights"]),
+                                       ptr(out["opacity"]), ptr(out["depth"]), ptr(out["rgb_fg"]), ptr(out["comp_rgb"]), ptr(out["comp_normal"]),
+                                       stream()))
+    return out
+
+
+def neus_composite_bwd(sdf, normal, dirs, t0, t1, features, color_act: int, inv_std_param, cos_anneal_ratio: float, use_volsdf: bool, bg,
+                       offset, count, fwd, d_comp_rgb=None, d_rgb_fg=None, d_opacity=None, d_depth=None, d_weights=None,
+                       want_normal: bool = True, want_bg: bool = True, want_inv_std: bool = False):
+    """-> (d_sdf [n], d_normal [n, 3] or None, d_features [n, 3], d_bg [n_rays, 3] or None, d_inv_std_param (shaped like the parameter) or None)"""
+    _need_cuda(sdf, normal, dirs, t0, t1, features, inv_std_param, bg, offset, count)
+    k = _Keep()
+    nr, n, dev = count.shape[0], sdf.numel(), sdf.device
+    new = lambda *sh: torch.empty(sh, device=dev, dtype=torch.float32)
+    d_sdf, d_feat = new(n), new(n, 3)
+    d_normal = new(n, 3) if want_normal else None
+    d_bg = new(nr, 3) if want_bg else None
+    d_p, partial = (torch.empty_like(inv_std_param, dtype=torch.float32), new(nr)) if want_inv_std else (None, None)
+    check(lib().asd_neus_composite_bwd(k(sdf), k(normal), k(dirs), k(t0), k(t1), k(features), i32(color_act), k(inv_std_param),
+                                       f32(cos_anneal_ratio), i32(int(use_volsdf)), k(bg), ptr(offset), ptr(count), i32(nr), ptr(fwd["weights"]),
+                                       ptr(fwd["opacity"]), k(d_comp_rgb), k(d_rgb_fg), k(d_opacity), k(d_depth), k(d_weights), ptr(d_sdf),
+                                       ptr(d_normal), ptr(d_feat), ptr(d_bg), ptr(d_p), ptr(partial), stream()))
+    return d_sdf, d_normal, d_feat, d_bg, d_p
+
+
 def relayout(x: torch.Tensor) -> torch.Tensor:
     """[batch, rows, cols] -> [batch, cols, rows] (fp32)."""
     _need_cuda(x)
