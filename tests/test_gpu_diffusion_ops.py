@@ -37,6 +37,11 @@ def test_gemm_bias_rowbias_residual_silu(M, N, K):
     for sk in (1, 3):
         _close(H.gemm(a, w, split_k=sk), a.float() @ w.float().T)
     _close(H.gemm(a, w, out_f32=True), a.float() @ w.float().T, tol=1e-3)
+    for tile in (0, 12):      # the same again on a pinned plan: what is checked no longer depends on what the tuner timed
+        plan = dict(tile_cfg=tile + 1, split_k=1)
+        _close(H.gemm(a, w, bias=bias, row_bias=rb, rows_per_group=M // groups, residual=res, act=1, **plan), ref)
+        _close(H.gemm(a, w, **plan), a.float() @ w.float().T)
+        _close(H.gemm(a, w, out_f32=True, **plan), a.float() @ w.float().T, tol=1e-3)
 
 
 def test_gemm_strided_views():
@@ -49,6 +54,11 @@ def test_gemm_strided_views():
     H.gemm(a, w, out=outbuf[:, 192:384])
     _close(outbuf[:, 192:384], a.float() @ w.float().T)
     assert float(outbuf[:, :192].abs().max()) == 0 and float(outbuf[:, 384:].abs().max()) == 0
+    for tile in (0, 12):      # the same again on a pinned plan: what is checked no longer depends on what the tuner timed
+        outbuf.zero_()
+        H.gemm(a, w, out=outbuf[:, 192:384], tile_cfg=tile + 1, split_k=1)
+        _close(outbuf[:, 192:384], a.float() @ w.float().T)
+        assert float(outbuf[:, :192].abs().max()) == 0 and float(outbuf[:, 384:].abs().max()) == 0
 
 
 @pytest.mark.parametrize("B,H_,W_,Cin,Cout,stride,pad,up", [
