@@ -973,6 +973,34 @@ typedef struct {
  * 4-byte aligned, B H n_panels W < 2^31).  `panels` is a host array. */
 int asd_image_grid_u8(const AsdImagePanel* panels, int32_t n_panels, int64_t B, int32_t H, int32_t W, uint8_t* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * CLIP evaluation of test renders (csrc/clip.hip; the schedule is scaledreamer_amd/clip_eval.py).
+ *
+ * Front end: frames uint8 [B, H, Wfull, 3] RGB (the image grids of asd_image_grid_u8).  The left H x H square of each frame is resized to
+ * S x S exactly as PIL's Image.resize((S, S), BILINEAR) does on 8-bit data: a horizontal and a vertical pass, each
+ * clip8((2^21 + sum_x in[x + xmin] * kk[x]) >> 22) in int32 and rounded to a byte; H == S skips both.  The taps come from the caller:
+ * bounds int32 [S, 2] = (xmin, tap count) and kk int32 [S, ksize] of the size pair H -> S (clip_eval.resize_tables), device arrays used by
+ * both passes; tmp uint8 [B, H, S, 3] holds the first pass (all three may be null when H == S).  Then (u8 / 255 - mean_c) / std_c in fp32
+ * with CLIP's constants, stored as fp16 patch rows [B (S/P)^2, Kpad] of row stride ldp: row b g^2 + py g + px, column c P^2 + dy P + dx (the flattening of
+ * the patch convolution's weight), columns 3 P^2 .. Kpad zero (Kpad % 8 == 0: the K of asd_gemm_f16).  resized (optional) receives the
+ * uint8 [B, S, S, 3] image.  Wfull < H is an error. */
+int asd_clip_preprocess_u8(const uint8_t* frames, int32_t B, int32_t H, int32_t Wfull, int32_t S, int32_t P, int32_t Kpad, const int32_t* bounds,
+                           const int32_t* kk, int32_t ksize, uint8_t* tmp, uint8_t* resized, void* patches, int32_t ldp, void* stream);
+/* Token assembly: out [B, Lpad, C] fp16 = LayerNorm(cat(class_embedding, patch rows) + position_embedding) for the first g2 + 1 rows of each
+ * image (sum and statistics in fp32), zeros for the rows up to Lpad (Lpad % 8 == 0, the lk_stride of asd_attention_f16).
+ * patch [B g2, C], class_embedding [C], position_embedding [g2 + 1, C], gamma, beta [C]: fp16, 16-byte aligned; C % 8 == 0, C <= 2048. */
+int asd_clip_embed_f16(const void* patch, const void* class_embedding, const void* position_embedding, const void* gamma, const void* beta, float eps,
+                       int32_t B, int32_t g2, int32_t C, int32_t Lpad, void* out, void* stream);
+/* y = x * sigmoid(1.702 x) elementwise, fp16, any n >= 1 (x, y 16-byte aligned; may be the same buffer). */
+int asd_quick_gelu_f16(const void* x, int64_t n, void* y, void* stream);
+/* Scoring, fp32 throughout and without atomics: img [B, D] (any scale, L2-normalised here), txt [P, D] (L2-normalised by the caller),
+ * own int32 [B]: sim[b] = <img_b / |img_b|, txt[own[b]]> (NaN when own[b] is outside [0, P)), top1[b] = argmax_p <img_b, txt_p> with the
+ * lowest index among equal values (P when nothing compares, i.e. a NaN row).  D <= 1024.  The workspace holds one (value, index) per
+ * image and 64-prompt chunk. */
+int64_t asd_clip_score_workspace(int64_t B, int64_t P);
+int asd_clip_score_f32(const float* img, const float* txt, const int32_t* own, int64_t B, int64_t P, int32_t D, float* sim, int32_t* top1,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
 /* library info */
 const char* asd_version(void);
 const char* asd_last_error(void);

@@ -188,6 +188,7 @@ SYMBOLS = [
     "asd_mesh_cc_round", "asd_mesh_face_counts", "asd_mesh_keep", "asd_mesh_compact",
     "asd_atlas_layout", "asd_atlas_uv", "asd_atlas_bake", "asd_atlas_pack_u8",
     "asd_image_minmax_workspace", "asd_image_minmax_f32", "asd_image_grid_u8",
+    "asd_clip_preprocess_u8", "asd_clip_embed_f16", "asd_quick_gelu_f16", "asd_clip_score_workspace", "asd_clip_score_f32",
     "asd_comm_unique_id", "asd_comm_create", "asd_comm_destroy", "asd_allreduce_mean_f32",
     "asd_version", "asd_last_error", "asd_modulated_weights_fwd", "asd_modulated_weights_bwd", "asd_timestep_plus", "asd_loss_tail_fwd", "asd_loss_tail_bwd", "asd_probe_events", "asd_probe_mark",
 ]
@@ -209,7 +210,8 @@ def lib() -> C.CDLL:
         l.asd_grid_meta_init.argtypes = [C.POINTER(GridMeta), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double]
         for fn in ("asd_gemm_workspace_bytes", "asd_unet_workspace_bytes", "asd_unet_workspace_bytes_shared", "asd_vae_enc_workspace_bytes",
                    "asd_conv3d_workspace_bytes", "asd_tx_linear_workspace", "asd_tx_wgrad_workspace", "asd_tx_attention_workspace",
-                   "asd_tritx_packed_floats", "asd_tritx_save_floats", "asd_tritx_workspace_floats", "asd_image_minmax_workspace"):
+                   "asd_tritx_packed_floats", "asd_tritx_save_floats", "asd_tritx_workspace_floats", "asd_image_minmax_workspace",
+                   "asd_clip_score_workspace"):
             getattr(l, fn).restype = C.c_int64
         l.asd_unet_destroy.restype = None
         l.asd_vae_enc_destroy.restype = None
