@@ -507,6 +507,12 @@ int asd_groupnorm_f16(const void* x1, int32_t c1, const void* x2, int32_t c2, in
                       const void* gamma, const void* beta, float eps, int32_t silu, void* y,
                       float* stats /* ASD_GN_STATS_FLOATS(batch): [batch*32*2] sums for the backward pass + per-block partials */,
                       void* stream);
+/* the same GroupNorm, reproducible to the bit: its statistics are summed in a fixed order on a grid that depends on (hw, c) only, so an
+ * image's result depends neither on the call nor on the batch it is part of (asd_groupnorm_f16 folds its threads' sums with atomics in
+ * arrival order, and sizes its grid by the batch).  One tensor, c <= 2048, batch * min(32, ceil(hw / 64)) <= 512.  Used by the VAE
+ * decoder (decode_latents, stable_diffusion_asd_guidance.py:180-194: diffusers GroupNorm inside vae.decode). */
+int asd_groupnorm_ordered_f16(const void* x, int32_t c, int32_t batch, int32_t hw, const void* gamma, const void* beta, float eps,
+                              int32_t silu, void* y, float* stats, void* stream);
 /* the same GroupNorm when the tensor's producer already left its statistics as `records` 64-float records per batch element
  * (asd_gemm_args.gn_partials): no statistics pass over x.  stats: ASD_GN_STATS_FLOATS(batch) floats; its first batch*64 receive the
  * per-(batch, group) sums (kept for a backward pass). */
@@ -642,6 +648,24 @@ int asd_vae_enc_fwd(asd_vae_enc* h, const void* x_nhwc32, int32_t batch, int32_t
 int asd_vae_enc_bwd(asd_vae_enc* h, const float* d_moments_nhwc, int32_t batch, int32_t H, int32_t W, void* workspace,
                     int64_t workspace_bytes, void* dx_nhwc32, int32_t tune, void* stream);
 
+/* VAE decoder, forward only: replaces self.vae.decode of decode_latents (stable_diffusion_asd_guidance.py:180-194; Decoder
+ * diffusionmodules/model.py:546-655) behind asd_latent_decode_prep, which applies the resize, 1 / scaling_factor and post_quant_conv
+ * (models/autoencoder.py:33,87-90).  Same protocol as the encoder; the descriptor is the encoder's (in_channels = image channels).
+ * hl, wl: even, hl * wl a multiple of 8; batch <= 16.  workspace_bytes returns -ASD_ERR_ARG (and sets the error text) for a shape it
+ * refuses.  An image's output is the same bits in every call and every batch: the schedule runs unsplit GEMM tiles chosen from a
+ * layer's width alone and asd_groupnorm_ordered_f16, so `tune` is accepted for the protocol's sake and ignored. */
+typedef struct asd_vae_dec asd_vae_dec;
+int asd_vae_dec_create(const asd_vae_desc* desc, asd_vae_dec** out);
+void asd_vae_dec_destroy(asd_vae_dec* h);
+int32_t asd_vae_dec_num_weights(const asd_vae_dec* h);
+int asd_vae_dec_weight_info(const asd_vae_dec* h, int32_t i, asd_weight_info* info);
+int asd_vae_dec_bind_weights(asd_vae_dec* h, const void* const* device_ptrs, int32_t count);
+int64_t asd_vae_dec_workspace_bytes(asd_vae_dec* h, int32_t batch, int32_t hl, int32_t wl, int32_t tune);
+/* z_nhwc32: fp16 [batch,hl,wl,32], channels >= z_channels zero; x_nhwc32: fp16 [batch,8hl,8wl,32] (for four levels), channels <
+ * in_channels hold the decoded image in [-1,1] before any clamp, the rest are zero */
+int asd_vae_dec_fwd(asd_vae_dec* h, const void* z_nhwc32, int32_t batch, int32_t hl, int32_t wl, void* workspace, int64_t workspace_bytes,
+                    void* x_nhwc32, int32_t tune, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * ASD latent-space glue (csrc/asd_glue.hip): everything between the rendered image and the scalar loss that is not a network.
  * Replaces the torch elementwise code of SDTimestepShiftedScoreDistillationGuidance.__call__ / get_latents / encode_images /
@@ -679,6 +703,25 @@ int asd_prompt_context(const float* text_vd, const float* uncond_vd, int32_t n_d
 /* d loss / d moments (fp32 [B,hl,wl,2C]) given grad: d z = upstream * grad / B (upstream: device scalar or NULL = 1) */
 int asd_latents_bwd(const float* grad, const float* moments_nhwc, const float* post_noise, const float* upstream, int32_t B, int32_t C,
                     int32_t hl, int32_t wl, float scaling, float* d_moments_nhwc, void* stream);
+/* Latent-space rendering (rgb_as_latents: the field renders the 4 latent channels).
+ * asd_latent_input_fwd replaces get_latents' latent branch (stable_diffusion_asd_guidance.py:199-202, mvdream_asd_guidance.py:117-120:
+ * F.interpolate(rgb_BCHW, (hl, wl), "bilinear", align_corners=False)) and the two add_noise calls (:242-246): latents fp32 NCHW
+ * [B,4,hl,wl] = the resized render_bhwc fp32 [B,h,w,4] (no posterior sample, no scaling factor); unet_x / unet_t as asd_latents_fwd. */
+int asd_latent_input_fwd(const float* render_bhwc, const float* noise, const int64_t* t, const int64_t* t_plus, const float* alphas_cumprod,
+                         int32_t B, int32_t h, int32_t w, int32_t hl, int32_t wl, int32_t n_rep, float* latents, void* unet_x, float* unet_t,
+                         void* stream);
+/* the gradient autograd carries through that resize (:281-283 loss_asd.backward): d_render_bhwc fp32 [B,h,w,4] = bilinear adjoint of
+ * upstream * grad / B (grad fp32 NCHW [B,4,hl,wl]; upstream: device scalar or NULL = 1) */
+int asd_latent_input_bwd(const float* grad, const float* upstream, int32_t B, int32_t h, int32_t w, int32_t hl, int32_t wl, float* d_render_bhwc,
+                         void* stream);
+/* front of decode_latents (stable_diffusion_asd_guidance.py:186-190): z_nhwc32 fp16 [B,hl,wl,32] = post_quant_conv(bilinear(latents_bhwc
+ * fp32 [B,h,w,4] -> (hl, wl)) * inv_scaling), channels 4..31 zero.  post_quant20 (device fp32): the 1x1 convolution's W[4][4] (out, in)
+ * and bias[4] (models/autoencoder.py:33,87-88). */
+int asd_latent_decode_prep(const float* latents_bhwc, int32_t B, int32_t h, int32_t w, int32_t hl, int32_t wl, float inv_scaling,
+                           const float* post_quant20, void* z_nhwc32, void* stream);
+/* tail of decode_latents (:192-193): image fp32 [n_pixels,3] = clamp(0.5 x + 0.5, 0, 1) of the decoder's padded output x_nhwc32 fp16
+ * [n_pixels,32]; raw (or NULL) receives x[:, 0:3] itself as fp32 */
+int asd_image_from_decoder(const void* x_nhwc32, int64_t n_pixels, float* image, float* raw, void* stream);
 /* t_plus = clamp(t + (int64)(u * clamp(plus_ratio * (t - min_step), 0, T - 1 - t)), 1, T - 1) in the reference's float32 arithmetic
  * (stable_diffusion_asd_guidance.py:294-316 get_t_plus); u: fp32 [n] uniform draws, or NULL (plus_random off: u = 1) */
 int asd_timestep_plus(const int64_t* t, const float* u, int32_t n, int64_t min_step, int64_t num_train_timesteps, float plus_ratio,

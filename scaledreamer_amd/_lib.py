@@ -169,13 +169,16 @@ SYMBOLS = [
     "asd_occgrid_update", "asd_composite_fwd", "asd_composite_bwd",
     "asd_gemm_f16", "asd_gemm_force_tile", "asd_groupnorm_f16", "asd_groupnorm_bwd_f16", "asd_transpose_f16", "asd_layernorm_f16", "asd_softmax_f16", "asd_softmax_bwd_f16", "asd_geglu_f16", "asd_silu_f16",
     "asd_timestep_embedding_f16", "asd_concat_f16", "asd_attention_f16",
-    "asd_gemm_plan_set", "asd_gemm_plan_get", "asd_gemm_plan_count", "asd_gemm_plan_generation", "asd_gemm_plan_entry", "asd_gemm_tile_info", "asd_gemm_workspace_bytes", "asd_gemm_tune", "asd_gemm_gn_records", "asd_gemm_gn_applies", "asd_groupnorm_apply_f16", "asd_groupnorm_bwd_apply_f16",
+    "asd_gemm_plan_set", "asd_gemm_plan_get", "asd_gemm_plan_count", "asd_gemm_plan_generation", "asd_gemm_plan_entry", "asd_gemm_tile_info", "asd_gemm_workspace_bytes", "asd_gemm_tune", "asd_gemm_gn_records", "asd_gemm_gn_applies", "asd_groupnorm_apply_f16", "asd_groupnorm_bwd_apply_f16", "asd_groupnorm_ordered_f16",
     "asd_pad_cast_f16",
     "asd_image_prep_fwd", "asd_image_prep_bwd", "asd_latents_fwd", "asd_score_fwd", "asd_latents_bwd", "asd_prompt_context",
     "asd_unet_create", "asd_unet_destroy", "asd_unet_num_weights", "asd_unet_weight_info", "asd_unet_bind_weights",
     "asd_unet_workspace_bytes", "asd_unet_fwd", "asd_unet_workspace_bytes_shared", "asd_unet_fwd_shared", "asd_gather_rows_f16",
     "asd_vae_enc_create", "asd_vae_enc_destroy", "asd_vae_enc_num_weights", "asd_vae_enc_weight_info", "asd_vae_enc_bind_weights",
     "asd_vae_enc_workspace_bytes", "asd_vae_enc_fwd", "asd_vae_enc_bwd",
+    "asd_vae_dec_create", "asd_vae_dec_destroy", "asd_vae_dec_num_weights", "asd_vae_dec_weight_info", "asd_vae_dec_bind_weights",
+    "asd_vae_dec_workspace_bytes", "asd_vae_dec_fwd",
+    "asd_latent_input_fwd", "asd_latent_input_bwd", "asd_latent_decode_prep", "asd_image_from_decoder",
     "asd_adamw_f32", "asd_adan_f32",
     "asd_conv3d_workspace_bytes", "asd_conv3d_fwd", "asd_conv3d_dgrad", "asd_conv3d_wgrad", "asd_layer_act_bwd", "asd_upsample3d_fwd", "asd_upsample3d_bwd",
     "asd_torgb_fwd", "asd_torgb_bwd", "asd_absmax_f32", "asd_voxfield_fwd", "asd_voxfield_bwd_workspace", "asd_voxfield_bwd",
@@ -209,6 +212,7 @@ def lib() -> C.CDLL:
         l.asd_grid_meta_init.restype = C.c_uint32
         l.asd_grid_meta_init.argtypes = [C.POINTER(GridMeta), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double]
         for fn in ("asd_gemm_workspace_bytes", "asd_unet_workspace_bytes", "asd_unet_workspace_bytes_shared", "asd_vae_enc_workspace_bytes",
+                   "asd_vae_dec_workspace_bytes",
                    "asd_conv3d_workspace_bytes", "asd_tx_linear_workspace", "asd_tx_wgrad_workspace", "asd_tx_attention_workspace",
                    "asd_tritx_packed_floats", "asd_tritx_save_floats", "asd_tritx_workspace_floats", "asd_image_minmax_workspace",
                    "asd_clip_score_workspace"):
@@ -217,11 +221,20 @@ def lib() -> C.CDLL:
         l.asd_vae_enc_destroy.restype = None
         l.asd_unet_destroy.argtypes = [C.c_void_p]
         l.asd_vae_enc_destroy.argtypes = [C.c_void_p]
+        l.asd_vae_dec_destroy.restype = None
+        l.asd_vae_dec_destroy.argtypes = [C.c_void_p]
         vp, i, f = C.c_void_p, C.c_int32, C.c_float
         l.asd_neus_step_alpha.argtypes = [vp, i, vp, vp, f, i, vp, vp]
         l.asd_neus_prune_count.argtypes = [vp, vp, vp, i, vp, f, i, f, f, vp, vp, vp]
         l.asd_neus_composite_fwd.argtypes = [vp] * 6 + [i, vp, f, i, vp, vp, vp, i] + [vp] * 7
         l.asd_neus_composite_bwd.argtypes = [vp] * 6 + [i, vp, f, i, vp, vp, vp, i] + [vp] * 14
+        l.asd_latent_input_fwd.argtypes = [vp] * 5 + [i] * 6 + [vp] * 4
+        l.asd_latent_input_bwd.argtypes = [vp, vp] + [i] * 5 + [vp, vp]
+        l.asd_latent_decode_prep.argtypes = [vp] + [i] * 5 + [f, vp, vp, vp]
+        l.asd_image_from_decoder.argtypes = [vp, C.c_int64, vp, vp, vp]
+        l.asd_vae_dec_workspace_bytes.argtypes = [vp, i, i, i, i]
+        l.asd_groupnorm_ordered_f16.argtypes = [vp, i, i, i, vp, vp, f, i, vp, vp, vp]
+        l.asd_vae_dec_fwd.argtypes = [vp, vp, i, i, i, vp, C.c_int64, vp, i, vp]
         _lib = l
     return _lib
 

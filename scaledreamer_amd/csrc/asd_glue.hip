@@ -10,6 +10,11 @@
 //   asd_latents_bwd          d loss / d moments through the posterior sample (gradient reaches the VAE encoder, :225)
 //   asd_prompt_context       view-dependent / Perp-Neg prompt selection (prompt_processors/base.py:82-167, 262-294) written into the
 //                            UNet's context buffer in get_eps' batch order, with the Perp-Neg weights
+// Latent-space rendering (rgb_as_latents: the field renders the 4 latent channels themselves):
+//   asd_latent_input_fwd/bwd the render resized to the UNet's latent grid IS the latents (:196-202 get_latents, mvdream_asd_guidance.py:
+//                            114-120): resize + both noisings in one launch, and the resize's adjoint — no VAE, no posterior sample
+//   asd_latent_decode_prep   resize, 1 / scaling_factor and post_quant_conv in front of the VAE decoder (:180-191 decode_latents)
+//   asd_image_from_decoder   clamp(0.5 x + 0.5, 0, 1) behind it (:192-193)
 // MVDream (mvdream_asd_guidance.py:181-304) is the same with n_rep = 2, n_neg = 0 and one t per 4-view group.
 #include "asd_common.h"
 
@@ -367,6 +372,145 @@ __global__ __launch_bounds__(128) void prompt_context_kernel(const float* __rest
     }
 }
 
+// ---- latent-space rendering -----------------------------------------------------------------------------------------------------
+// bilinear sample of the 4 channels of pixel (Y, X) of the resized image.  Same operands and order as image_prep_fwd_kernel and ATen,
+// (1-ly) * ((1-lx) v00 + lx v01) + ly * ((1-lx) v10 + lx v11), with the roundings of ATen's device kernel, which is compiled with
+// contraction on: each sum is one fma on its FIRST product, fma(1-lx, v00, lx * v01) and fma(1-ly, top, ly * bottom).  Latents are
+// signed, the sums cancel, and any other placement of the roundings is hundreds of ulp of a small result away (measured against
+// F.interpolate on an MI355X: this form 0 ulp on every tested size; the unfused form up to 6272 ulp)
+__device__ __forceinline__ float bilerp_aten(float v00, float v01, float v10, float v11, float ly, float lx) {
+    const float top = fmaf(1.f - lx, v00, lx * v01), bottom = fmaf(1.f - lx, v10, lx * v11);
+    return fmaf(1.f - ly, top, ly * bottom);
+}
+__device__ __forceinline__ void bilinear4(const float* __restrict__ p /*[h,w,4]*/, int h, int w, int Y, int X, float sy, float sx, float* v) {
+    int y0, y1, x0, x1;
+    float ly, lx;
+    bilinear_src(Y, sy, h, &y0, &y1, &ly);
+    bilinear_src(X, sx, w, &x0, &x1, &lx);
+    const float4 v00 = *reinterpret_cast<const float4*>(p + ((size_t)y0 * w + x0) * 4), v01 = *reinterpret_cast<const float4*>(p + ((size_t)y0 * w + x1) * 4);
+    const float4 v10 = *reinterpret_cast<const float4*>(p + ((size_t)y1 * w + x0) * 4), v11 = *reinterpret_cast<const float4*>(p + ((size_t)y1 * w + x1) * 4);
+    v[0] = bilerp_aten(v00.x, v01.x, v10.x, v11.x, ly, lx);
+    v[1] = bilerp_aten(v00.y, v01.y, v10.y, v11.y, ly, lx);
+    v[2] = bilerp_aten(v00.z, v01.z, v10.z, v11.z, ly, lx);
+    v[3] = bilerp_aten(v00.w, v01.w, v10.w, v11.w, ly, lx);
+}
+
+// one thread per latent pixel: z = post_quant_conv(bilinear(render) / scaling_factor) as the decoder's NHWC-32 input
+__global__ __launch_bounds__(256) void latent_decode_prep_kernel(const float* __restrict__ lat /*[B,h,w,4]*/, int B, int h, int w, int hl, int wl,
+                                                                 float inv_scaling, const float* __restrict__ pq /*W[4][4] (out, in), bias[4]*/,
+                                                                 half_t* __restrict__ z /*[B,hl,wl,32]*/) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)B * hl * wl) return;
+    const int X = (int)(i % wl), Y = (int)((i / wl) % hl), b = (int)(i / ((size_t)wl * hl));
+    float v[4];
+    bilinear4(lat + (size_t)b * h * w * 4, h, w, Y, X, (float)h / (float)hl, (float)w / (float)wl, v);
+    half_t o[32];
+#pragma unroll
+    for (int c = 0; c < 32; ++c) o[c] = (half_t)0.f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) v[c] *= inv_scaling;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float a = pq[16 + j];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) a = fmaf(pq[4 * j + c], v[c], a);
+        o[j] = (half_t)a;
+    }
+    uint4* dst = reinterpret_cast<uint4*>(z + i * 32);
+    const uint4* src = reinterpret_cast<const uint4*>(o);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) dst[q] = src[q];
+}
+
+// one thread per pixel of the decoder's padded output: image = clamp(0.5 x + 0.5, 0, 1), optionally x itself (pre-clamp, for parity tests)
+__global__ __launch_bounds__(256) void image_from_decoder_kernel(const half_t* __restrict__ x /*[n,32]*/, size_t n, float* __restrict__ image /*[n,3]*/,
+                                                                 float* __restrict__ raw /*[n,3] | null*/) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint2 r = *reinterpret_cast<const uint2*>(x + i * 32);
+    const half_t* v = reinterpret_cast<const half_t*>(&r);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float f = (float)v[c];
+        image[i * 3 + c] = fminf(fmaxf(f * 0.5f + 0.5f, 0.f), 1.f);
+        if (raw) raw[i * 3 + c] = f;
+    }
+}
+
+// the latent-space counterpart of latents_fwd_kernel: the resized render is z (no posterior sample, no scaling factor); both noisings and
+// the timesteps go into the UNet's buffers in the same batch order and replication
+__global__ __launch_bounds__(256) void latent_input_fwd_kernel(const float* __restrict__ render /*[B,h,w,4]*/, const float* __restrict__ noise /*[B,4,hw]*/,
+                                                               const int64_t* __restrict__ t, const int64_t* __restrict__ t_plus,
+                                                               const float* __restrict__ alphas, int B, int h, int w, int hl, int wl, int n_rep,
+                                                               float* __restrict__ latents /*[B,4,hw]*/, half_t* __restrict__ unet_x /*[(n_rep+1)B,hw,32]*/,
+                                                               float* __restrict__ unet_t) {
+    const int i = blockIdx.x * 256 + threadIdx.x, hw = hl * wl;
+    if (i < (n_rep + 1) * B) unet_t[i] = (float)(i < n_rep * B ? t[i % B] : t_plus[i - n_rep * B]);
+    if (i >= B * hw) return;
+    const int b = i / hw, p = i - b * hw;
+    const float a0 = alphas[t[b]], a1 = alphas[t_plus[b]];
+    const float sa0 = sqrtf(a0), sn0 = sqrtf(1.f - a0), sa1 = sqrtf(a1), sn1 = sqrtf(1.f - a1);
+    float z[4];
+    bilinear4(render + (size_t)b * h * w * 4, h, w, p / wl, p % wl, (float)h / (float)hl, (float)w / (float)wl, z);
+    half_t x0[32], x1[32];
+#pragma unroll
+    for (int c = 0; c < 32; ++c) { x0[c] = (half_t)0.f; x1[c] = (half_t)0.f; }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const size_t q = ((size_t)b * 4 + c) * hw + p;
+        latents[q] = z[c];
+        const float e = noise[q];
+        x0[c] = (half_t)(sa0 * z[c] + sn0 * e);
+        x1[c] = (half_t)(sa1 * z[c] + sn1 * e);
+    }
+    const uint4* s0 = reinterpret_cast<const uint4*>(x0);
+    const uint4* s1 = reinterpret_cast<const uint4*>(x1);
+    for (int r = 0; r <= n_rep; ++r) {
+        uint4* dst = reinterpret_cast<uint4*>(unet_x + ((size_t)(r * B + b) * hw + p) * 32);
+        const uint4* src = r < n_rep ? s0 : s1;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) dst[q] = src[q];
+    }
+}
+
+// adjoint of the resize as a gather (image_prep_bwd_kernel): one wave per render pixel, its lanes share the latent pixels whose footprint
+// contains it.  The candidate window is the interval of destinations whose source coordinate lies in (s - 1, s + 1), widened by one and
+// clamped to the grid: it covers the clamp of negative source coordinates to 0 (source row 0 collects every destination above it), a
+// single source row or column (h == 1: every destination row) and the wide footprints of an upscale (h < hl); the weights themselves are
+// recomputed by bilinear_src, so a candidate that does not touch the pixel contributes an exact 0.
+__global__ __launch_bounds__(256) void latent_input_bwd_kernel(const float* __restrict__ grad /*[B,4,hl*wl]*/, const float* __restrict__ upstream, int B,
+                                                               int h, int w, int hl, int wl, float* __restrict__ d_render /*[B,h,w,4]*/) {
+    const int pix = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (pix >= B * h * w) return;
+    const int xs = pix % w, ys = (pix / w) % h, b = pix / (w * h), hw = hl * wl;
+    const float sy = (float)h / (float)hl, sx = (float)w / (float)wl;
+    int Y0 = (int)floorf(((float)ys - 0.5f) / sy - 0.5f) - 1, Y1 = (int)ceilf(((float)ys + 1.5f) / sy - 0.5f) + 1;
+    int X0 = (int)floorf(((float)xs - 0.5f) / sx - 0.5f) - 1, X1 = (int)ceilf(((float)xs + 1.5f) / sx - 0.5f) + 1;
+    Y0 = Y0 < 0 ? 0 : Y0; X0 = X0 < 0 ? 0 : X0; Y1 = Y1 > hl - 1 ? hl - 1 : Y1; X1 = X1 > wl - 1 ? wl - 1 : X1;
+    const int nx = X1 - X0 + 1, n = nx * (Y1 - Y0 + 1);
+    const float* g = grad + (size_t)b * 4 * hw;
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int k = lane; k < n; k += 64) {
+        const int Y = Y0 + k / nx, X = X0 + k % nx;
+        int y0, y1, x0, x1;
+        float ly, lx;
+        bilinear_src(Y, sy, h, &y0, &y1, &ly);
+        bilinear_src(X, sx, w, &x0, &x1, &lx);
+        const float wy = (y0 == ys ? 1.f - ly : 0.f) + (y1 == ys ? ly : 0.f);
+        const float wx = (x0 == xs ? 1.f - lx : 0.f) + (x1 == xs ? lx : 0.f);
+        const float wt = wy * wx;
+        if (wt == 0.f) continue;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) a[c] = fmaf(wt, g[(size_t)c * hw + Y * wl + X], a[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) a[c] = asd_wave_sum(a[c]);
+    if (lane == 0) {
+        const float up = (upstream ? upstream[0] : 1.f) / (float)B;      // d loss / d z = grad / B
+        *reinterpret_cast<float4*>(d_render + (size_t)pix * 4) = make_float4(up * a[0], up * a[1], up * a[2], up * a[3]);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -472,6 +616,44 @@ int asd_loss_tail_bwd(const float* upstream, const float* weights, int32_t n_ter
     for (int j = 0; j < ASD_LOSS_MAX_TERMS; ++j) { t.value[j] = nullptr; t.weight[j] = j < n_terms ? weights[j] : 0.f; }
     hipLaunchKernelGGL(loss_tail_bwd_kernel, dim3(asd_div_up((int)n_rays, 256)), dim3(256), 0, (hipStream_t)stream, t, upstream, opacity,
                        (long long)n_rays, lambda_sparsity, lambda_opaque, lambda_z_variance, out5, d_terms, d_opacity, d_z_variance);
+    ASD_LAUNCH_CHECK();
+    return ASD_OK;
+}
+
+int asd_latent_decode_prep(const float* latents_bhwc, int32_t B, int32_t h, int32_t w, int32_t hl, int32_t wl, float inv_scaling,
+                           const float* post_quant20, void* z_nhwc32, void* stream) {
+    ASD_CHECK_ARG(latents_bhwc && post_quant20 && z_nhwc32 && B > 0 && h > 0 && w > 0 && hl > 0 && wl > 0, "bad argument");
+    hipLaunchKernelGGL(latent_decode_prep_kernel, dim3(asd_div_up((int64_t)B * hl * wl, 256)), dim3(256), 0, (hipStream_t)stream, latents_bhwc, B, h, w,
+                       hl, wl, inv_scaling, post_quant20, (half_t*)z_nhwc32);
+    ASD_LAUNCH_CHECK();
+    return ASD_OK;
+}
+
+int asd_image_from_decoder(const void* x_nhwc32, int64_t n_pixels, float* image, float* raw, void* stream) {
+    ASD_CHECK_ARG(x_nhwc32 && image && n_pixels > 0, "bad argument");
+    hipLaunchKernelGGL(image_from_decoder_kernel, dim3(asd_div_up(n_pixels, 256)), dim3(256), 0, (hipStream_t)stream, (const half_t*)x_nhwc32,
+                       (size_t)n_pixels, image, raw);
+    ASD_LAUNCH_CHECK();
+    return ASD_OK;
+}
+
+int asd_latent_input_fwd(const float* render_bhwc, const float* noise, const int64_t* t, const int64_t* t_plus, const float* alphas_cumprod,
+                         int32_t B, int32_t h, int32_t w, int32_t hl, int32_t wl, int32_t n_rep, float* latents, void* unet_x, float* unet_t,
+                         void* stream) {
+    ASD_CHECK_ARG(render_bhwc && noise && t && t_plus && alphas_cumprod && latents && unet_x && unet_t, "null argument");
+    ASD_CHECK_ARG(B > 0 && h > 0 && w > 0 && hl > 0 && wl > 0 && n_rep >= 1 && (int64_t)B * hl * wl < ((int64_t)1 << 31), "latent input: n_rep >= 1, sizes positive");
+    const int n = B * hl * wl > (n_rep + 1) * B ? B * hl * wl : (n_rep + 1) * B;
+    hipLaunchKernelGGL(latent_input_fwd_kernel, dim3(asd_div_up(n, 256)), dim3(256), 0, (hipStream_t)stream, render_bhwc, noise, t, t_plus,
+                       alphas_cumprod, B, h, w, hl, wl, n_rep, latents, (half_t*)unet_x, unet_t);
+    ASD_LAUNCH_CHECK();
+    return ASD_OK;
+}
+
+int asd_latent_input_bwd(const float* grad, const float* upstream, int32_t B, int32_t h, int32_t w, int32_t hl, int32_t wl, float* d_render_bhwc,
+                         void* stream) {
+    ASD_CHECK_ARG(grad && d_render_bhwc && B > 0 && h > 0 && w > 0 && hl > 0 && wl > 0 && (int64_t)B * h * w < ((int64_t)1 << 31), "bad argument");
+    hipLaunchKernelGGL(latent_input_bwd_kernel, dim3(asd_div_up((int64_t)B * h * w, 4)), dim3(256), 0, (hipStream_t)stream, grad, upstream, B, h, w, hl,
+                       wl, d_render_bhwc);
     ASD_LAUNCH_CHECK();
     return ASD_OK;
 }

@@ -6,6 +6,8 @@
 //   asd_vae_enc_*  VAE encoder forward + input gradient    (stable_diffusion_asd_guidance.py:171-178 encode_images; Encoder
 //                  diffusionmodules/model.py:452-543, ResnetBlock :88-146, Downsample :66-85, AttnBlock :152-227, quant_conv
 //                  models/autoencoder.py:32,81-85)
+//   asd_vae_dec_*  VAE decoder, forward only                (stable_diffusion_asd_guidance.py:180-194 decode_latents; Decoder
+//                  diffusionmodules/model.py:546-655, Upsample :41-63; post_quant_conv is applied by asd_latent_decode_prep)
 // A network is a handle created once from its hyper-parameters.  It publishes the table of PACKED weights it reads (name, rows,
 // cols: conv -> [Cout][ky][kx][Cin], q|k fused, every time-embedding projection fused into one matrix, ...), the caller binds
 // device pointers to that table and owns the workspace; a forward is a single chain of kernel launches with no host
@@ -42,6 +44,8 @@ struct Run {                // state of one pass over a schedule
     hipStream_t stream = nullptr;
     bool dry = true;        // no launches
     bool tune = false;      // time un-tuned GEMM shapes before launching them
+    bool fixed = false;     // every GEMM on a tile chosen from its N alone, never split: an output element's sum order then depends
+                            // neither on the batch nor on the plan table (VAE decoder)
     float* scratch = nullptr;   // split-K slabs
     size_t scratch_bytes = 0, scratch_need = 0;
     const void* zero_page = nullptr;
@@ -115,7 +119,8 @@ void launch_gemm(Run& r, asd_gemm_args& g, Act* gn_out = nullptr, bool gn_bwd_fo
     g.zero_page = r.zero_page;
     g.split_k = 0;          // auto: tuned plan of this shape (asd_gemm_plan_*), else cost model
     g.tile_cfg = 0;
-    if (r.tune && !r.dry) {
+    if (r.fixed) { g.split_k = 1; g.tile_cfg = g.N % 128 == 0 ? 2 : 1; }      // PLAIN 128 x 128, else PLAIN 128 x 64 (any N)
+    if (r.tune && !r.fixed && !r.dry) {
         int32_t t, s;
         if (asd_gemm_plan_get(&g, &t, &s) != ASD_OK) {       // 1 = not tuned yet
             if (asd_gemm_tune(&g, r.scratch, (int64_t)r.scratch_bytes, r.stream) != ASD_OK) { r.status = ASD_ERR_LAUNCH; return; }
@@ -890,6 +895,161 @@ void vae_backward(Vae& n, Run& r, const std::vector<VSaved>& saved, const float*
     }
 }
 
+// ================================================================================================================================
+// VAE decoder: forward only — nothing is kept for a backward pass, the activations rotate through four buffers of the largest size
+// ================================================================================================================================
+struct VaeDec : Net {
+    asd_vae_desc d;
+    std::vector<VLayer> plan;       // 0 conv_in, 1 res, 3 attn, 4 out (norm_out + conv_out), 5 nearest-2x + conv
+};
+
+void d_norm(VaeDec& n, const std::string& p, int c) { n.add(p + ".weight", 1, c); n.add(p + ".bias", 1, c); }
+void d_conv(VaeDec& n, const std::string& p, int cin, int cout) { n.add(p + ".fwd", cout, 9 * pad32(cin)); n.add(p + ".bias", 1, cout); }
+void d_res(VaeDec& n, const std::string& p, int cin, int cout) {
+    d_norm(n, p + ".norm1", cin);
+    d_conv(n, p + ".conv1", cin, cout);
+    d_norm(n, p + ".norm2", cout);
+    d_conv(n, p + ".conv2", cout, cout);
+    if (cin != cout) { n.add(p + ".nin.w", cout, cin); n.add(p + ".nin.b", 1, cout); }
+    n.plan.push_back(VLayer{1, p, cin, cout});
+}
+
+// GroupNorm(32)(+SiLU) of an activation into a buffer the schedule owns, with the ordered statistics pass: an image's result is the
+// same bits in every call and every batch.  (Not the encoder's groupnorm(): its statistics pass sums in arrival order on a grid sized
+// by the batch, and it reserves an output whenever it is handed a null pointer, which every buffer is in a sizing pass.)
+void d_groupnorm(Run& r, const Act& x, int c, int B, int hw, const half_t* gamma, const half_t* beta, int silu, half_t* y, float* stats) {
+    LEAF(asd_groupnorm_ordered_f16(x.p, c, B, hw, gamma, beta, 1e-6f, silu, y, stats, r.stream));
+}
+
+// the construction loop of Decoder.__init__ (model.py:546-617)
+void vae_dec_build(VaeDec& n) {
+    const asd_vae_desc& d = n.d;
+    int block_in = d.ch * d.ch_mult[d.n_levels - 1];
+    d_conv(n, "decoder.conv_in", d.z_channels, block_in);
+    n.plan.push_back(VLayer{0, "decoder.conv_in", d.z_channels, block_in});
+    d_res(n, "decoder.mid.block_1", block_in, block_in);
+    {
+        const std::string p = "decoder.mid.attn_1";
+        d_norm(n, p + ".norm", block_in);
+        for (const char* nm : {".q", ".k", ".v", ".proj_out"}) { n.add(p + nm + ".w", block_in, block_in); n.add(p + nm + ".b", 1, block_in); }
+        n.plan.push_back(VLayer{3, p, block_in, block_in});
+    }
+    d_res(n, "decoder.mid.block_2", block_in, block_in);
+    for (int lvl = d.n_levels - 1; lvl >= 0; --lvl) {
+        const int block_out = d.ch * d.ch_mult[lvl];
+        for (int b = 0; b <= d.num_res_blocks; ++b) {
+            d_res(n, "decoder.up." + std::to_string(lvl) + ".block." + std::to_string(b), block_in, block_out);
+            block_in = block_out;
+        }
+        if (lvl != 0) {     // Upsample.conv in its parity form: [4 parities][cout][2 x 2 taps x cin] (weights._pack_upsample_conv3x3)
+            const std::string p = "decoder.up." + std::to_string(lvl) + ".upsample.conv";
+            n.add(p + ".fwd", 4 * block_in, 4 * pad32(block_in)); n.add(p + ".bias", 1, block_in);
+            n.plan.push_back(VLayer{5, p, block_in, block_in});
+        }
+    }
+    d_norm(n, "decoder.norm_out", block_in);
+    // the image channels padded to 32 output columns (zero rows, zero bias), as the encoder's conv_in input gradient pads its 3
+    n.add("decoder.conv_out.fwd", pad32(d.in_channels), 9 * block_in); n.add("decoder.conv_out.bias", 1, pad32(d.in_channels));
+    n.plan.push_back(VLayer{4, "decoder", block_in, pad32(d.in_channels)});
+}
+
+// Decoder.forward (model.py:619-655): z32 fp16 [B,hl,wl,32] (post_quant_conv already applied) -> x fp16 [B,H,W,pad32(in_channels)]
+void vae_dec_run(VaeDec& n, Run& r, const half_t* z32, int B, int hl, int wl, half_t* image32) {
+    size_t max_act = 0;
+    {
+        int hh = hl, ww = wl;
+        for (const VLayer& l : n.plan) {
+            if (l.kind == 5) { hh *= 2; ww *= 2; }
+            const size_t a = (size_t)B * hh * ww * (l.cin > l.cout ? l.cin : l.cout);
+            if (a > max_act) max_act = a;
+        }
+    }
+    half_t* buf[4];
+    for (int j = 0; j < 4; ++j) buf[j] = r.mem.halfs(max_act);
+    float* stats = r.mem.floats(ASD_GN_STATS_FLOATS(B));      // one GroupNorm at a time reads them: no pass keeps its statistics
+    // a buffer none of the live tensors occupies (the dry pass carries null pointers: slot numbers stand in for addresses)
+    int slot_of_h = -1;
+    auto pick = [&](int busy0, int busy1 = -1, int busy2 = -1) {
+        for (int j = 0; j < 4; ++j)
+            if (j != busy0 && j != busy1 && j != busy2) return j;
+        return 0;
+    };
+    // No layer asks its producer for GroupNorm records (GemmOpt::gn_rows): the epilogue that writes them folds its lanes' sums with LDS
+    // atomics in arrival order, so a record is not the same bits in two calls.  Every GroupNorm here runs the ordered statistics pass.
+    Act h;
+    h.p = z32;
+    int hh = hl, ww = wl;
+    for (const VLayer& l : n.plan) {
+        const int hw = hh * ww, M = B * hw;
+        const std::string& p = l.name;
+        Act produced;
+        int out_slot = -1;
+        if (l.kind == 0) {
+            out_slot = pick(slot_of_h);
+            GemmOpt o; o.bias = n.w(p + ".bias"); o.out = &produced;
+            conv3x3(r, h.p, B, hh, ww, pad32(l.cin), n.w(p + ".fwd"), l.cout, buf[out_slot], hh, ww, 1, 1, 0, o);
+        } else if (l.kind == 1) {
+            const int s_tmp = pick(slot_of_h), s_t2 = pick(slot_of_h, s_tmp);
+            half_t* tmp = buf[s_tmp];
+            half_t* t2 = buf[s_t2];
+            d_groupnorm(r, h, l.cin, B, hw, n.w(p + ".norm1.weight"), n.w(p + ".norm1.bias"), 1, tmp, stats);
+            Act a2;
+            { GemmOpt o; o.bias = n.w(p + ".conv1.bias"); o.out = &a2;
+              conv3x3(r, tmp, B, hh, ww, l.cin, n.w(p + ".conv1.fwd"), l.cout, t2, hh, ww, 1, 1, 0, o); }
+            d_groupnorm(r, a2, l.cout, B, hw, n.w(p + ".norm2.weight"), n.w(p + ".norm2.bias"), 1, tmp, stats);
+            const half_t* sc = h.p;
+            int s_sc = slot_of_h;
+            if (n.has(p + ".nin.w")) {
+                s_sc = pick(slot_of_h, s_tmp, s_t2);
+                GemmOpt o; o.bias = n.w(p + ".nin.b");
+                gemm(r, h.p, M, l.cin, n.w(p + ".nin.w"), l.cout, l.cin, l.cin, buf[s_sc], l.cout, o);
+                sc = buf[s_sc];
+            }
+            out_slot = pick(s_sc, s_tmp, s_sc == slot_of_h ? -1 : slot_of_h);     // conv1's output is dead once norm2 has read it
+            GemmOpt o; o.bias = n.w(p + ".conv2.bias"); o.residual = sc; o.ldr = l.cout; o.out = &produced;   // x + h (model.py:141-148)
+            conv3x3(r, tmp, B, hh, ww, l.cout, n.w(p + ".conv2.fwd"), l.cout, buf[out_slot], hh, ww, 1, 1, 0, o);
+        } else if (l.kind == 3) {          // single-head attention over the hw positions of each image, as the encoder's (vae_forward kind 3)
+            const int C = l.cin, L = hw;
+            const int s_tmp = pick(slot_of_h);
+            half_t* tmp = buf[s_tmp];
+            d_groupnorm(r, h, C, B, hw, n.w(p + ".norm.weight"), n.w(p + ".norm.bias"), 0, tmp, stats);
+            half_t* qkv[3];
+            const char* nm[3] = {".q", ".k", ".v"};
+            for (int j = 0; j < 3; ++j) {
+                qkv[j] = r.mem.halfs((size_t)M * C);
+                GemmOpt o; o.bias = n.w(p + nm[j] + ".b");
+                gemm(r, tmp, M, C, n.w(p + nm[j] + ".w"), C, C, C, qkv[j], C, o);
+            }
+            half_t* sc = r.mem.halfs((size_t)L * L);
+            half_t* P = r.mem.halfs((size_t)L * L);
+            half_t* vt = r.mem.halfs((size_t)C * L);
+            half_t* ao = r.mem.halfs((size_t)M * C);
+            for (int b = 0; b < B; ++b) {
+                const size_t ro = (size_t)b * L * C;
+                gemm(r, qkv[0] + ro, L, C, qkv[1] + ro, L, C, C, sc, L);                                // S = Q K^T
+                LEAF(asd_softmax_f16(sc, L, L, L, 1.0f / sqrtf((float)C), P, L, r.stream));
+                LEAF(asd_transpose_f16(qkv[2] + ro, L, C, C, vt, L, r.stream));
+                gemm(r, P, L, L, vt, C, L, L, ao + ro, C);                                               // O = P V
+            }
+            out_slot = pick(slot_of_h, s_tmp);
+            GemmOpt o; o.bias = n.w(p + ".proj_out.b"); o.residual = h.p; o.ldr = C; o.out = &produced;   // x + proj_out(attn)
+            gemm(r, ao, M, C, n.w(p + ".proj_out.w"), C, C, C, buf[out_slot], C, o);
+        } else if (l.kind == 5) {          // nearest-2x is the convolution's own gather mode: the upsampled tensor never exists
+            out_slot = pick(slot_of_h);
+            GemmOpt o; o.bias = n.w(p + ".bias"); o.out = &produced;
+            conv3x3(r, h.p, B, hh, ww, l.cin, n.w(p + ".fwd"), l.cout, buf[out_slot], 2 * hh, 2 * ww, 1, 1, 3, o);
+            hh *= 2; ww *= 2;
+        } else {
+            half_t* tmp = buf[pick(slot_of_h)];
+            d_groupnorm(r, h, l.cin, B, hw, n.w(p + ".norm_out.weight"), n.w(p + ".norm_out.bias"), 1, tmp, stats);
+            GemmOpt o; o.bias = n.w(p + ".conv_out.bias");
+            conv3x3(r, tmp, B, hh, ww, l.cin, n.w(p + ".conv_out.fwd"), l.cout, image32, hh, ww, 1, 1, 0, o);
+            break;
+        }
+        h = produced; h.p = buf[out_slot]; slot_of_h = out_slot;
+    }
+}
+
 int make_zero_page(Net& n) {
     if (hipMalloc(&n.zero_page, 256) != hipSuccess || hipMemset(n.zero_page, 0, 256) != hipSuccess) {
         asd_set_error("zero page allocation failed");
@@ -1112,6 +1272,60 @@ int asd_vae_enc_bwd(asd_vae_enc* h, const float* d_moments_nhwc, int32_t batch, 
        /* checked: the forward on this workspace sized both passes under the same plans and shape */
        n->gen_of[workspace] != 0 && n->gen_of[workspace] == asd_gemm_plan_generation() && n->sized.gen == n->gen_of[workspace] &&
            n->sized.batch == batch && n->sized.H == H && n->sized.W == W && n->sized.tune == tune && workspace_bytes >= n->sized.need);
+}
+
+// ---- VAE decoder -----------------------------------------------------------------------------------------------------------
+int asd_vae_dec_create(const asd_vae_desc* desc, asd_vae_dec** out) {
+    ASD_CHECK_ARG(desc && out, "null argument");
+    ASD_CHECK_ARG(desc->n_levels >= 1 && desc->n_levels <= 8 && desc->ch > 0 && desc->ch % 32 == 0 && desc->num_res_blocks >= 0 && desc->z_channels >= 1 &&
+                  desc->z_channels <= 32 && desc->in_channels >= 1 && desc->in_channels <= 32, "bad descriptor");
+    for (int i = 0; i < desc->n_levels; ++i) ASD_CHECK_ARG(desc->ch_mult[i] >= 1, "bad descriptor");
+    VaeDec* n = new VaeDec();
+    n->d = *desc;
+    vae_dec_build(*n);
+    *out = (asd_vae_dec*)n;
+    return ASD_OK;
+}
+void asd_vae_dec_destroy(asd_vae_dec* h) {
+    VaeDec* n = (VaeDec*)h;
+    if (!n) return;
+    if (n->zero_page) (void)hipFree(n->zero_page);
+    delete n;
+}
+int32_t asd_vae_dec_num_weights(const asd_vae_dec* h) { return h ? (int32_t)((const VaeDec*)h)->specs.size() : 0; }
+int asd_vae_dec_weight_info(const asd_vae_dec* h, int32_t i, asd_weight_info* info) {
+    const VaeDec* n = (const VaeDec*)h;
+    ASD_CHECK_ARG(n && info && i >= 0 && i < (int)n->specs.size(), "bad argument");
+    info->name = n->specs[i].name.c_str(); info->rows = n->specs[i].rows; info->cols = n->specs[i].cols;
+    return ASD_OK;
+}
+int asd_vae_dec_bind_weights(asd_vae_dec* h, const void* const* ptrs, int32_t count) {
+    ASD_CHECK_ARG(h && ptrs, "null argument");
+    return bind(*(VaeDec*)h, ptrs, count);
+}
+// hl, wl even and hl * wl a multiple of 8: the rows of the mid block's [hl*wl, hl*wl] score matrix are 16-byte aligned GEMM operands;
+// at most 16 images per call (asd_groupnorm_ordered_f16)
+static bool vae_dec_shape_ok(int32_t batch, int32_t hl, int32_t wl) {
+    return batch >= 1 && batch <= 16 && hl >= 2 && wl >= 2 && hl % 2 == 0 && wl % 2 == 0 && ((int64_t)hl * wl) % 8 == 0 && (int64_t)hl * wl <= 16384;
+}
+int64_t asd_vae_dec_workspace_bytes(asd_vae_dec* h, int32_t batch, int32_t hl, int32_t wl, int32_t tune) {
+    VaeDec* n = (VaeDec*)h;
+    if (!n || !vae_dec_shape_ok(batch, hl, wl)) {
+        asd_set_error("VAE decoder: 1 <= batch <= 16 and an even latent grid of at most 16384 positions, hl * wl a multiple of 8 (got %d x %d x %d)", batch, hl, wl);
+        return -(int64_t)ASD_ERR_ARG;
+    }
+    (void)tune;      // the decoder runs fixed tiles: nothing to tune, no tuning scratch
+    return (int64_t)plan_bytes([&](Run& r) { r.fixed = true; vae_dec_run(*n, r, nullptr, batch, hl, wl, nullptr); }, false);
+}
+int asd_vae_dec_fwd(asd_vae_dec* h, const void* z_nhwc32, int32_t batch, int32_t hl, int32_t wl, void* workspace, int64_t workspace_bytes,
+                    void* x_nhwc32, int32_t tune, void* stream) {
+    VaeDec* n = (VaeDec*)h;
+    ASD_CHECK_ARG(n && z_nhwc32 && workspace && x_nhwc32, "null argument");
+    ASD_CHECK_ARG(n->bound, "weights are not bound (asd_vae_dec_bind_weights)");
+    ASD_CHECK_ARG(vae_dec_shape_ok(batch, hl, wl), "VAE decoder: 1 <= batch <= 16 and an even latent grid of at most 16384 positions, hl * wl a multiple of 8");
+    (void)tune;
+    return run_pass([&](Run& r) { r.fixed = true; vae_dec_run(*n, r, (const half_t*)z_nhwc32, batch, hl, wl, (half_t*)x_nhwc32); }, workspace,
+                    (size_t)workspace_bytes, (hipStream_t)stream, false, n->zero_page);
 }
 
 }  // extern "C"

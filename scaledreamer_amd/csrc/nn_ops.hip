@@ -80,6 +80,39 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const half_t* __restrict_
     }
 }
 
+// The same statistics with nothing left to arrival order: a thread's per-channel sums go to LDS and 64 threads (group, sum | sum of
+// squares) add them up in thread order.  With a grid that depends on (hw, C) only (asd_groupnorm_ordered_f16) the partials of an image
+// — and with them every bit of its GroupNorm — do not depend on the call or on the batch the image travels in.  C <= 2048.
+__global__ __launch_bounds__(256) void gn_stats_ordered_kernel(const half_t* __restrict__ x, int C, int hw, int rows_per_block, float* __restrict__ stats) {
+    __shared__ float ts[256][17];       // [thread][8 sums | 8 sums of squares], padded against bank conflicts of the column walk
+    const int slots = C / 8, cg = C / 32;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int r0 = blockIdx.y * rows_per_block, r1 = min(hw, r0 + rows_per_block);
+    const int rows_in_flight = 256 / slots, rsub = tid / slots, slot = tid % slots;
+    const bool live = rsub < rows_in_flight;
+    float s[8], q[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { s[k] = 0.f; q[k] = 0.f; }
+    if (live) {
+        const half_t* base = x + (size_t)b * hw * C + slot * 8;
+        for (int r = r0 + rsub; r < r1; r += rows_in_flight) {
+            const half8 v = *(const half8*)(base + (size_t)r * C);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { const float f = (float)v[k]; s[k] += f; q[k] = fmaf(f, f, q[k]); }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { ts[tid][k] = s[k]; ts[tid][8 + k] = q[k]; }
+    __syncthreads();
+    if (tid < 64) {
+        const int g = tid >> 1, sq = tid & 1;
+        float acc = 0.f;
+        for (int rs = 0; rs < rows_in_flight; ++rs)
+            for (int c = g * cg; c < (g + 1) * cg; ++c) acc += ts[rs * slots + c / 8][sq * 8 + (c & 7)];
+        stats[((size_t)b * gridDim.y + blockIdx.y) * 64 + tid] = acc;
+    }
+}
+
 // sum of the statistics partials of batch element b -> st[64] (LDS); 256 threads.  Four independent loads in flight per thread:
 // the partials are the head of the kernel's dependency chain (partials -> scale/shift -> first store), and these launches are short
 // enough (5-10 us) that every serialized L2/HBM round trip shows.
@@ -714,6 +747,24 @@ int asd_groupnorm_f16(const void* x1, int32_t c1, const void* x2, int32_t c2, in
     hipLaunchKernelGGL(gn_stats_kernel, dim3(batch, chunks_s), dim3(256), 0, s, (const half_t*)x1, c1, (const half_t*)x2, c2, hw,
                        asd_div_up(hw, chunks_s), partials);
     gn_launch_apply(dim3(batch, chunks_a), s, x1, c1, x2, c2, hw, asd_div_up(hw, chunks_a), gamma, beta, eps, silu, partials, chunks_s, stats, y);
+    ASD_LAUNCH_CHECK();
+    return ASD_OK;
+}
+
+int asd_groupnorm_ordered_f16(const void* x, int32_t c, int32_t batch, int32_t hw, const void* gamma, const void* beta, float eps, int32_t silu,
+                              void* y, float* stats, void* stream) {
+    ASD_CHECK_ARG(x && gamma && beta && y && stats && batch > 0 && hw > 0, "null argument");
+    ASD_CHECK_ARG(c % 32 == 0 && c >= 32 && c <= 2048, "channels must be a multiple of 32, at most 2048");
+    ASD_CHECK_ARG(((((uintptr_t)gamma) | ((uintptr_t)beta)) & 15) == 0, "gamma / beta must be 16-byte aligned");
+    // the statistics grid depends on hw alone: an image's partials are the same numbers in every batch
+    int chunks = asd_div_up(hw, 64);
+    if (chunks > 32) chunks = 32;
+    ASD_CHECK_ARG((int64_t)batch * chunks <= 512, "ordered GroupNorm: at most 16 images per call (the partials area of ASD_GN_STATS_FLOATS)");
+    hipStream_t s = (hipStream_t)stream;
+    float* partials = stats + 64 * batch;
+    hipLaunchKernelGGL(gn_stats_ordered_kernel, dim3(batch, chunks), dim3(256), 0, s, (const half_t*)x, c, hw, asd_div_up(hw, chunks), partials);
+    const int chunks_a = gn_apply_chunks(hw, c, batch);
+    gn_launch_apply(dim3(batch, chunks_a), s, x, c, nullptr, 0, hw, asd_div_up(hw, chunks_a), gamma, beta, eps, silu, partials, chunks, stats, y);
     ASD_LAUNCH_CHECK();
     return ASD_OK;
 }

@@ -9,6 +9,8 @@ The reference reads two formats:
 Both end up as `{ldm_name: tensor}` dictionaries checked against the layout's shapes (missing / unexpected / mis-shaped keys
 raise).  Random weights are never substituted silently: `resolve_params` raises unless the caller passed
 `allow_random_weights=True` (bench, smoke and the parity tests do; no pretrained weights exist offline).
+The VAE decoder (`decoder.*`, `post_quant_conv.*`: latent-space rendering's validation images) is read on its own by
+`resolve_decoder_params`, lazily; `resolve_params` and `diffusers_vae_key_to_ldm` keep ignoring those keys.
 """
 from __future__ import annotations
 
@@ -124,6 +126,33 @@ def diffusers_vae_key_to_ldm(key: str) -> Optional[str]:
     raise KeyError(key)
 
 
+def diffusers_vae_decoder_key_to_ldm(key: str, cfg: W.VAEConfig) -> Optional[str]:
+    """AutoencoderKL name -> LDM first-stage name, decoder + post_quant_conv only (every other key returns None).  diffusers numbers the
+    up blocks in execution order, LDM by resolution level: `decoder.up_blocks.i` is `decoder.up.{n_levels - 1 - i}`."""
+    if key.startswith("post_quant_conv."):
+        return key
+    if not key.startswith("decoder."):
+        return None
+    k = key[len("decoder."):]
+    for a, b in (("conv_in.", "conv_in."), ("conv_out.", "conv_out."), ("conv_norm_out.", "norm_out.")):
+        if k.startswith(a):
+            return "decoder." + b + k[len(a):]
+    n_levels = len(cfg.ch_mult)
+    m = re.match(r"up_blocks\.(\d+)\.resnets\.(\d+)\.(.+)", k)
+    if m:
+        return f"decoder.up.{n_levels - 1 - int(m.group(1))}.block.{m.group(2)}.{m.group(3).replace('conv_shortcut', 'nin_shortcut')}"
+    m = re.match(r"up_blocks\.(\d+)\.upsamplers\.0\.conv\.(.+)", k)
+    if m:
+        return f"decoder.up.{n_levels - 1 - int(m.group(1))}.upsample.conv.{m.group(2)}"
+    m = re.match(r"mid_block\.resnets\.(\d)\.(.+)", k)
+    if m:
+        return f"decoder.mid.block_{int(m.group(1)) + 1}.{m.group(2).replace('conv_shortcut', 'nin_shortcut')}"
+    m = re.match(r"mid_block\.attentions\.0\.(.+)\.(weight|bias)", k)
+    if m and m.group(1) in _VAE_ATTN:
+        return f"decoder.mid.attn_1.{_VAE_ATTN[m.group(1)]}.{m.group(2)}"
+    raise KeyError(key)
+
+
 def _check(params: P, shapes: W.Shapes, what: str) -> P:
     missing = [k for k in shapes if k not in params]
     extra = [k for k in params if k not in shapes]
@@ -208,3 +237,51 @@ def resolve_params(cfg, unet_cfg: W.UNetConfig, vae_cfg: W.VAEConfig):
 
     warn(f"diffusion prior: {wanted!r} not found, using SEEDED RANDOM weights (seed {seed}) because allow_random_weights is set")
     return None, None, f"seeded random init (seed {seed})"
+
+
+def load_diffusers_vae_decoder(path: str, vae_cfg: W.VAEConfig) -> P:
+    """<path>/vae of a diffusers pipeline -> decoder + post_quant_conv params in LDM names"""
+    vf = _first_existing(*(os.path.join(path, "vae", f) for f in ("diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.bin")))
+    if vf is None:
+        raise MissingWeightsError(f"{path}: no vae/diffusion_pytorch_model.(safetensors|bin)")
+    dec = {}
+    for k, v in _read_state_dict(vf).items():
+        nk = diffusers_vae_decoder_key_to_ldm(k, vae_cfg)
+        if nk is not None:
+            dec[nk] = v
+    return _check(dec, W.vae_decoder_layout(vae_cfg)[0], "diffusers VAE decoder")
+
+
+def load_ldm_vae_decoder(path: str, vae_cfg: W.VAEConfig) -> P:
+    """`first_stage_model.{decoder,post_quant_conv}.*` of one LDM / MVDream checkpoint"""
+    sd = _read_state_dict(path)
+    vp = "first_stage_model."
+    shapes = W.vae_decoder_layout(vae_cfg)[0]
+    return _check({k[len(vp):]: v for k, v in sd.items() if k.startswith(vp) and k[len(vp):] in shapes}, shapes, "LDM first-stage decoder")
+
+
+def resolve_decoder_params(cfg, vae_cfg: W.VAEConfig):
+    """(decoder_params, description) for a guidance config, in the search order of `resolve_params`; `decoder_params` is None for the
+    seeded random weights, which are only allowed behind `allow_random_weights`.  Called on the first decode_latents: a training run
+    that never validates never reads the decoder's tensors."""
+    ckpt = getattr(cfg, "ckpt_path", None)
+    name = getattr(cfg, "pretrained_model_name_or_path", None)
+    if ckpt and os.path.isfile(ckpt):
+        return load_ldm_vae_decoder(ckpt, vae_cfg), f"LDM checkpoint {ckpt}"
+    if name and os.path.isdir(name):
+        return load_diffusers_vae_decoder(name, vae_cfg), f"diffusers pipeline {name}"
+    if name and os.path.isfile(name):
+        return load_ldm_vae_decoder(name, vae_cfg), f"LDM checkpoint {name}"
+    snap = hub_cache_snapshot(name) if name else None
+    if snap:
+        return load_diffusers_vae_decoder(snap, vae_cfg), f"diffusers pipeline {name} (local hub cache: {snap})"
+    wanted = ckpt or name or getattr(cfg, "model_name", None)
+    if not getattr(cfg, "allow_random_weights", False):
+        raise MissingWeightsError(
+            f"VAE decoder weights {wanted!r} are not on disk.  Point `pretrained_model_name_or_path` at a local diffusers directory / "
+            "`ckpt_path` at an LDM checkpoint, or set `allow_random_weights: true` (benchmarks and tests only — it decodes noise).")
+    seed = getattr(cfg, "weights_seed", 1)
+    from ..registry import warn
+
+    warn(f"VAE decoder: {wanted!r} not found, using SEEDED RANDOM weights (seed {seed}) because allow_random_weights is set")
+    return None, f"seeded random init (seed {seed})"

@@ -28,7 +28,7 @@ P = Dict[str, torch.Tensor]
 
 class CNet:
     """A frozen network held by the library (csrc/net.hip): created from its descriptor, bound to the packed weights its table asks
-    for.  `kind` = "unet" | "vae_enc"."""
+    for.  `kind` = "unet" | "vae_enc" | "vae_dec"."""
 
     def __init__(self, kind: str, desc, packed: P, device, dtype=torch.float16):
         self.kind, self.device = kind, torch.device(device)
@@ -176,8 +176,12 @@ class HipBackend(DiffusionBackend):
 
     def __init__(self, device, dtype=torch.float16, seed: int = 1, unet_cfg: Optional[W.UNetConfig] = None,
                  vae_cfg: Optional[W.VAEConfig] = None, unet_params: Optional[P] = None, vae_params: Optional[P] = None,
-                 use_graph: bool = True):
+                 use_graph: bool = True, decoder_params=None):
+        """decoder_params: the VAE decoder's LDM state dict, or a callable returning it (or None for seeded random weights) — it is
+        only called by the first decode, so a run that never validates never holds the decoder"""
         from .vae_hip import HipVAEEncoder
+
+        self.seed, self._decoder_params, self.hip_vae_dec = seed, decoder_params, None
 
         self.device = torch.device(device)
         self.unet_cfg = unet_cfg or W.UNetConfig()
@@ -199,6 +203,27 @@ class HipBackend(DiffusionBackend):
 
     def encode(self, images):
         return self.hip_vae(images)
+
+    def decoder(self):
+        """the VAE decoder, built (weights read, packed and uploaded) on first use"""
+        if self.hip_vae_dec is None:
+            from .vae_hip import HipVAEDecoder
+
+            dp = self._decoder_params() if callable(self._decoder_params) else self._decoder_params
+            if dp is None:
+                dp = W.gen_params(W.vae_decoder_layout(self.vae_cfg)[0], self.seed + 2)
+            self.hip_vae_dec = HipVAEDecoder(dp, self.vae_cfg, self.device)
+            self._decoder_params = None
+        return self.hip_vae_dec
+
+    @torch.no_grad()
+    def decode(self, latents):
+        """latents [B,4,hl,wl] (already divided by the scaling factor) -> images [B,3,8hl,8wl] in [-1,1]"""
+        _, raw = self.decoder()(latents.permute(0, 2, 3, 1), latents.shape[2:], return_raw=True, inv_scaling=1.0)
+        return raw.permute(0, 3, 1, 2).to(latents.dtype)
+
+    def decode_latents_bhwc(self, latents_bhwc, latent_hw):
+        return self.decoder()(latents_bhwc, latent_hw)
 
     # buffer protocol of the fused guidance: no re-layout between the ASD kernels and the networks
     def vae_forward(self, x_nhwc32):
@@ -226,7 +251,7 @@ def _backend_from_cfg(cfg, device, dtype, unet_cfg: W.UNetConfig) -> HipBackend:
     vae_cfg = W.VAEConfig()
     up, vp, what = checkpoint.resolve_params(cfg, unet_cfg, vae_cfg)
     backend = HipBackend(device, dtype, seed=getattr(cfg, "weights_seed", 1), unet_cfg=unet_cfg, vae_cfg=vae_cfg,
-                         unet_params=up, vae_params=vp)
+                         unet_params=up, vae_params=vp, decoder_params=lambda: checkpoint.resolve_decoder_params(cfg, vae_cfg)[0])
     backend.weights_source = what
     return backend
 

@@ -13,6 +13,10 @@ GroupNorm+SiLU forward/backward are the NHWC kernels of nn_ops.hip, 1x1 convolut
 GEMMs around row-softmax kernels; conv_out and quant_conv are both linear and are folded into one 3x3 convolution at pack time.
 The per-layer autograd Functions below (_Conv3x3Fn, _GroupNormFn) drive the same leaf kernels one at a time; they are kept as
 the unit-test harness of those kernels' gradients (tests/test_gpu_vae_hip.py), not used by the encoder.
+
+`HipVAEDecoder` is the decoder of the same autoencoder (Decoder model.py:546-655, post_quant_conv autoencoder.py:33,87-90), forward
+only, for the validation / test images of latent-space rendering (stable_diffusion_asd_guidance.py:180-194 decode_latents): the
+C-ABI network asd_vae_dec_fwd between the two small kernels asd_latent_decode_prep and asd_image_from_decoder.
 """
 from __future__ import annotations
 
@@ -141,3 +145,76 @@ class HipVAEEncoder:
         if not images.is_cuda:
             raise AsdError("the HIP VAE encoder needs device tensors (there is no CPU fallback)")
         return _EncodeFn.apply(images, self)
+
+
+class HipVAEDecoder:
+    """latents fp32 [B,h,w,4] (channels last, as the renderer leaves them) -> image fp32 [B,8hl,8wl,3] in [0,1]:
+         asd_latent_decode_prep   bilinear resize to latent_hw, 1 / scale_factor, post_quant_conv -> fp16 NHWC-32
+         asd_vae_dec_fwd          the decoder (csrc/net.hip: vae_dec_run)
+         asd_image_from_decoder   clamp(0.5 x + 0.5, 0, 1)
+    Batches are walked in chunks.  Chunk rule: the largest chunk, of at most 16 images, whose workspace (asd_vae_dec_workspace_bytes, four
+    activation buffers of the widest level dominate it) stays within `workspace_limit` = 2 GiB, and at least 1 — at 64x64 -> 512x512 that
+    is 3 images (0.59 GiB for one, 1.63 GiB for three); the eval pass hands up to 16 views.  The network runs GEMM tiles chosen from a
+    layer's width alone, never split, and GroupNorms whose statistics are summed in a fixed order per image, so an image's result is the
+    same bits whatever batch or chunk it is part of, and in every call."""
+
+    workspace_limit = 2 << 30
+
+    def __init__(self, params: P, cfg: Optional[W.VAEConfig] = None, device="cuda", chunk: Optional[int] = None):
+        from .engine import CNet
+
+        self.cfg = cfg or W.VAEConfig()
+        self.device = torch.device(device)
+        self.net = CNet("vae_dec", vae_desc(self.cfg), W.pack_vae_decoder(params, self.cfg), self.device)
+        self.post_quant = W.post_quant_matrix(params).to(self.device)
+        self.chunk = chunk            # forced chunk size (tests); None: the rule above
+        self.up = 2 ** (len(self.cfg.ch_mult) - 1)
+        self._chunk_of = {}
+
+    def workspace_bytes(self, B, hl, wl) -> int:
+        nb = lib().asd_vae_dec_workspace_bytes(self.net.handle, i32(B), i32(hl), i32(wl), i32(0))
+        if nb < 0:
+            raise AsdError(lib().asd_last_error().decode())
+        return nb
+
+    def chunk_for(self, B, hl, wl) -> int:
+        if self.chunk:
+            return min(B, self.chunk)
+        key = (hl, wl)
+        if key not in self._chunk_of:      # workspace_bytes grows with the batch: the first size over the limit ends the search
+            n = 1
+            while n < 16 and self.workspace_bytes(n + 1, hl, wl) <= self.workspace_limit:
+                n += 1
+            self._chunk_of[key] = n
+        return min(B, self._chunk_of[key])
+
+    @torch.no_grad()
+    def __call__(self, latents: torch.Tensor, latent_hw=(64, 64), return_raw: bool = False, inv_scaling: Optional[float] = None):
+        """return_raw: also the decoder's output before 0.5 x + 0.5 and the clamp; inv_scaling: replaces 1 / cfg.scale_factor"""
+        if not latents.is_cuda:
+            raise AsdError("the HIP VAE decoder needs device tensors (there is no CPU fallback)")
+        if latents.dim() != 4 or latents.shape[-1] != 4:
+            raise ValueError(f"latents must be [B,h,w,4] (channels last), got {tuple(latents.shape)}")
+        B, h, w, _ = latents.shape
+        hl, wl = int(latent_hw[0]), int(latent_hw[1])
+        Ho, Wo = hl * self.up, wl * self.up
+        lat = latents.detach().float().contiguous()
+        image = torch.empty((B, Ho, Wo, 3), device=lat.device, dtype=torch.float32)
+        raw = torch.empty_like(image) if return_raw else None
+        n = self.chunk_for(B, hl, wl)
+        z = torch.empty((n, hl, wl, 32), device=lat.device, dtype=torch.float16)
+        x = torch.empty((n, Ho, Wo, 32), device=lat.device, dtype=torch.float16)
+        ws, ws_for = None, None
+        for b0 in range(0, B, n):
+            nb = min(n, B - b0)
+            if ws_for != nb:
+                ws = None            # release before the next size is allocated
+                ws, ws_for = torch.empty(self.workspace_bytes(nb, hl, wl), dtype=torch.uint8, device=lat.device), nb
+            check(lib().asd_latent_decode_prep(ptr(lat[b0:b0 + nb]), i32(nb), i32(h), i32(w), i32(hl), i32(wl),
+                                               C.c_float(1.0 / self.cfg.scale_factor if inv_scaling is None else inv_scaling),
+                                               ptr(self.post_quant), ptr(z), stream()))
+            check(lib().asd_vae_dec_fwd(self.net.handle, ptr(z), i32(nb), i32(hl), i32(wl), ptr(ws), C.c_int64(ws.numel()), ptr(x), i32(0),
+                                        stream()))
+            check(lib().asd_image_from_decoder(ptr(x), C.c_int64(nb * Ho * Wo), ptr(image[b0:b0 + nb]), ptr(None if raw is None else raw[b0:b0 + nb]),
+                                               stream()))
+        return (image, raw) if return_raw else image

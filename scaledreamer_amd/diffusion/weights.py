@@ -195,6 +195,41 @@ def vae_encoder_layout(cfg: VAEConfig):
     return s, plan
 
 
+def vae_decoder_layout(cfg: VAEConfig):
+    """(shapes, plan) of post_quant_conv (models/autoencoder.py:33,87-88) + Decoder (model.py:546-655); plan = ordered (kind, prefix,
+    cin, cout) in execution order.  A level holds num_res_blocks + 1 ResnetBlocks; `up.{lvl}.upsample.conv` exists for lvl > 0."""
+    s: Shapes = {}
+    plan: List[Tuple[str, str, int, int]] = []
+    _conv(s, "post_quant_conv", cfg.embed_dim, cfg.z_channels, 1)
+    plan.append(("post_quant", "post_quant_conv", cfg.embed_dim, cfg.z_channels))
+    block_in = cfg.ch * cfg.ch_mult[-1]
+    _conv(s, "decoder.conv_in", cfg.z_channels, block_in, 3)
+    plan.append(("conv", "decoder.conv_in", cfg.z_channels, block_in))
+    _vae_res(s, "decoder.mid.block_1", block_in, block_in)
+    plan.append(("res", "decoder.mid.block_1", block_in, block_in))
+    p = "decoder.mid.attn_1"
+    _norm(s, p + ".norm", block_in)
+    for n in ("q", "k", "v", "proj_out"):
+        _conv(s, f"{p}.{n}", block_in, block_in, 1)
+    plan.append(("attn", p, block_in, block_in))
+    _vae_res(s, "decoder.mid.block_2", block_in, block_in)
+    plan.append(("res", "decoder.mid.block_2", block_in, block_in))
+    for lvl in reversed(range(len(cfg.ch_mult))):
+        block_out = cfg.ch * cfg.ch_mult[lvl]
+        for b in range(cfg.num_res_blocks + 1):
+            p = f"decoder.up.{lvl}.block.{b}"
+            _vae_res(s, p, block_in, block_out)
+            plan.append(("res", p, block_in, block_out))
+            block_in = block_out
+        if lvl != 0:
+            _conv(s, f"decoder.up.{lvl}.upsample.conv", block_in, block_in, 3)
+            plan.append(("up", f"decoder.up.{lvl}.upsample.conv", block_in, block_in))
+    _norm(s, "decoder.norm_out", block_in)
+    _conv(s, "decoder.conv_out", block_in, cfg.in_channels, 3)
+    plan.append(("out", "decoder", block_in, cfg.in_channels))
+    return s, plan
+
+
 def _vae_res(s: Shapes, p: str, cin: int, cout: int):
     _norm(s, p + ".norm1", cin)
     _conv(s, p + ".conv1", cin, cout, 3)
@@ -408,3 +443,48 @@ def pack_vae_encoder(p: Dict[str, torch.Tensor], cfg: VAEConfig) -> Dict[str, to
             conv(name + ".conv_out_quant", torch.einsum("om,mikl->oikl", wq, wc),
                  wq @ p[name + ".conv_out.bias"].float() + p["quant_conv.bias"].float())
     return out
+
+
+def pack_vae_decoder(p: Dict[str, torch.Tensor], cfg: VAEConfig) -> Dict[str, torch.Tensor]:
+    """LDM first-stage decoder state dict -> the C table of csrc/net.hip: vae_dec_build.  Forward only: no gradient matrices.  The
+    upsampling convolutions go in the parity form of _pack_upsample_conv3x3 (4/9 of the nine-tap form's multiply-adds, the form the
+    UNet's up path runs); conv_out's image channels are padded to 32 output rows (zero weights, zero bias).  post_quant_conv is NOT
+    folded into conv_in — its bias would have to leak through the 3x3's zero padding at the border — and is not part of the table:
+    `post_quant_matrix` hands it to asd_latent_decode_prep."""
+    _, plan = vae_decoder_layout(cfg)
+    out: Dict[str, torch.Tensor] = {}
+
+    def conv(name):
+        out[name + ".fwd"], out[name + ".bias"] = _pack_conv3x3(p[name + ".weight"].float()), p[name + ".bias"].float()
+
+    for kind, name, cin, cout in plan:
+        if kind == "conv":
+            conv(name)
+        elif kind == "res":
+            for n in ("norm1", "norm2"):
+                out[f"{name}.{n}.weight"], out[f"{name}.{n}.bias"] = p[f"{name}.{n}.weight"], p[f"{name}.{n}.bias"]
+            conv(name + ".conv1")
+            conv(name + ".conv2")
+            if name + ".nin_shortcut.weight" in p:
+                out[name + ".nin.w"], out[name + ".nin.b"] = p[name + ".nin_shortcut.weight"].reshape(cout, cin), p[name + ".nin_shortcut.bias"]
+        elif kind == "attn":
+            out[name + ".norm.weight"], out[name + ".norm.bias"] = p[name + ".norm.weight"], p[name + ".norm.bias"]
+            for n in ("q", "k", "v", "proj_out"):
+                out[f"{name}.{n}.w"], out[f"{name}.{n}.b"] = p[f"{name}.{n}.weight"].reshape(cout, cin), p[f"{name}.{n}.bias"]
+        elif kind == "up":
+            out[name + ".fwd"], out[name + ".bias"] = _pack_upsample_conv3x3(p[name + ".weight"].float()), p[name + ".bias"].float()
+        elif kind == "out":
+            out[name + ".norm_out.weight"], out[name + ".norm_out.bias"] = p[name + ".norm_out.weight"], p[name + ".norm_out.bias"]
+            w, b = p[name + ".conv_out.weight"].float(), p[name + ".conv_out.bias"].float()
+            cp = (cout + 31) // 32 * 32
+            out[name + ".conv_out.fwd"] = _pack_conv3x3(torch.cat([w, w.new_zeros(cp - cout, *w.shape[1:])], 0))
+            out[name + ".conv_out.bias"] = torch.cat([b, b.new_zeros(cp - cout)])
+    return out
+
+
+def post_quant_matrix(p: Dict[str, torch.Tensor]) -> torch.Tensor:
+    """fp32 [20]: post_quant_conv's W[4][4] (out, in) then bias[4] — the argument of asd_latent_decode_prep"""
+    w, b = p["post_quant_conv.weight"].float(), p["post_quant_conv.bias"].float()
+    if w.shape[0] != 4 or w.reshape(4, -1).shape[1] != 4:
+        raise ValueError(f"post_quant_conv is {tuple(w.shape)}: the latent kernels are built for 4 latent channels")
+    return torch.cat([w.reshape(16), b.reshape(4)]).contiguous()

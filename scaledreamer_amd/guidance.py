@@ -112,10 +112,12 @@ class DiffusionBackend:
     (include/asd_hip.h: NHWC fp16 padded to 32 channels in, fp32 NHWC out), so that the fused ASD kernels write the UNet's input
     in place and nothing is re-laid-out between them and the networks:
         vae_forward(x_nhwc32) -> (moments_nhwc fp32, saved)      vae_backward(saved, d_moments_nhwc) -> dx_nhwc32
+        decode_latents_bhwc(latents_bhwc fp32, (hl, wl)) -> image_bhwc fp32 in [0,1]
         unet_buffers(N, hl, wl, n_ctx, frames[, shared_reps]) -> UNetIO          unet_run(io) -> io.eps
     The product implementation is scaledreamer_amd.diffusion.engine.HipBackend (C-ABI networks).  Subclasses that only define
-    `unet(latents, t, context[, camera, num_frames]) -> eps` and `encode(images[B,3,H,W] in [-1,1]) -> moments[B,8,H/8,W/8]`
-    (differentiable w.r.t. the images) get the buffer protocol from the adaptors below: the stand-ins of the parity tests and the
+    `unet(latents, t, context[, camera, num_frames]) -> eps`, `encode(images[B,3,H,W] in [-1,1]) -> moments[B,8,H/8,W/8]`
+    (differentiable w.r.t. the images) and, for latent-space rendering's validation images, `decode(latents[B,4,hl,wl]) ->
+    images[B,3,8hl,8wl] in [-1,1]` get the buffer protocol from the adaptors below: the stand-ins of the parity tests and the
     library-op A/B tool (tools/eager_backend.py) use that."""
     scaling_factor: float = 0.18215
     context_dim: int = 1024
@@ -128,7 +130,20 @@ class DiffusionBackend:
     def encode(self, images: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError
 
-    # ---- buffer protocol on top of unet() / encode() ---------------------------------------------------------------------------
+    def decode(self, latents: torch.Tensor) -> torch.Tensor:
+        """latents [B,4,hl,wl] (divided by the scaling factor) -> images [B,3,8hl,8wl] in [-1,1]: vae.decode of decode_latents (:191)"""
+        raise NotImplementedError
+
+    # ---- buffer protocol on top of unet() / encode() / decode() ----------------------------------------------------------------
+    def decode_latents_bhwc(self, latents_bhwc: torch.Tensor, latent_hw) -> torch.Tensor:
+        """rendered latents fp32 [B,h,w,4] -> image fp32 [B,8hl,8wl,3] in [0,1] (decode_latents :180-194, channels last on both sides)"""
+        import torch.nn.functional as F
+
+        z = F.interpolate(latents_bhwc.permute(0, 3, 1, 2).float(), tuple(latent_hw), mode="bilinear", align_corners=False)
+        with torch.no_grad():
+            img = self.decode(z * (1.0 / self.scaling_factor))
+        return (img.float() * 0.5 + 0.5).clamp(0, 1).permute(0, 2, 3, 1).contiguous()
+
     def vae_forward(self, x_nhwc32: torch.Tensor):
         img = x_nhwc32[..., :3].permute(0, 3, 1, 2).float().detach().requires_grad_(True)
         with torch.enable_grad():
@@ -198,6 +213,8 @@ class _ScoreDistillation(torch.autograd.Function):
          forward : image_prep -> VAE encoder -> latents (+ both noisings, written into the UNet's input) -> UNet -> score (CFG /
                    Perp-Neg / w(t) / nan_to_num / loss)
          backward: latents_bwd -> VAE encoder input gradient -> image_prep adjoint
+       Latent mode (job["latent_mode"], rgb_as_latents: the render carries the 4 latent channels) has no VAE in it:
+         forward : latent_input (resize + both noisings) -> UNet -> score          backward: latent_input adjoint
        The loss is 0.5 * ||z - sg(z - g)||^2 / B, i.e. its value is 0.5 ||g||^2 / B and d loss / d z = g / B: g is computed once in
        the forward pass and only rescaled here."""
 
@@ -212,9 +229,11 @@ class _ScoreDistillation(torch.autograd.Function):
         C_ = 4
         dev = rgb.device
         rgb32 = rgb.detach().contiguous().float()
-        x = torch.empty((B, H, H, 32), device=dev, dtype=torch.float16)
-        check(l.asd_image_prep_fwd(ptr(rgb32), i32(B), i32(h), i32(w), i32(H), i32(H), ptr(x), stream()))
-        moments, saved = backend.vae_forward(x)
+        latent_mode = bool(job.get("latent_mode"))
+        if not latent_mode:
+            x = torch.empty((B, H, H, 32), device=dev, dtype=torch.float16)
+            check(l.asd_image_prep_fwd(ptr(rgb32), i32(B), i32(h), i32(w), i32(H), i32(H), ptr(x), stream()))
+            moments, saved = backend.vae_forward(x)
         n_rep, n_neg = job["n_rep"], job["n_neg"]
         # the first n_rep * B entries repeat the same noised latents / timesteps / cameras under different prompts (asd_latents_fwd below)
         io = backend.unet_buffers((n_rep + 1) * B, hl, hl, job["n_ctx"], job["frames"], shared_reps=n_rep)
@@ -227,15 +246,23 @@ class _ScoreDistillation(torch.autograd.Function):
             io.camera.copy_(job["camera"])
         latents = torch.empty((B, C_, hl, hl), device=dev, dtype=torch.float32)
         alphas = job["alphas"]
-        check(l.asd_latents_fwd(ptr(moments), ptr(job["post_noise"]), ptr(job["noise"]), ptr(job["t"]), ptr(job["t_plus"]), ptr(alphas), i32(B), i32(C_),
-                                i32(hl), i32(hl), f32(backend.scaling_factor), i32(n_rep), ptr(latents), ptr(io.x), ptr(io.t), stream()))
+        if latent_mode:      # the resized render is the latents: no VAE call, no VAE workspace
+            check(l.asd_latent_input_fwd(ptr(rgb32), ptr(job["noise"]), ptr(job["t"]), ptr(job["t_plus"]), ptr(alphas), i32(B), i32(h), i32(w), i32(hl),
+                                         i32(hl), i32(n_rep), ptr(latents), ptr(io.x), ptr(io.t), stream()))
+        else:
+            check(l.asd_latents_fwd(ptr(moments), ptr(job["post_noise"]), ptr(job["noise"]), ptr(job["t"]), ptr(job["t_plus"]), ptr(alphas), i32(B), i32(C_),
+                                    i32(hl), i32(hl), f32(backend.scaling_factor), i32(n_rep), ptr(latents), ptr(io.x), ptr(io.t), stream()))
         eps = backend.unet_run(io)
         grad = torch.empty_like(latents)
         scratch = torch.empty(B + 2, device=dev, dtype=torch.float32)
         check(l.asd_score_fwd(ptr(eps), i32(B), i32(C_), i32(hl * hl), i32(n_neg), ptr(neg_w), f32(job["guidance_scale"]), ptr(job["t"]), ptr(alphas),
                               i32(job["weighting"]), f32(job["grad_clip"] or 0.0), ptr(grad), ptr(scratch), ptr(scratch[B:]), stream()))
-        ctx.backend, ctx.saved_vae, ctx.dims, ctx.in_dtype = backend, saved, (B, h, w, H, hl, C_), rgb.dtype
-        ctx.save_for_backward(grad, moments, job["post_noise"])
+        ctx.latent_mode, ctx.dims, ctx.in_dtype = latent_mode, (B, h, w, H, hl, C_), rgb.dtype
+        if latent_mode:
+            ctx.save_for_backward(grad)
+        else:
+            ctx.backend, ctx.saved_vae = backend, saved
+            ctx.save_for_backward(grad, moments, job["post_noise"])
         loss, norm = scratch[B], scratch[B + 1]
         ctx.mark_non_differentiable(norm)
         return loss, norm
@@ -245,10 +272,15 @@ class _ScoreDistillation(torch.autograd.Function):
         from ._lib import check, f32, i32, lib, ptr, stream
 
         l = lib()
-        grad, moments, post_noise = ctx.saved_tensors
         B, h, w, H, hl, C_ = ctx.dims
-        d_m = torch.empty_like(moments)
         up = d_loss.detach().reshape(1).float().contiguous()
+        if ctx.latent_mode:
+            (grad,) = ctx.saved_tensors
+            d_render = torch.empty((B, h, w, 4), device=grad.device, dtype=torch.float32)
+            check(l.asd_latent_input_bwd(ptr(grad), ptr(up), i32(B), i32(h), i32(w), i32(hl), i32(hl), ptr(d_render), stream()))
+            return d_render.to(ctx.in_dtype), None, None
+        grad, moments, post_noise = ctx.saved_tensors
+        d_m = torch.empty_like(moments)
         check(l.asd_latents_bwd(ptr(grad), ptr(moments), ptr(post_noise), ptr(up), i32(B), i32(C_), i32(hl), i32(hl), f32(ctx.backend.scaling_factor),
                                 ptr(d_m), stream()))
         dx = ctx.backend.vae_backward(ctx.saved_vae, d_m)
@@ -310,9 +342,15 @@ class _AsdGuidanceBase(BaseObject):
             room = room * self.rand_fn(t.shape, t.device)
         return (t + room.to(torch.long)).clamp(1, T - 1)
 
+    @staticmethod
+    def _check_channels(rgb: torch.Tensor, rgb_as_latents: bool) -> None:
+        if rgb_as_latents and (rgb.dim() != 4 or rgb.shape[-1] != 4):
+            raise ValueError(f"rgb_as_latents=True needs a render of 4 latent channels [B,h,w,4]; got {rgb.shape[-1]} channels "
+                             f"(shape {tuple(rgb.shape)})")
+
     def _distill(self, rgb: torch.Tensor, context: Optional[torch.Tensor], neg_w: Optional[torch.Tensor], n_rep: int, shared_t: bool,
                  camera: Optional[torch.Tensor] = None, frames: int = 1, context_fill=None, n_ctx: Optional[int] = None,
-                 n_neg: Optional[int] = None) -> Dict[str, Any]:
+                 n_neg: Optional[int] = None, rgb_as_latents: bool = False) -> Dict[str, Any]:
         """context [ (n_rep + 1) * B, n_ctx, D ] + neg_w [B, n_neg], or context_fill(io) -> neg_w which writes io.context itself"""
         if not rgb.is_cuda:
             from ._lib import AsdError
@@ -320,7 +358,8 @@ class _AsdGuidanceBase(BaseObject):
             raise AsdError("the ASD guidance runs on the HIP path only (device tensors; there is no CPU fallback)")
         B, dev, hl = rgb.shape[0], rgb.device, self.image_size // 8
         like = torch.empty((B, 4, hl, hl), device=dev, dtype=torch.float32)
-        post_noise = self.posterior_noise_fn(like).float().contiguous()        # VAE posterior sample
+        # latent mode has no posterior to sample: the reference draws only `noise` there, and the draw order is the contract
+        post_noise = None if rgb_as_latents else self.posterior_noise_fn(like).float().contiguous()        # VAE posterior sample
         noise = self.noise_fn(like).float().contiguous()                        # shared by both timesteps
         t = self.timestep_fn(self.min_step, self.max_step + 1, 1 if shared_t else B, dev).to(dev)
         t_plus = self.get_t_plus(t)
@@ -328,7 +367,7 @@ class _AsdGuidanceBase(BaseObject):
             t, t_plus = t.repeat(B), t_plus.repeat(B)
         if n_neg is None:
             n_neg = 0 if neg_w is None else neg_w.shape[1]
-        job = dict(image_size=self.image_size, n_rep=n_rep, n_neg=n_neg, frames=frames, context_fill=context_fill,
+        job = dict(image_size=self.image_size, n_rep=n_rep, n_neg=n_neg, frames=frames, context_fill=context_fill, latent_mode=rgb_as_latents,
                    n_ctx=context.shape[1] if n_ctx is None else n_ctx, context=context, camera=camera, post_noise=post_noise, noise=noise, t=t.contiguous(), t_plus=t_plus.contiguous(),
                    alphas=self.alphas.to(dev), neg_w=None if neg_w is None else neg_w.float().contiguous(),
                    guidance_scale=float(self.cfg.guidance_scale), weighting=WEIGHTING[self.cfg.weighting_strategy], grad_clip=self.grad_clip_val)
@@ -393,15 +432,24 @@ class SDTimestepShiftedScoreDistillationGuidance(_AsdGuidanceBase):
 
     def __call__(self, rgb: torch.Tensor, prompt_utils, elevation, azimuth, camera_distances, rgb_as_latents=False,
                  guidance_eval=False, **kwargs) -> Dict[str, Any]:
-        if rgb_as_latents:
-            raise NotImplementedError("rgb_as_latents=True (latent-space rendering) is not on the ASD hot path of any shipped config")
+        self._check_channels(rgb, rgb_as_latents)
         fill = self._device_conditioning(prompt_utils, elevation, azimuth, rgb) if rgb.is_cuda else None
         if fill is not None:
             return self._distill(rgb, None, None, 4 if self.use_perp_neg else 2, shared_t=False, context_fill=fill,
-                                 n_ctx=prompt_utils.text_embeddings_vd.shape[1], n_neg=2 if self.use_perp_neg else 0)
+                                 n_ctx=prompt_utils.text_embeddings_vd.shape[1], n_neg=2 if self.use_perp_neg else 0, rgb_as_latents=rgb_as_latents)
         context, neg_w = self.conditioning(prompt_utils, elevation, azimuth, camera_distances)
         n_rep = context.shape[0] // rgb.shape[0] - 1
-        return self._distill(rgb, context.to(rgb.device), None if neg_w is None else neg_w.to(rgb.device), n_rep, shared_t=False)
+        return self._distill(rgb, context.to(rgb.device), None if neg_w is None else neg_w.to(rgb.device), n_rep, shared_t=False,
+                             rgb_as_latents=rgb_as_latents)
+
+    def decode_latents(self, latents: torch.Tensor, latent_height: int = 64, latent_width: int = 64) -> torch.Tensor:
+        """stable_diffusion_asd_guidance.py:180-194: latents [B,4,H,W] -> bilinear resize to (latent_height, latent_width), 1 / scaling
+        factor, VAE decoder, clamp(0.5 x + 0.5, 0, 1) -> [B,3,8 latent_height,8 latent_width] in the input's dtype."""
+        if latents.dim() != 4 or latents.shape[1] != 4:
+            raise ValueError(f"decode_latents needs latents [B,4,H,W]; got {latents.shape[1] if latents.dim() == 4 else '?'} channels "
+                             f"(shape {tuple(latents.shape)})")
+        img = self.backend.decode_latents_bhwc(latents.detach().permute(0, 2, 3, 1).float().contiguous(), (latent_height, latent_width))
+        return img.permute(0, 3, 1, 2).to(latents.dtype)
 
     def _device_conditioning(self, prompt_utils, elevation, azimuth, rgb):
         """`conditioning` as one kernel launch that writes the UNet's context buffer (csrc/asd_glue.hip: asd_prompt_context) — for the
@@ -499,8 +547,9 @@ class MVDreamTimestepShiftedScoreDistillationGuidance(_AsdGuidanceBase):
 
     def __call__(self, rgb: torch.Tensor, prompt_utils, elevation, azimuth, camera_distances, c2w, rgb_as_latents: bool = False,
                  fovy=None, input_is_latent=False, **kwargs) -> Dict[str, Any]:
-        if rgb_as_latents or input_is_latent:
-            raise NotImplementedError("latent-space inputs are not on the ASD hot path of any shipped config")
+        if input_is_latent:       # (the reference declares the argument and never reads it, mvdream_asd_guidance.py:177)
+            raise NotImplementedError("input_is_latent is not implemented; latent-space rendering is rgb_as_latents=True")
+        self._check_channels(rgb, rgb_as_latents)
         if c2w is None:
             raise NotImplementedError("the multi-view prior is camera-conditioned: c2w is required")
         B = rgb.shape[0]
@@ -509,4 +558,4 @@ class MVDreamTimestepShiftedScoreDistillationGuidance(_AsdGuidanceBase):
         cond, uncond = emb[:half].repeat(B // half, 1, 1), emb[half:].repeat(B // half, 1, 1)
         context = torch.cat([cond, uncond, cond], dim=0).to(rgb.device)
         camera = self.get_camera_cond(c2w, fovy).repeat(3, 1).to(rgb.device)
-        return self._distill(rgb, context, None, n_rep=2, shared_t=True, camera=camera, frames=self.cfg.n_view)
+        return self._distill(rgb, context, None, n_rep=2, shared_t=True, camera=camera, frames=self.cfg.n_view, rgb_as_latents=rgb_as_latents)

@@ -359,8 +359,18 @@ class MultipromptRadienceFieldGeneratorSystem(StableDreamer):
         else:
             batch["text_embed"] = self.prompt_utils.get_global_text_embeddings()
         if self.cfg.stage == "geometry":
-            return {**self.renderer(**batch, render_rgb=False)}
-        return {**self.renderer(**batch)}
+            out = {**self.renderer(**batch, render_rgb=False)}
+        else:
+            out = {**self.renderer(**batch)}
+        if self.cfg.rgb_as_latents and not self.training:      # the rendered latents as an image, in validation and test only (:109-121)
+            if "comp_rgb" not in out:
+                raise ValueError("comp_rgb is required for rgb_as_latents, no comp_rgb is found in the output.")
+            decode = getattr(self.guidance, "decode_latents", None)
+            if decode is None:       # no guidance configured, or the MVDream guidance (the reference's has no decode_latents either)
+                raise NotImplementedError("rgb_as_latents: the image grid shows decoded_rgb, which needs the guidance's decode_latents "
+                                          f"(the VAE decoder); {type(self.guidance).__name__} has none")
+            out["decoded_rgb"] = decode(out["comp_rgb"].permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
+        return out
 
     GEOMETRY_PASS_WEIGHT = 0.2       # multiprompt_radience_field_generator.py:203
 
@@ -382,19 +392,24 @@ class MultipromptRadienceFieldGeneratorSystem(StableDreamer):
         K = self.EVAL_VIEWS_PER_CALL
         if V <= K:
             out = self(dict(batch))
-            return {k: out[k] for k in self.EVAL_PANEL_KEYS if k in out}
+            return {k: out[k] for k in self._panel_keys() if k in out}
         per_view = [k for k, v in batch.items() if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == V and k not in ("noise", "ratio")]
         parts = []
         for v0 in range(0, V, K):
             out = self({k: (v[v0:v0 + K] if k in per_view else v) for k, v in batch.items()})
-            parts.append({k: out[k] for k in self.EVAL_PANEL_KEYS if k in out})
+            parts.append({k: out[k] for k in self._panel_keys() if k in out})
         return {k: torch.cat([p[k] for p in parts], dim=0) for k in parts[0]}
 
-    def _eval_step(self, batch, stem: str):
+    def _panel_keys(self):
+        """with rgb_as_latents the grid's first column is the decoded image; the 4-channel render itself is not a panel (:243,337)"""
         if self.cfg.rgb_as_latents:
-            raise NotImplementedError("rgb_as_latents: the image grid shows decoded_rgb, which needs the guidance's decode_latents "
-                                      "(the VAE decoder); this port has the encoder only")
+            return tuple("decoded_rgb" if k == "comp_rgb" else k for k in self.EVAL_PANEL_KEYS)
+        return self.EVAL_PANEL_KEYS
+
+    def _eval_step(self, batch, stem: str):
         out = self._eval_outputs(batch)
+        if self.cfg.rgb_as_latents and "decoded_rgb" in out:
+            out = {("comp_rgb" if k == "decoded_rgb" else k): v for k, v in out.items()}      # _grid_columns' first column
         grids = compose(panels_of(self._grid_columns(out, select=lambda t: t), batched=True))        # one launch for all views
         name = self._eval_name(batch)
         for b in range(grids.shape[0]):
