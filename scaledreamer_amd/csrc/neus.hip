@@ -6,33 +6,13 @@
 //   asd_neus_composite_bwd  its gradient w.r.t. sdf, normal, features, background and the variance                     (one wave per ray + one tiny reduce)
 // Roofline: bandwidth-trivial (4 096 rays x ~100 kept samples x ~60 B); what these kernels buy is launches — the composed route forms alpha
 // with about fifteen elementwise launches per pass, each way.  Per sample two exponentials, one expm1 and four IEEE divisions (neus_cdfs).
-// The learned variance is read on the device from the raw parameter p: a = clamp(exp(10 p), 1e-6, 1e6) (LearnedVariance.forward, :26-37),
-// for VolSDF clamped to [0, 80] on top (volsdf_density, :19-23).
+// Shared with render.hip and volsdf.hip, in ray_composite.h: the learned variance read on the device and the VolSDF density, the colour
+// read, the transmittance step, the per-ray images and the common part of their gradients.  This file keeps the logistic-cdf model, its
+// backward recurrence, and the variance-gradient reduce both SDF renderers launch.
 #include "asd_common.h"
+#include "ray_composite.h"
 
 #define NEUS_RAYS_PER_BLOCK 4     // 256 threads = 4 waves = 4 rays
-
-struct neus_var {
-    float a;        // the clamped inverse standard deviation
-    float dadp;     // d a / d p: 10 exp(10 p) where no clamp is active (torch.clamp passes the gradient on the closed interval), else 0
-};
-
-__device__ __forceinline__ neus_var neus_variance(const float* __restrict__ p, int use_volsdf) {
-    const float raw = expf(p[0] * 10.0f);
-    const float a1 = fminf(fmaxf(raw, 1.0e-6f), 1.0e6f);
-    neus_var v;
-    v.a = use_volsdf ? fminf(fmaxf(a1, 0.f), 80.f) : a1;
-    v.dadp = (raw >= 1.0e-6f && raw <= (use_volsdf ? 80.f : 1.0e6f)) ? 10.0f * raw : 0.f;
-    return v;
-}
-
-// sigma = a (0.5 + 0.5 sign(s) expm1(-|s| / beta)), beta = 1 / a, in the reference's operation order (as volsdf.hip)
-__device__ __forceinline__ float neus_volsdf_sigma(float s, float a, float& sg, float& em1) {
-    const float beta = 1.f / a;
-    sg = s > 0.f ? 1.f : (s < 0.f ? -1.f : 0.f);
-    em1 = expm1f(-fabsf(s) / beta);
-    return a * (0.5f + 0.5f * sg * em1);
-}
 
 // The two logistic cdf values prev = sigmoid(xp), next = sigmoid(xn) with what the opacity and its derivatives need of them.  `delta` is
 // xp - xn formed WITHOUT the subtraction (step a, or -iter_cos dt a).  The opacity lives on D = prev - next, the difference of two numbers
@@ -64,7 +44,7 @@ __device__ __forceinline__ float neus_ratio(const neus_cdf& c) { return (c.D + 1
 __device__ __forceinline__ float neus_step_alpha_of(float s, float a, float step, int use_volsdf) {
     if (use_volsdf) {
         float sg, em1;
-        return step * neus_volsdf_sigma(s, a, sg, em1);
+        return step * volsdf_sigma(s, a, sg, em1);
     }
     const float q = neus_ratio(neus_cdfs((s + step * 0.5f) * a, (s - step * 0.5f) * a, step * a));
     return fminf(fmaxf(q, 0.f), 1.f);
@@ -75,18 +55,13 @@ __device__ __forceinline__ float neus_iter_cos(float c, float k) {
     return -(fmaxf(-c * 0.5f + 0.5f, 0.f) * (1.0f - k) + fmaxf(-c, 0.f) * k);
 }
 
-__device__ __forceinline__ float neus_colour(const float* __restrict__ f, size_t i, int k, int act) {
-    const float v = f[3 * i + k];
-    return act == 1 ? 1.f / (1.f + expf(-v)) : v;
-}
-
 // alpha of sample i as the compositing pass forms it (get_alpha)
 __device__ __forceinline__ float neus_sample_alpha(const float* __restrict__ sdf, const float* __restrict__ normal, const float* __restrict__ dirs,
                                                    size_t i, float dt, float a, float k, int use_volsdf) {
     const float s = sdf[i];
     if (use_volsdf) {
         float sg, em1;
-        return fabsf(dt) * neus_volsdf_sigma(s, a, sg, em1);
+        return fabsf(dt) * volsdf_sigma(s, a, sg, em1);
     }
     const float c = dirs[3 * i] * normal[3 * i] + dirs[3 * i + 1] * normal[3 * i + 1] + dirs[3 * i + 2] * normal[3 * i + 2];
     const float ic = neus_iter_cos(c, k);
@@ -99,7 +74,7 @@ __device__ __forceinline__ float neus_sample_alpha(const float* __restrict__ sdf
 __global__ __launch_bounds__(256) void neus_step_alpha_kernel(const float* __restrict__ sdf, int n, const int* __restrict__ n_dev,
                                                               const float* __restrict__ p, float step, int use_volsdf, float* __restrict__ alpha) {
     const int live = n_dev ? min(n_dev[0], n) : n;
-    const neus_var v = neus_variance(p, use_volsdf);
+    const sdf_var v = sdf_variance(p, use_volsdf);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < live; i += (long long)gridDim.x * 256)
         alpha[i] = neus_step_alpha_of(sdf[i], v.a, step, use_volsdf);
 }
@@ -112,21 +87,17 @@ __global__ __launch_bounds__(256) void neus_prune_kernel(const float* __restrict
     if (r >= n_rays) return;
     const int lane = asd_lane();
     const int b = offset[r], cnt = count[r];
-    const neus_var v = neus_variance(p, use_volsdf);
+    const sdf_var v = sdf_variance(p, use_volsdf);
     float carry = 1.f;
     int kept = 0;
     for (int j0 = 0; j0 < cnt; j0 += 64) {
         const int j = j0 + lane;
         const bool valid = j < cnt;
         const float alpha = valid ? neus_step_alpha_of(sdf[(size_t)b + j], v.a, step, use_volsdf) : 0.f;
-        const float incl = asd_wave_incl_prod(1.f - alpha);
-        float excl = __shfl_up(incl, 1, 64);
-        if (lane == 0) excl = 1.f;
-        const float T = carry * excl;
+        const float T = ray_trans_step(alpha, carry);
         const bool k = valid && (T >= early_stop_eps) && (alpha >= alpha_thre);
         if (valid) keep[(size_t)b + j] = (uint8_t)k;
         kept += __popcll(__ballot(k));
-        carry *= __shfl(incl, 63, 64);
     }
     if (lane == 0) kept_count[r] = kept;
 }
@@ -143,9 +114,10 @@ __global__ __launch_bounds__(256) void neus_composite_fwd_kernel(
     const int lane = asd_lane();
     const int cnt = count[r];
     const size_t b = (size_t)offset[r];
-    const neus_var v = neus_variance(p, use_volsdf);
+    const sdf_var v = sdf_variance(p, use_volsdf);
     float carry = 1.f;
-    float op = 0.f, dp = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f, n0 = 0.f, n1 = 0.f, n2 = 0.f;
+    ray_images img;
+    ray_normal nrm;
     for (int j0 = 0; j0 < cnt; j0 += 64) {
         const int j = j0 + lane;
         const bool valid = j < cnt;
@@ -156,43 +128,19 @@ __global__ __launch_bounds__(256) void neus_composite_fwd_kernel(
             alpha = neus_sample_alpha(sdf, normal, dirs, i, t1 - t0, v.a, k_anneal, use_volsdf);
             tm = (t0 + t1) / 2.0f;
         }
-        const float incl = asd_wave_incl_prod(1.f - alpha);
-        float excl = __shfl_up(incl, 1, 64);      // exclusive product: the inclusive scan shifted by one lane
-        if (lane == 0) excl = 1.f;
-        const float T = carry * excl;
-        carry *= __shfl(incl, 63, 64);
+        const float T = ray_trans_step(alpha, carry);
         if (valid) {
             const float w = T * alpha;
             weights[i] = w;
-            op += w;
-            dp = fmaf(w, tm, dp);
-            c0 = fmaf(w, neus_colour(feat, i, 0, color_act), c0);
-            c1 = fmaf(w, neus_colour(feat, i, 1, color_act), c1);
-            c2 = fmaf(w, neus_colour(feat, i, 2, color_act), c2);
-            if (comp_normal) {
-                n0 = fmaf(w, normal[3 * i], n0);
-                n1 = fmaf(w, normal[3 * i + 1], n1);
-                n2 = fmaf(w, normal[3 * i + 2], n2);
-            }
+            img.add(w, tm, feat, i, color_act);
+            if (comp_normal) nrm.add(w, normal, i);
         }
     }
-    op = asd_wave_sum(op); dp = asd_wave_sum(dp);
-    c0 = asd_wave_sum(c0); c1 = asd_wave_sum(c1); c2 = asd_wave_sum(c2);
-    if (comp_normal) { n0 = asd_wave_sum(n0); n1 = asd_wave_sum(n1); n2 = asd_wave_sum(n2); }
+    img.reduce();
+    if (comp_normal) nrm.reduce();
     if (lane == 0) {
-        opacity[r] = op;
-        depth[r] = dp;
-        rgb_fg[3 * (size_t)r] = c0; rgb_fg[3 * (size_t)r + 1] = c1; rgb_fg[3 * (size_t)r + 2] = c2;
-        const float k = 1.0f - op;
-        comp_rgb[3 * (size_t)r] = c0 + bg[3 * (size_t)r] * k;
-        comp_rgb[3 * (size_t)r + 1] = c1 + bg[3 * (size_t)r + 1] * k;
-        comp_rgb[3 * (size_t)r + 2] = c2 + bg[3 * (size_t)r + 2] * k;
-        if (comp_normal) {      // (F.normalize(sum_i w_i n_i) + 1) / 2 * opacity (:337-344)
-            const float len = fmaxf(sqrtf(n0 * n0 + n1 * n1 + n2 * n2), 1e-12f);
-            comp_normal[3 * (size_t)r] = (n0 / len + 1.0f) / 2.0f * op;
-            comp_normal[3 * (size_t)r + 1] = (n1 / len + 1.0f) / 2.0f * op;
-            comp_normal[3 * (size_t)r + 2] = (n2 / len + 1.0f) / 2.0f * op;
-        }
+        img.store(r, bg, opacity, depth, rgb_fg, comp_rgb);
+        if (comp_normal) nrm.store(r, img.op, comp_normal);
     }
 }
 
@@ -233,24 +181,9 @@ __global__ __launch_bounds__(256) void neus_composite_bwd_kernel(
     const int lane = asd_lane();
     const int cnt = count[r];
     const size_t b = (size_t)offset[r];
-    const neus_var v = neus_variance(p, use_volsdf);
-    const float op = opacity[r];
-    float G[3], gop = d_opacity ? d_opacity[r] : 0.f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float gc = d_comp_rgb ? d_comp_rgb[3 * (size_t)r + k] : 0.f;
-        G[k] = gc + (d_rgb_fg ? d_rgb_fg[3 * (size_t)r + k] : 0.f);
-        gop -= gc * bg[3 * (size_t)r + k];
-        if (d_bg && lane == 0) d_bg[3 * (size_t)r + k] = gc * (1.0f - op);
-    }
-    const float gdp = d_depth ? d_depth[r] : 0.f;
-    auto gw_of = [&](size_t i, float tm, const float (&col)[3]) {
-        float gw = gop + gdp * tm + (d_weights ? d_weights[i] : 0.f);
-        gw = fmaf(G[0], col[0], gw);
-        gw = fmaf(G[1], col[1], gw);
-        gw = fmaf(G[2], col[2], gw);
-        return gw;
-    };
+    const sdf_var v = sdf_variance(p, use_volsdf);
+    ray_grads g;
+    g.load(r, d_comp_rgb, d_rgb_fg, d_opacity, d_depth, bg, opacity[r], d_bg);
     // pass 1, far to near: R_i
     float carry_r = 0.f;
     for (int j0 = cnt > 0 ? ((cnt - 1) / 64) * 64 : -1; j0 >= 0; j0 -= 64) {
@@ -260,10 +193,10 @@ __global__ __launch_bounds__(256) void neus_composite_bwd_kernel(
         float m = 1.f, c = 0.f;     // the identity map behind the end of the ray
         if (valid) {
             const float t0 = t_start[i], t1 = t_end[i];
-            const float col[3] = {neus_colour(feat, i, 0, color_act), neus_colour(feat, i, 1, color_act), neus_colour(feat, i, 2, color_act)};
+            const float col[3] = {ray_colour(feat, i, 0, color_act), ray_colour(feat, i, 1, color_act), ray_colour(feat, i, 2, color_act)};
             const float alpha = neus_sample_alpha(sdf, normal, dirs, i, t1 - t0, v.a, k_anneal, use_volsdf);
             m = 1.f - alpha;
-            c = gw_of(i, (t0 + t1) / 2.0f, col) * alpha;
+            c = g.gw(i, (t0 + t1) / 2.0f, col, d_weights) * alpha;
         }
         neus_wave_suffix_affine(m, c);
         float m_behind = __shfl_down(m, 1, 64), c_behind = __shfl_down(c, 1, 64);     // the lanes behind this one
@@ -286,7 +219,7 @@ __global__ __launch_bounds__(256) void neus_composite_bwd_kernel(
             dt = t1 - t0;
             s = sdf[i];
             if (use_volsdf) {
-                alpha = fabsf(dt) * neus_volsdf_sigma(s, v.a, sg, em1);
+                alpha = fabsf(dt) * volsdf_sigma(s, v.a, sg, em1);
             } else {
                 cosv = dirs[3 * i] * normal[3 * i] + dirs[3 * i + 1] * normal[3 * i + 1] + dirs[3 * i + 2] * normal[3 * i + 2];
                 const float ic = neus_iter_cos(cosv, k_anneal);
@@ -298,14 +231,10 @@ __global__ __launch_bounds__(256) void neus_composite_bwd_kernel(
             w = weights[i];
             R = d_sdf[i];
 #pragma unroll
-            for (int k = 0; k < 3; ++k) col[k] = neus_colour(feat, i, k, color_act);
-            gw = gw_of(i, (t0 + t1) / 2.0f, col);
+            for (int k = 0; k < 3; ++k) col[k] = ray_colour(feat, i, k, color_act);
+            gw = g.gw(i, (t0 + t1) / 2.0f, col, d_weights);
         }
-        const float incl_t = asd_wave_incl_prod(1.f - alpha);
-        float excl = __shfl_up(incl_t, 1, 64);
-        if (lane == 0) excl = 1.f;
-        const float T = carry_t * excl;
-        carry_t *= __shfl(incl_t, 63, 64);
+        const float T = ray_trans_step(alpha, carry_t);
         if (valid) {
             const float da = T * (gw - R);
             float dn = 0.f;
@@ -331,8 +260,7 @@ __global__ __launch_bounds__(256) void neus_composite_bwd_kernel(
                 d_normal[3 * i + 1] = dn * dirs[3 * i + 1];
                 d_normal[3 * i + 2] = dn * dirs[3 * i + 2];
             }
-#pragma unroll
-            for (int k = 0; k < 3; ++k) d_feat[3 * i + k] = w * G[k] * (color_act == 1 ? col[k] * (1.f - col[k]) : 1.f);
+            g.store_d_feat(d_feat, i, w, col, color_act);
         }
     }
     if (dp_partial) {
@@ -341,7 +269,8 @@ __global__ __launch_bounds__(256) void neus_composite_bwd_kernel(
     }
 }
 
-// d_p[0] = (sum_r dp_partial[r]) da/dp: one block, every thread a fixed strided subset, a fixed tree above — the same bits every run
+// d_p[0] = (sum_r dp_partial[r]) da/dp: one block, every thread a fixed strided subset, a fixed tree above — the same bits every run.
+// Behind sdf_dp_reduce (ray_composite.h) for this file's backward pass and for asd_volsdf_composite_bwd.
 __global__ __launch_bounds__(1024) void neus_dp_reduce_kernel(const float* __restrict__ dp_partial, int n_rays, const float* __restrict__ p,
                                                               int use_volsdf, float* __restrict__ d_p) {
     __shared__ double ws[1024];
@@ -353,7 +282,11 @@ __global__ __launch_bounds__(1024) void neus_dp_reduce_kernel(const float* __res
         if ((int)threadIdx.x < o) ws[threadIdx.x] += ws[threadIdx.x + o];
         __syncthreads();
     }
-    if (threadIdx.x == 0) d_p[0] = (float)(ws[0] * (double)neus_variance(p, use_volsdf).dadp);
+    if (threadIdx.x == 0) d_p[0] = (float)(ws[0] * (double)sdf_variance(p, use_volsdf).dadp);
+}
+
+void sdf_dp_reduce(const float* dp_partial, int n_rays, const float* p, int use_volsdf, float* d_p, hipStream_t stream) {
+    hipLaunchKernelGGL(neus_dp_reduce_kernel, dim3(1), dim3(1024), 0, stream, dp_partial, n_rays, p, use_volsdf, d_p);
 }
 
 extern "C" {
@@ -412,9 +345,7 @@ int asd_neus_composite_bwd(const float* sdf, const float* normal, const float* d
                        t_start, t_end, features, color_act, inv_std_param, cos_anneal_ratio, use_volsdf != 0, bg, offset, count, n_rays, weights, opacity,
                        d_comp_rgb, d_rgb_fg, d_opacity, d_depth, d_weights, d_sdf, d_normal, d_features, d_bg,
                        d_inv_std_param ? dp_partial : (float*)nullptr);
-    if (d_inv_std_param)
-        hipLaunchKernelGGL(neus_dp_reduce_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, dp_partial, n_rays, inv_std_param, use_volsdf != 0,
-                           d_inv_std_param);
+    if (d_inv_std_param) sdf_dp_reduce(dp_partial, n_rays, inv_std_param, use_volsdf != 0, d_inv_std_param, (hipStream_t)stream);
     ASD_LAUNCH_CHECK();
     return ASD_OK;
 }

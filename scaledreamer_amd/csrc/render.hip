@@ -10,6 +10,7 @@
 // Roofline: bandwidth-trivial (32 B/sample in, 36 B/ray out — SURVEY.md §8d); these kernels are
 // latency/launch bound, so the design goal is FEW launches, not bytes.
 #include "asd_common.h"
+#include "ray_composite.h"
 
 #define RAYS_PER_BLOCK 4  // 256 threads = 4 waves = 4 rays
 
@@ -225,13 +226,7 @@ __global__ __launch_bounds__(256) void compact_kernel(const float* __restrict__ 
 // ---------------------------------------------------------------------------------------------------
 // compositing
 // ---------------------------------------------------------------------------------------------------
-// colour of sample i, channel k: `rgb` holds activated colours, or — rgb_act == 1 — the raw features of a material that is
-// colour = sigmoid(features) (NoMaterial, no_material.py:41-54): the activation and its gradient then ride in these kernels
-__device__ __forceinline__ float comp_colour(const float* __restrict__ rgb, size_t i, int k, int rgb_act) {
-    const float v = rgb[3 * i + k];
-    return rgb_act == 1 ? 1.f / (1.f + expf(-v)) : v;
-}
-
+// (colour read, transmittance step, per-ray images and the common part of their gradients: ray_composite.h)
 template <int MODE>
 __global__ __launch_bounds__(256) void composite_fwd_kernel(
     const float* __restrict__ sigma, const float* __restrict__ t_start, const float* __restrict__ t_end,
@@ -246,7 +241,7 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(
     // renderer's plain second moment sum_i w_i (t_i - depth)^2 (generative_space_volsdf_volume_renderer.py:380-385) instead of the
     // opacity-normalised, opacity-masked variance of the NeRF renderer (nerf_volume_renderer.py:335-349)
     float carry = MODE == 0 ? 0.f : 1.f;
-    float op = 0.f, dp = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f;
+    ray_images img;
     for (int j0 = 0; j0 < cnt; j0 += 64) {
         const int j = j0 + lane;
         const bool valid = j < cnt;
@@ -260,26 +255,16 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(
             carry += __shfl(incl, 63, 64);
         } else {
             alpha = valid ? sigma[i] : 0.f;
-            const float om = 1.f - alpha;
-            const float incl = asd_wave_incl_prod(om);
-            // exclusive product: shift the inclusive scan by one lane
-            float excl = __shfl_up(incl, 1, 64);
-            if (lane == 0) excl = 1.f;
-            T = carry * excl;
-            carry *= __shfl(incl, 63, 64);
+            T = ray_trans_step(alpha, carry);
         }
         if (valid) {
             const float w = T * alpha, t = (t_start[i] + t_end[i]) * 0.5f;
             weights[i] = w;
-            op += w;
-            dp = fmaf(w, t, dp);
-            c0 = fmaf(w, comp_colour(rgb, i, 0, rgb_act), c0);
-            c1 = fmaf(w, comp_colour(rgb, i, 1, rgb_act), c1);
-            c2 = fmaf(w, comp_colour(rgb, i, 2, rgb_act), c2);
+            img.add(w, t, rgb, i, rgb_act);
         }
     }
-    op = asd_wave_sum(op); dp = asd_wave_sum(dp);
-    c0 = asd_wave_sum(c0); c1 = asd_wave_sum(c1); c2 = asd_wave_sum(c2);
+    img.reduce();
+    const float op = img.op, dp = img.dp;
     const float m = MODE == 2 ? 1.f : fmaxf(op, 1e-5f), zm = dp / m;
     float zv = 0.f;
     for (int j = lane; j < cnt; j += 64) {
@@ -289,14 +274,8 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(
     }
     zv = asd_wave_sum(zv);
     if (lane == 0) {
-        opacity[r] = op;
-        depth[r] = dp;
+        img.store(r, bg, opacity, depth, rgb_fg, comp_rgb);
         z_var[r] = (MODE == 2 || op > 0.5f) ? zv : 0.f;
-        rgb_fg[3 * (size_t)r] = c0; rgb_fg[3 * (size_t)r + 1] = c1; rgb_fg[3 * (size_t)r + 2] = c2;
-        const float k = 1.f - op;
-        comp_rgb[3 * (size_t)r] = c0 + bg[3 * (size_t)r] * k;
-        comp_rgb[3 * (size_t)r + 1] = c1 + bg[3 * (size_t)r + 1] * k;
-        comp_rgb[3 * (size_t)r + 2] = c2 + bg[3 * (size_t)r + 2] * k;
     }
 }
 
@@ -314,15 +293,8 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
     const int lane = asd_lane();
     const int b = offset[r], cnt = count[r];
     const float op = opacity[r], m = MODE == 2 ? 1.f : fmaxf(op, 1e-5f), zm = depth[r] / m;
-    float G[3], gop = d_opacity ? d_opacity[r] : 0.f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float gc = d_comp_rgb ? d_comp_rgb[3 * (size_t)r + k] : 0.f;
-        G[k] = gc + (d_rgb_fg ? d_rgb_fg[3 * (size_t)r + k] : 0.f);
-        gop -= gc * bg[3 * (size_t)r + k];
-        if (d_bg && lane == 0) d_bg[3 * (size_t)r + k] = gc * (1.f - op);
-    }
-    const float gdp = d_depth ? d_depth[r] : 0.f;
+    ray_grads g;
+    g.load(r, d_comp_rgb, d_rgb_fg, d_opacity, d_depth, bg, op, d_bg);
     const float gzv = (d_z_var && (MODE == 2 || op > 0.5f)) ? d_z_var[r] : 0.f;
     float zvu = 0.f;
     if (gzv != 0.f && MODE != 2) {
@@ -333,17 +305,18 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
         }
         zvu = asd_wave_sum(zvu);
     }
+    // dL/dw_i: the common part and the z-variance's own
+    auto gw_of = [&](int i, float t, const float (&col)[3]) {
+        float gw = g.gw(i, t, col, d_weights);
+        if (gzv != 0.f) gw += MODE == 2 ? gzv * ((t - zm) * (t - zm) - 2.f * t * zm * (1.f - op)) : gzv * ((t - zm) * (t - zm) - zvu) / m;
+        return gw;
+    };
     // pass 1: total = sum_i w_i gw_i
     float tot = 0.f;
     for (int j = lane; j < cnt; j += 64) {
         const int i = b + j;
-        const float t = (t_start[i] + t_end[i]) * 0.5f;
-        float gw = gop + gdp * t + (d_weights ? d_weights[i] : 0.f);
-        gw = fmaf(G[0], comp_colour(rgb, i, 0, rgb_act), gw);
-        gw = fmaf(G[1], comp_colour(rgb, i, 1, rgb_act), gw);
-        gw = fmaf(G[2], comp_colour(rgb, i, 2, rgb_act), gw);
-        if (gzv != 0.f) gw += MODE == 2 ? gzv * ((t - zm) * (t - zm) - 2.f * t * zm * (1.f - op)) : gzv * ((t - zm) * (t - zm) - zvu) / m;
-        tot = fmaf(weights[i], gw, tot);
+        const float col[3] = {ray_colour(rgb, i, 0, rgb_act), ray_colour(rgb, i, 1, rgb_act), ray_colour(rgb, i, 2, rgb_act)};
+        tot = fmaf(weights[i], gw_of(i, (t_start[i] + t_end[i]) * 0.5f, col), tot);
     }
     tot = asd_wave_sum(tot);
     // pass 2: suffix sums S_i = tot - inclusive_prefix_i and the transmittances
@@ -360,10 +333,9 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
             dt = t_end[i] - t_start[i];
             w = weights[i];
             sv = sigma[i];
-            gw = gop + gdp * t + (d_weights ? d_weights[i] : 0.f);
 #pragma unroll
-            for (int k = 0; k < 3; ++k) { col[k] = comp_colour(rgb, i, k, rgb_act); gw = fmaf(G[k], col[k], gw); }
-            if (gzv != 0.f) gw += MODE == 2 ? gzv * ((t - zm) * (t - zm) - 2.f * t * zm * (1.f - op)) : gzv * ((t - zm) * (t - zm) - zvu) / m;
+            for (int k = 0; k < 3; ++k) col[k] = ray_colour(rgb, i, k, rgb_act);
+            gw = gw_of(i, t, col);
         }
         const float wg = w * gw;
         const float incl_s = asd_wave_incl_scan(wg);
@@ -377,18 +349,12 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
             carry_t += __shfl(incl_t, 63, 64);
             ds = dt * (Tnext * gw - S);
         } else {
-            const float om = valid ? 1.f - sv : 1.f;
-            const float incl_t = asd_wave_incl_prod(om);
-            float excl = __shfl_up(incl_t, 1, 64);
-            if (lane == 0) excl = 1.f;
-            const float T = carry_t * excl;
-            carry_t *= __shfl(incl_t, 63, 64);
+            const float T = ray_trans_step(sv, carry_t);       // (sv = 0 in a lane without a sample)
             ds = T * gw - S / fmaxf(1.f - sv, 1e-10f);
         }
         if (valid) {
             d_sigma[i] = ds;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) d_rgb[3 * (size_t)i + k] = w * G[k] * (rgb_act == 1 ? col[k] * (1.f - col[k]) : 1.f);
+            g.store_d_feat(d_rgb, i, w, col, rgb_act);
         }
     }
 }

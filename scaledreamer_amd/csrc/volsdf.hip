@@ -9,40 +9,14 @@
 //   asd_volsdf_composite_bwd  its gradient w.r.t. sdf, features, background and the variance      (one wave per ray + one tiny reduce)
 // Roofline: bandwidth-trivial (4 096 rays x 193 samples x ~36 B = 28 MB per compositing pass); what these kernels buy is launches —
 // seven forward and one or two backward where the composed path enqueues about ninety (782 -> 702 per Hyper-iNGP step).
-// The learned variance is read on the device from the raw parameter p: a = clamp(clamp(exp(10 p), 1e-6, 1e6), 0, 80)
-// (LearnedVariance.forward + volsdf_density, neus_volume_renderer.py:19-23,31-44).
+// Shared with render.hip and neus.hip, in ray_composite.h: the learned variance read on the device (here always with the VolSDF clamp)
+// and the density, the colour read, the transmittance step, the per-ray images and the common part of their gradients; the
+// variance-gradient reduce is sdf_dp_reduce of neus.hip.
 #include "asd_common.h"
+#include "ray_composite.h"
 
 #define VOLSDF_RAYS_PER_BLOCK 4     // 256 threads = 4 waves = 4 rays
 #define VOLSDF_MAX_CDF_SAMPLES 2048 // asd_volsdf_proposal_cdf keeps one float per sample of its 4 rays in LDS (32 KB)
-
-struct volsdf_var {
-    float a;        // the clamped inverse standard deviation the density uses
-    float beta;     // 1 / a: the density divides by it, as the reference does
-    float dadp;     // d a / d p: 10 exp(10 p) where neither clamp is active (torch.clamp passes the gradient on the closed interval), else 0
-};
-
-__device__ __forceinline__ volsdf_var volsdf_variance(const float* __restrict__ p) {
-    const float raw = expf(p[0] * 10.0f);
-    const float a1 = fminf(fmaxf(raw, 1.0e-6f), 1.0e6f);
-    volsdf_var v;
-    v.a = fminf(fmaxf(a1, 0.f), 80.f);
-    v.beta = 1.f / v.a;
-    v.dadp = (raw >= 1.0e-6f && raw <= 80.f) ? 10.0f * raw : 0.f;
-    return v;
-}
-
-// sigma = a (0.5 + 0.5 sign(s) expm1(-|s| / beta)) in the reference's operation order; em1 = expm1(-|s| / beta), sg = sign(s)
-__device__ __forceinline__ float volsdf_sigma(float s, const volsdf_var& v, float& sg, float& em1) {
-    sg = s > 0.f ? 1.f : (s < 0.f ? -1.f : 0.f);
-    em1 = expm1f(-fabsf(s) / v.beta);
-    return v.a * (0.5f + 0.5f * sg * em1);
-}
-
-__device__ __forceinline__ float volsdf_colour(const float* __restrict__ f, size_t i, int k, int act) {
-    const float v = f[3 * i + k];
-    return act == 1 ? 1.f / (1.f + expf(-v)) : v;
-}
 
 // ---- sampling ---------------------------------------------------------------------------------------------------------------------
 // asd_importance_resample's search and interpolation (amortized.hip: same arithmetic, bit-identical edges) with the s -> t map behind it
@@ -103,10 +77,10 @@ __global__ __launch_bounds__(256) void volsdf_proposal_cdf_kernel(const float* _
     float* acc_s = lds + (size_t)wid * S;
     const float* t = t_edges + (size_t)(live ? r : 0) * (S + 1);
     if (live) {
-        const volsdf_var v = volsdf_variance(p);
+        const sdf_var v = sdf_variance(p, 1);
         for (int j = lane; j < S; j += 64) {
             float sg, em1;
-            acc_s[j] = volsdf_sigma(sdf[(size_t)r * S + j], v, sg, em1);
+            acc_s[j] = volsdf_sigma(sdf[(size_t)r * S + j], v.a, sg, em1);
         }
     }
     __syncthreads();
@@ -140,9 +114,10 @@ __global__ __launch_bounds__(256) void volsdf_composite_fwd_kernel(
     const int lane = asd_lane();
     const size_t b = (size_t)r * S;
     const float* t = t_edges + (size_t)r * (S + 1);
-    const volsdf_var v = volsdf_variance(p);
+    const sdf_var v = sdf_variance(p, 1);
     float carry = 1.f;
-    float op = 0.f, dp = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f, n0 = 0.f, n1 = 0.f, n2 = 0.f;
+    ray_images img;
+    ray_normal nrm;
     for (int j0 = 0; j0 < S; j0 += 64) {
         const int j = j0 + lane;
         const bool valid = j < S;
@@ -151,55 +126,31 @@ __global__ __launch_bounds__(256) void volsdf_composite_fwd_kernel(
         if (valid) {
             const float t0 = t[j], t1 = t[j + 1];
             float sg, em1;
-            alpha = fabsf(t1 - t0) * volsdf_sigma(sdf[i], v, sg, em1);
+            alpha = fabsf(t1 - t0) * volsdf_sigma(sdf[i], v.a, sg, em1);
             tm = (t0 + t1) * 0.5f;
         }
-        const float incl = asd_wave_incl_prod(1.f - alpha);
-        float excl = __shfl_up(incl, 1, 64);      // exclusive product: the inclusive scan shifted by one lane
-        if (lane == 0) excl = 1.f;
-        const float T = carry * excl;
-        carry *= __shfl(incl, 63, 64);
+        const float T = ray_trans_step(alpha, carry);
         if (valid) {
             const float w = T * alpha;
             weights[i] = w;
-            op += w;
-            dp = fmaf(w, tm, dp);
-            c0 = fmaf(w, volsdf_colour(feat, i, 0, color_act), c0);
-            c1 = fmaf(w, volsdf_colour(feat, i, 1, color_act), c1);
-            c2 = fmaf(w, volsdf_colour(feat, i, 2, color_act), c2);
-            if (normal) {
-                n0 = fmaf(w, normal[3 * i], n0);
-                n1 = fmaf(w, normal[3 * i + 1], n1);
-                n2 = fmaf(w, normal[3 * i + 2], n2);
-            }
+            img.add(w, tm, feat, i, color_act);
+            if (normal) nrm.add(w, normal, i);
         }
     }
-    op = asd_wave_sum(op); dp = asd_wave_sum(dp);
-    c0 = asd_wave_sum(c0); c1 = asd_wave_sum(c1); c2 = asd_wave_sum(c2);
+    img.reduce();
     // z_variance = sum_i w_i (t_i - depth)^2, unnormalised and unmasked (generative_space_volsdf_volume_renderer.py:380-385); every lane
     // reads back the weights it wrote itself
     float zv = 0.f;
     for (int j = lane; j < S; j += 64) {
         const float tm = (t[j] + t[j + 1]) * 0.5f;
-        zv = fmaf(weights[b + j], (tm - dp) * (tm - dp), zv);
+        zv = fmaf(weights[b + j], (tm - img.dp) * (tm - img.dp), zv);
     }
     zv = asd_wave_sum(zv);
-    if (normal) { n0 = asd_wave_sum(n0); n1 = asd_wave_sum(n1); n2 = asd_wave_sum(n2); }
+    if (normal) nrm.reduce();
     if (lane == 0) {
-        opacity[r] = op;
-        depth[r] = dp;
         z_var[r] = zv;
-        rgb_fg[3 * (size_t)r] = c0; rgb_fg[3 * (size_t)r + 1] = c1; rgb_fg[3 * (size_t)r + 2] = c2;
-        const float k = 1.f - op;
-        comp_rgb[3 * (size_t)r] = c0 + bg[3 * (size_t)r] * k;
-        comp_rgb[3 * (size_t)r + 1] = c1 + bg[3 * (size_t)r + 1] * k;
-        comp_rgb[3 * (size_t)r + 2] = c2 + bg[3 * (size_t)r + 2] * k;
-        if (normal) {       // lerp(0, (F.normalize(sum_i w_i n_i) + 1) / 2, opacity)
-            const float len = fmaxf(sqrtf(n0 * n0 + n1 * n1 + n2 * n2), 1e-12f);
-            comp_normal[3 * (size_t)r] = (n0 / len + 1.0f) * 0.5f * op;
-            comp_normal[3 * (size_t)r + 1] = (n1 / len + 1.0f) * 0.5f * op;
-            comp_normal[3 * (size_t)r + 2] = (n2 / len + 1.0f) * 0.5f * op;
-        }
+        img.store(r, bg, opacity, depth, rgb_fg, comp_rgb);
+        if (normal) nrm.store(r, img.op, comp_normal);
     }
 }
 
@@ -222,7 +173,7 @@ __device__ __forceinline__ float volsdf_wave_suffix_sum(float v) {
 // S_i is summed from the FAR end of the ray (a suffix scan, walking the trips backwards) instead of `total - prefix`: behind the surface, where
 // T_i and S_i both vanish, the difference of two sums of the whole ray would leave a rounding residue of ~1e-7 in every sample — harmless in
 // d_sdf, but dL/da adds it up over every sample inside the object.  The suffix sums wait in d_sdf (each lane reads back what it wrote itself).
-// dp_partial[r] receives the ray's part of dL/da (a wave sum: no atomics), volsdf_dp_reduce_kernel adds the rays in a fixed order.
+// dp_partial[r] receives the ray's part of dL/da (a wave sum: no atomics), sdf_dp_reduce adds the rays in a fixed order.
 __global__ __launch_bounds__(256) void volsdf_composite_bwd_kernel(
     const float* __restrict__ sdf, const float* __restrict__ feat, int color_act, const float* __restrict__ normal,
     const float* __restrict__ t_edges, const float* __restrict__ p, const float* __restrict__ bg, int n_rays, int S,
@@ -235,38 +186,22 @@ __global__ __launch_bounds__(256) void volsdf_composite_bwd_kernel(
     const int lane = asd_lane();
     const size_t b = (size_t)r * S;
     const float* t = t_edges + (size_t)r * (S + 1);
-    const volsdf_var v = volsdf_variance(p);
+    const sdf_var v = sdf_variance(p, 1);
     const float op = opacity[r], zm = depth[r];
-    float G[3], gop = d_opacity ? d_opacity[r] : 0.f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float gc = d_comp_rgb ? d_comp_rgb[3 * (size_t)r + k] : 0.f;
-        G[k] = gc + (d_rgb_fg ? d_rgb_fg[3 * (size_t)r + k] : 0.f);
-        gop -= gc * bg[3 * (size_t)r + k];
-        if (d_bg && lane == 0) d_bg[3 * (size_t)r + k] = gc * (1.f - op);
-    }
-    const float gdp = d_depth ? d_depth[r] : 0.f;
+    ray_grads g;
+    g.load(r, d_comp_rgb, d_rgb_fg, d_opacity, d_depth, bg, op, d_bg);
     const float gzv = d_z_var ? d_z_var[r] : 0.f;
     if (normal && d_comp_normal) {      // d opacity += d comp_normal . (normalize(sum_i w_i n_i) + 1) / 2
-        float n0 = 0.f, n1 = 0.f, n2 = 0.f;
-        for (int j = lane; j < S; j += 64) {
-            const size_t i = b + j;
-            const float w = weights[i];
-            n0 = fmaf(w, normal[3 * i], n0);
-            n1 = fmaf(w, normal[3 * i + 1], n1);
-            n2 = fmaf(w, normal[3 * i + 2], n2);
-        }
-        n0 = asd_wave_sum(n0); n1 = asd_wave_sum(n1); n2 = asd_wave_sum(n2);
-        const float len = fmaxf(sqrtf(n0 * n0 + n1 * n1 + n2 * n2), 1e-12f);
-        gop = fmaf(d_comp_normal[3 * (size_t)r], (n0 / len + 1.0f) * 0.5f, gop);
-        gop = fmaf(d_comp_normal[3 * (size_t)r + 1], (n1 / len + 1.0f) * 0.5f, gop);
-        gop = fmaf(d_comp_normal[3 * (size_t)r + 2], (n2 / len + 1.0f) * 0.5f, gop);
+        ray_normal nrm;
+        for (int j = lane; j < S; j += 64) nrm.add(weights[b + j], normal, b + j);
+        nrm.reduce();
+        float u[3];
+        nrm.shade(u);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) g.gop = fmaf(d_comp_normal[3 * (size_t)r + k], u[k], g.gop);
     }
     auto gw_of = [&](size_t i, float tm, const float (&col)[3]) {
-        float gw = gop + gdp * tm + (d_weights ? d_weights[i] : 0.f);
-        gw = fmaf(G[0], col[0], gw);
-        gw = fmaf(G[1], col[1], gw);
-        gw = fmaf(G[2], col[2], gw);
+        float gw = g.gw(i, tm, col, d_weights);
         // d z_var / d w_i = (t_i - depth)^2 - 2 t_i depth (1 - opacity): the second term is the depth moving under every other sample
         if (gzv != 0.f) gw += gzv * ((tm - zm) * (tm - zm) - 2.f * tm * zm * (1.f - op));
         return gw;
@@ -279,7 +214,7 @@ __global__ __launch_bounds__(256) void volsdf_composite_bwd_kernel(
         const size_t i = b + j;
         float wg = 0.f;
         if (valid) {
-            const float col[3] = {volsdf_colour(feat, i, 0, color_act), volsdf_colour(feat, i, 1, color_act), volsdf_colour(feat, i, 2, color_act)};
+            const float col[3] = {ray_colour(feat, i, 0, color_act), ray_colour(feat, i, 1, color_act), ray_colour(feat, i, 2, color_act)};
             wg = weights[i] * gw_of(i, (t[j] + t[j + 1]) * 0.5f, col);
         }
         const float incl = volsdf_wave_suffix_sum(wg);
@@ -300,50 +235,31 @@ __global__ __launch_bounds__(256) void volsdf_composite_bwd_kernel(
             const float t0 = t[j], t1 = t[j + 1];
             dt = fabsf(t1 - t0);
             s = sdf[i];
-            alpha = dt * volsdf_sigma(s, v, sg, em1);
+            alpha = dt * volsdf_sigma(s, v.a, sg, em1);
             w = weights[i];
             Ssuf = d_sdf[i];
 #pragma unroll
-            for (int k = 0; k < 3; ++k) col[k] = volsdf_colour(feat, i, k, color_act);
+            for (int k = 0; k < 3; ++k) col[k] = ray_colour(feat, i, k, color_act);
             gw = gw_of(i, (t0 + t1) * 0.5f, col);
         }
         const float om = 1.f - alpha;
-        const float incl_t = asd_wave_incl_prod(om);
-        float excl = __shfl_up(incl_t, 1, 64);
-        if (lane == 0) excl = 1.f;
-        const float T = carry_t * excl;
-        carry_t *= __shfl(incl_t, 63, 64);
+        const float T = ray_trans_step(alpha, carry_t);
         if (valid) {
             // d w_j / d alpha_i = -w_j / (1 - alpha_i) for j > i holds for either sign of 1 - alpha_i (alpha is not clamped); only a
             // factor of exactly zero has no quotient form, and is kept away from it
             const float om_safe = fabsf(om) < 1e-10f ? copysignf(1e-10f, om) : om;
             const float da = T * gw - Ssuf / om_safe;
-            const float e = expf(-fabsf(s) / v.beta);       // (not em1 + 1: far from the surface that sum has no digits left)
+            const float beta = 1.f / v.a;
+            const float e = expf(-fabsf(s) / beta);       // (not em1 + 1: far from the surface that sum has no digits left)
             d_sdf[i] = da * dt * (-0.5f * v.a * v.a * e * sg * sg);
             dpa = fmaf(da * dt, (0.5f + 0.5f * sg * em1) - 0.5f * v.a * s * e, dpa);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) d_feat[3 * i + k] = w * G[k] * (color_act == 1 ? col[k] * (1.f - col[k]) : 1.f);
+            g.store_d_feat(d_feat, i, w, col, color_act);
         }
     }
     if (dp_partial) {
         dpa = asd_wave_sum(dpa);
         if (lane == 0) dp_partial[r] = dpa;
     }
-}
-
-// d_p[0] = (sum_r dp_partial[r]) da/dp: one block, every thread a fixed strided subset, a fixed tree above — the same bits every run
-__global__ __launch_bounds__(1024) void volsdf_dp_reduce_kernel(const float* __restrict__ dp_partial, int n_rays, const float* __restrict__ p,
-                                                                float* __restrict__ d_p) {
-    __shared__ double ws[1024];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < n_rays; i += 1024) acc += (double)dp_partial[i];
-    ws[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) ws[threadIdx.x] += ws[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) d_p[0] = (float)(ws[0] * (double)volsdf_variance(p).dadp);
 }
 
 extern "C" {
@@ -417,8 +333,7 @@ int asd_volsdf_composite_bwd(const float* sdf, const float* features, int32_t co
     hipLaunchKernelGGL(volsdf_composite_bwd_kernel, dim3(asd_div_up(n_rays, VOLSDF_RAYS_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream, sdf, features,
                        color_act, normal, t_edges, inv_std_param, bg, n_rays, S, weights, opacity, depth, d_comp_rgb, d_rgb_fg, d_opacity, d_depth,
                        d_z_var, d_weights, d_comp_normal, d_sdf, d_features, d_bg, d_inv_std_param ? dp_partial : (float*)nullptr);
-    if (d_inv_std_param)
-        hipLaunchKernelGGL(volsdf_dp_reduce_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, dp_partial, n_rays, inv_std_param, d_inv_std_param);
+    if (d_inv_std_param) sdf_dp_reduce(dp_partial, n_rays, inv_std_param, 1, d_inv_std_param, (hipStream_t)stream);
     ASD_LAUNCH_CHECK();
     return ASD_OK;
 }

@@ -7,7 +7,7 @@ csrc/render.hip; what is specific to NeuS — the opacity model of the learned v
     forward      field with normals -> material -> background -> ONE asd_neus_composite_fwd inside one autograd node
     update_step  cos_anneal_ratio, and the occupancy update with asd_neus_step_alpha as occ_eval_fn
 Two routes (ASD_NEUS, read at every call; "0" = composed, kept as fallback and A/B partner): the composed route forms alpha with tensor ops
-(get_alpha / step_alpha below), prunes with asd_prune_count fed -log(1 - alpha) / dt and composites with asd_composite_* mode 1.
+(get_alpha / step_alpha of sdf_opacity.py), prunes with asd_prune_count fed -log(1 - alpha) / dt and composites with asd_composite_* mode 1.
 This first version reads the kept count once per pass; the sync-free, capacity-sized form of the NeRF renderer is not carried over.
 """
 from __future__ import annotations
@@ -22,29 +22,7 @@ import torch.nn.functional as F
 from . import nerfacc_api, ops
 from .registry import register
 from .renderer import VolumeRenderer, chunk_batch, validate_empty_rays
-from .volsdf_renderer import LearnedVariance, volsdf_density
-
-
-def step_alpha(sdf: torch.Tensor, inv_std: torch.Tensor, step: float, use_volsdf: bool) -> torch.Tensor:
-    """alpha_fn / occ_eval_fn (neus_volume_renderer.py:154-164, 366-376) as tensor ops"""
-    if use_volsdf:
-        return step * volsdf_density(sdf, inv_std)
-    prev_cdf = torch.sigmoid((sdf + step * 0.5) * inv_std)
-    next_cdf = torch.sigmoid((sdf - step * 0.5) * inv_std)
-    return ((prev_cdf - next_cdf + 1e-5) / (prev_cdf + 1e-5)).clip(0.0, 1.0)
-
-
-def get_alpha(sdf, normal, dirs, dists, inv_std, cos_anneal_ratio: float, use_volsdf: bool) -> torch.Tensor:
-    """neus_volume_renderer.py:93-117 as tensor ops; sdf, dists [n, 1], normal, dirs [n, 3], inv_std broadcastable to sdf"""
-    if use_volsdf:
-        return torch.abs(dists.detach()) * volsdf_density(sdf, inv_std)
-    true_cos = (dirs * normal).sum(-1, keepdim=True)
-    iter_cos = -(F.relu(-true_cos * 0.5 + 0.5) * (1.0 - cos_anneal_ratio) + F.relu(-true_cos) * cos_anneal_ratio)   # always non-positive
-    estimated_next_sdf = sdf + iter_cos * dists * 0.5
-    estimated_prev_sdf = sdf - iter_cos * dists * 0.5
-    prev_cdf = torch.sigmoid(estimated_prev_sdf * inv_std)
-    next_cdf = torch.sigmoid(estimated_next_sdf * inv_std)
-    return ((prev_cdf - next_cdf + 1e-5) / (prev_cdf + 1e-5)).clip(0.0, 1.0)
+from .sdf_opacity import LearnedVariance, get_alpha, kernel_color_act, step_alpha
 
 
 class _NeuSCompositeFn(torch.autograd.Function):
@@ -120,13 +98,7 @@ class NeuSVolumeRenderer(VolumeRenderer):
         return os.environ.get("ASD_NEUS", "1") != "0" and t.is_cuda
 
     def _color_act(self) -> Optional[int]:
-        """asd_neus_composite_*'s color_act when the material is colour = activation(features) with an activation the kernels carry, else None"""
-        mat = self.material
-        if not getattr(mat, "elementwise", False) or getattr(mat.cfg, "n_output_dims", None) != 3:
-            return None
-        name = getattr(mat.cfg, "color_activation", None)
-        name = "none" if name is None else str(name).lower()
-        return {"none": 0, "sigmoid": 1}.get(name)
+        return kernel_color_act(self.material)
 
     def get_alpha(self, sdf, normal, dirs, dists):
         return get_alpha(sdf, normal, dirs, dists, self.variance(sdf), self.cos_anneal_ratio, self.cfg.use_volsdf)

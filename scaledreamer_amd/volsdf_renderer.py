@@ -26,33 +26,13 @@ from dataclasses import dataclass
 from typing import Any, Dict, Optional, Tuple
 
 import torch
-import torch.nn as nn
 import torch.nn.functional as F
 
 from . import nerfacc_api, ops
 from .estimators import ImportanceEstimator
 from .registry import register
 from .renderer import VolumeRenderer
-
-
-def volsdf_density(sdf: torch.Tensor, inv_std: torch.Tensor) -> torch.Tensor:
-    """neus_volume_renderer.py:19-23"""
-    inv_std = inv_std.clamp(0.0, 80.0)
-    beta = 1 / inv_std
-    return inv_std * (0.5 + 0.5 * sdf.sign() * torch.expm1(-sdf.abs() / beta))
-
-
-class LearnedVariance(nn.Module):
-    def __init__(self, init_val, requires_grad=True):
-        super().__init__()
-        self.register_parameter("_inv_std", nn.Parameter(torch.tensor(init_val), requires_grad=requires_grad))
-
-    @property
-    def inv_std(self):
-        return torch.exp(self._inv_std * 10.0)
-
-    def forward(self, x):
-        return torch.ones_like(x) * self.inv_std.clamp(1.0e-6, 1.0e6)
+from .sdf_opacity import LearnedVariance, get_alpha, kernel_color_act, volsdf_density
 
 
 class _VolSDFCompositeFn(torch.autograd.Function):
@@ -133,17 +113,7 @@ class GenerativeSpaceVolSDFVolumeRenderer(VolumeRenderer):
 
     # ---- alpha models ---------------------------------------------------------------------------------------------------------------
     def get_alpha(self, sdf, normal, dirs, dists):
-        """VolSDF: alpha = |dt| * sigma(sdf) (neus_volume_renderer.py:93-96); NeuS: the discrete opacity of the logistic cdf along
-        the ray with the annealed cosine (:97-117)"""
-        inv_std = self.variance(sdf)
-        if self.cfg.use_volsdf:
-            return dists.detach().abs() * volsdf_density(sdf, inv_std)
-        cos = (dirs * normal).sum(-1, keepdim=True)
-        k = self.cos_anneal_ratio
-        slope = -(F.relu(0.5 - 0.5 * cos) * (1.0 - k) + F.relu(-cos) * k)
-        half = slope * dists * 0.5
-        cdf_in, cdf_out = torch.sigmoid((sdf - half) * inv_std), torch.sigmoid((sdf + half) * inv_std)
-        return ((cdf_in - cdf_out + 1e-5) / (cdf_in + 1e-5)).clip(0.0, 1.0)
+        return get_alpha(sdf, normal, dirs, dists, self.variance(sdf), self.cos_anneal_ratio, self.cfg.use_volsdf)
 
     def _chunk(self) -> int:
         """point-axis chunk of the field calls: none while training unless train_chunk_size asks for it"""
@@ -232,13 +202,7 @@ class GenerativeSpaceVolSDFVolumeRenderer(VolumeRenderer):
 
     # ---- the pass-level route ---------------------------------------------------------------------------------------------------------
     def _color_act(self) -> Optional[int]:
-        """asd_volsdf_composite_*'s color_act when the material is colour = activation(features) with an activation the kernels carry, else None"""
-        mat = self.material
-        if not getattr(mat, "elementwise", False) or getattr(mat.cfg, "n_output_dims", None) != 3:
-            return None
-        name = getattr(mat.cfg, "color_activation", None)
-        name = "none" if name is None else str(name).lower()
-        return {"none": 0, "sigmoid": 1}.get(name)
+        return kernel_color_act(self.material)
 
     def _pass_level(self, rays_o) -> bool:
         return (os.environ.get("ASD_VOLSDF", "1") != "0" and rays_o.is_cuda and rays_o.dtype == torch.float32 and self.cfg.use_volsdf
