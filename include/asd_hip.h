@@ -1044,6 +1044,27 @@ int64_t asd_clip_score_workspace(int64_t B, int64_t P);
 int asd_clip_score_f32(const float* img, const float* txt, const int32_t* own, int64_t B, int64_t P, int32_t D, float* sim, int32_t* top1,
                        void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * CLIP text tower (csrc/text.hip; the schedule is scaledreamer_amd/diffusion/text_hip.py): what transformers' CLIPTextModel does for the
+ * reference's prompt processors, one string per call in fp32 (custom/amortized/models/prompt_processors/
+ * stable_diffusion_multi_prompt_processor.py:58-70, base.py:298-305).  LayerNorms and linears are asd_layernorm_f16 / asd_gemm_f16.
+ *
+ * CLIPTextEmbeddings.forward: x [P L, C] fp16 = token_embedding[input_ids[p, t]] + position_embedding[t], summed in fp32 and rounded once.
+ * input_ids int32 [P, L]; token_embedding [vocab, C], position_embedding [>= L, C], x: fp16, 16-byte aligned; C % 8 == 0.  The caller
+ * validates 0 <= id < vocab; an id outside is clamped here so that nothing outside the table is read. */
+int asd_text_embed_f16(const int32_t* input_ids, int32_t P, int32_t L, int32_t vocab, int32_t C, const void* token_embedding,
+                       const void* position_embedding, void* x, void* stream);
+/* CLIPAttention.forward with the causal mask (query t sees keys 0 .. t), head dim 64, fp16 in and out, fp32 scores, softmax and
+ * accumulation.  q, k, v, o are [batch * L, >= heads * 64] row-major with their own leading dimensions (in elements; ldq, ldk, ldv
+ * % 8 == 0, ldo % 4 == 0): the three column blocks of one fused qkv projection are read in place with ld = 3 C.  1 <= L <= 128, anything
+ * else is ASD_ERR_ARG without a launch.  One workgroup per (sequence, head); no atomics, no workspace; rows and keys from L up to the
+ * tile edge are neither read nor written, and output rows <= t do not depend on rows > t of q, k, v. */
+int asd_attention_causal_f16(const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v, int32_t ldv, void* o, int32_t ldo,
+                             int32_t batch, int32_t heads, int32_t L, float scale, void* stream);
+/* y = 0.5 x (1 + erf(x / sqrt 2)) elementwise (CLIPMLP with hidden_act "gelu": torch's exact-form GELU), fp16, any n >= 1 (x, y 16-byte
+ * aligned; may be the same buffer), with the erf of the GEGLU epilogue of asd_gemm_f16 (Abramowitz & Stegun 7.1.26, |error| <= 1.5e-7). */
+int asd_gelu_f16(const void* x, int64_t n, void* y, void* stream);
+
 /* library info */
 const char* asd_version(void);
 const char* asd_last_error(void);

@@ -192,6 +192,7 @@ SYMBOLS = [
     "asd_atlas_layout", "asd_atlas_uv", "asd_atlas_bake", "asd_atlas_pack_u8",
     "asd_image_minmax_workspace", "asd_image_minmax_f32", "asd_image_grid_u8",
     "asd_clip_preprocess_u8", "asd_clip_embed_f16", "asd_quick_gelu_f16", "asd_clip_score_workspace", "asd_clip_score_f32",
+    "asd_text_embed_f16", "asd_attention_causal_f16", "asd_gelu_f16",
     "asd_comm_unique_id", "asd_comm_create", "asd_comm_destroy", "asd_allreduce_mean_f32",
     "asd_version", "asd_last_error", "asd_modulated_weights_fwd", "asd_modulated_weights_bwd", "asd_timestep_plus", "asd_loss_tail_fwd", "asd_loss_tail_bwd", "asd_probe_events", "asd_probe_mark",
 ]

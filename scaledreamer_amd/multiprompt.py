@@ -351,6 +351,8 @@ class MultipromptRadienceFieldGeneratorSystem(StableDreamer):
         self.prompt_processor = prompt_processor
 
     def forward(self, batch: Dict[str, Any]) -> Dict[str, Any]:
+        if self.prompt_processor is None:       # none was passed in: the configured one (:68-90 there), built at first use
+            self.prompt_processor = find(self.cfg.prompt_processor_type)(self.cfg.prompt_processor)
         self.prompt_utils = self.prompt_processor(prompt=batch["prompt"])
         if "prompt_target" in batch:  # interpolation between two prompts (test time)
             target = self.prompt_processor(prompt=batch["prompt_target"])

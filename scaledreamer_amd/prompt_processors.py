@@ -2,8 +2,9 @@
 stable_diffusion_prompt_processor.py): view-dependent prompt strings, the text-embedding cache, and the PromptUtils object the
 guidance consumes.  The cache format is the reference's — `.threestudio_cache/text_embeddings/<md5(f"{model}-{prompt}")>.pt`
 holding one [77, 1024] tensor per prompt (base.py:19-23, 349-420) — so embeddings computed by a ScaleDreamer installation are
-picked up unchanged.  No text encoder ships with this repository (it runs once, off the step path): a missing cache entry is
-computed by `encode_fn(prompts) -> [n, 77, 1024]` when one is given, otherwise it is the reference's FileNotFoundError.
+picked up unchanged.  A missing cache entry is computed by `encode_fn(prompts) -> [n, 77, 1024]` when one is given; without one, by the
+HIP text encoder (diffusion/text_hip.py) when `<pretrained_model_name_or_path>/text_encoder` and `/tokenizer` exist locally; otherwise
+it is the reference's FileNotFoundError.
 """
 from __future__ import annotations
 
@@ -93,12 +94,32 @@ class StableDiffusionPromptProcessor(BaseObject):
     def prepare_text_embeddings(self) -> None:
         todo = [p for p in dict.fromkeys([self.prompt, self.negative_prompt] + self.prompts_vd + self.negative_prompts_vd)
                 if not (self.cfg.use_cache and os.path.exists(self._cache_path(p)))]
-        if not todo or self.encode_fn is None:
+        encode_fn = self.encode_fn
+        if todo and encode_fn is None:
+            from .multiprompt_processors import has_local_text_encoder
+
+            if has_local_text_encoder(self.cfg.pretrained_model_name_or_path):
+                encode_fn = self._encode_locally
+        if not todo or encode_fn is None:
             return
         os.makedirs(self._cache_dir, exist_ok=True)
-        emb = self.encode_fn(todo)
+        emb = encode_fn(todo)
         for p, e in zip(todo, emb):
             torch.save(e.detach().cpu(), self._cache_path(p))
+
+    def _encode_locally(self, prompts: List[str]) -> torch.Tensor:
+        """last_hidden_state fp32 [n, 77, C] from <model>/text_encoder and <model>/tokenizer on the HIP encoder (diffusion/text_hip.py)"""
+        from .multiprompt_processors import encode_in_batches, local_tokenizer
+
+        model, out = self.cfg.pretrained_model_name_or_path, {}
+
+        def factory():
+            from .diffusion.text_hip import HipClipTextEncoder
+
+            return HipClipTextEncoder.from_pretrained(model, device=self.device)
+
+        encode_in_batches(prompts, local_tokenizer(model), factory, lambda p, pooled, hidden: out.__setitem__(p, hidden))
+        return torch.stack([out[p] for p in prompts])
 
     def load_from_cache(self, prompt: str) -> torch.Tensor:
         path = self._cache_path(prompt)
