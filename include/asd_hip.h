@@ -115,6 +115,30 @@ int asd_field_bwd(const asd_grid_meta* meta, const asd_field_cfg* cfg, const flo
                   const float* d_fd_grad, float* d_grid_params, float* dw1_density, float* dw2_density, float* dw1_feature, float* dw2_feature,
                   float* workspace, void* stream);
 
+/* normal_type "analytic" of the same field (implicit_volume.py:114-116, 181-190: normal = -F.normalize(torch.autograd.grad(density,
+ * points, create_graph=True))): the position gradient of the activated density from the encode's own corner values, no offset points.
+ * Outputs: sigma[n], features[n,C] and enc_save[n, L*F] exactly as asd_field_fwd, grad[n,3] (NULL or d sigma / d p, un-normalised),
+ * normal[n,3] = -grad / max(|grad|, 1e-12) (+grad / ... in ASD_FIELD_SDF mode, as the finite-difference normal).  The bias terms
+ * p / |p| are taken as 0 at |p| = 0 (the reference gives NaN there); outside the bounding box the position is clamped, so the encoding
+ * contributes no gradient.  L != 16, H != 64 or C not in {0, 3}: ASD_ERR_UNSUPPORTED. */
+int asd_field_analytic_fwd(const asd_grid_meta* meta, const asd_field_cfg* cfg, const float* grid_params,
+                           const float* w1_density, const float* w2_density, const float* w1_feature, const float* w2_feature,
+                           const float* points, int32_t n, float* sigma, float* features, float* grad /*[n,3], may be NULL*/,
+                           float* normal /*[n,3]*/, float* enc_save, void* stream);
+/* Its backward — the double backward autograd and tcnn give the reference (create_graph=True, implicit_volume.py:183-189): given
+ * dL/dsigma[n], dL/dfeatures[n,C], dL/dnormal[n,3], dL/dgrad[n,3] (any may be NULL) accumulate (+=) d_grid_params (atomic scatter) and
+ * the MLP weight gradients (first layers: the fixed-order reduction of asd_field_bwd over value rows and second-order rows; second layers:
+ * per-block partial sums, reduced in a fixed order).  No gradient with respect to the points.  `workspace` holds
+ * asd_field_analytic_bwd_workspace() floats.  `sigma` is in the signature as in asd_field_bwd; the pass recomputes the raw density
+ * from enc_save and does not read it. */
+int asd_field_analytic_bwd_workspace(const asd_field_cfg* cfg, int32_t n, int64_t* n_floats);
+int asd_field_analytic_bwd(const asd_grid_meta* meta, const asd_field_cfg* cfg, const float* grid_params,
+                           const float* w1_density, const float* w2_density, const float* w1_feature, const float* w2_feature,
+                           const float* points, const float* enc_save, const float* sigma /* forward output */, int32_t n,
+                           const float* d_sigma, const float* d_features, const float* d_normal, const float* d_grad /*NULL or [n,3]*/,
+                           float* d_grid_params, float* dw1_density, float* dw2_density, float* dw1_feature, float* dw2_feature,
+                           float* workspace, void* stream);
+
 /* The same fused field over a SAMPLED feature volume (`3DConv-net`, custom/amortized/models/geometry/stylegan_3dconv_net.py:244-346:
  * contract -> get_trilinear_feature -> VanillaMLP sdf / feature heads -> sdf + bias -> finite-difference sdf_grad): the encoding of a
  * point is the trilinear sample (F.grid_sample, zeros, align_corners = False) of voxel_cl [D][H][W][32] instead of the hash grid, the

@@ -160,6 +160,7 @@ _lib: Optional[C.CDLL] = None
 SYMBOLS = [
     "asd_grid_meta_init", "asd_hashgrid_fwd", "asd_hashgrid_bwd",
     "asd_field_density", "asd_field_fwd", "asd_field_bwd_workspace", "asd_field_bwd",
+    "asd_field_analytic_fwd", "asd_field_analytic_bwd_workspace", "asd_field_analytic_bwd",
     "asd_envmap_fwd", "asd_envmap_bwd",
     "asd_importance_resample", "asd_transmittance_cdf", "asd_merge_sorted", "asd_voxel_sample_fwd", "asd_voxel_sample_bwd", "asd_voxel_sample_bwd_rows",
     "asd_triplane_sample_fwd", "asd_triplane_sample_bwd", "asd_triplane_sample_bwd_rows", "asd_relayout_f32",

@@ -15,6 +15,7 @@
 
 #include "asd_common.h"
 #include "field_paged.h"
+#include "field_math.h"
 
 
 // ---------------------------------------------------------------------------------------------------
@@ -87,59 +88,7 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(const asd_grid_meta m
 // ---------------------------------------------------------------------------------------------------
 // field helpers
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float field_bias(const asd_field_cfg& c, float px, float py, float pz) {
-    const float r2 = px * px + py * py + pz * pz;
-    if (c.bias_mode == ASD_BIAS_BLOB_MAGIC3D) return c.blob_scale * (1.f - sqrtf(r2) / c.blob_std);
-    if (c.bias_mode == ASD_BIAS_BLOB_DREAMFUSION) return c.blob_scale * expf(-0.5f * r2 / (c.blob_std * c.blob_std));
-    if (c.bias_mode == ASD_BIAS_SPHERE) return sqrtf(r2) - c.bias_value;
-    return c.bias_value;
-}
-__device__ __forceinline__ float field_act(const asd_field_cfg& c, float raw) {
-    switch (c.activation) {
-        case ASD_ACT_SOFTPLUS: return asd_softplus(raw);
-        case ASD_ACT_EXP:
-        case ASD_ACT_TRUNC_EXP: return expf(raw);
-        default: return raw;
-    }
-}
-__device__ __forceinline__ float field_act_grad(const asd_field_cfg& c, float raw) {
-    switch (c.activation) {
-        case ASD_ACT_SOFTPLUS: return raw > 20.f ? 1.f : asd_sigmoid(raw);
-        case ASD_ACT_EXP: return expf(raw);
-        case ASD_ACT_TRUNC_EXP: return expf(fminf(raw, 15.f));
-        default: return 1.f;
-    }
-}
-
-// out = W2 . relu(W1 . enc), single output.  Weight addresses are wave-uniform (scalar loads).
-template <int NIN, int H>
-__device__ __forceinline__ float mlp1(const float* __restrict__ w1, const float* __restrict__ w2,
-                                      const float (&enc)[NIN]) {
-    float out = 0.f;
-#pragma unroll 4
-    for (int h = 0; h < H; ++h) {
-        float a = 0.f;
-#pragma unroll
-        for (int k = 0; k < NIN; ++k) a = fmaf(w1[h * NIN + k], enc[k], a);
-        out = fmaf(w2[h], fmaxf(a, 0.f), out);
-    }
-    return out;
-}
-template <int NIN, int H, int C>
-__device__ __forceinline__ void mlpC(const float* __restrict__ w1, const float* __restrict__ w2,
-                                     const float (&enc)[NIN], float (&out)[C]) {
-#pragma unroll
-    for (int o = 0; o < C; ++o) out[o] = 0.f;
-#pragma unroll 4
-    for (int h = 0; h < H; ++h) {
-        float a = 0.f;
-#pragma unroll
-        for (int k = 0; k < NIN; ++k) a = fmaf(w1[h * NIN + k], enc[k], a);
-        a = fmaxf(a, 0.f);
-#pragma unroll
-        for (int o = 0; o < C; ++o) out[o] = fmaf(w2[o * H + h], a, out[o]);
-    }
-}
+// field_bias, field_act, field_act_grad, mlp1, mlpC: field_math.h (shared with field_analytic.hip)
 
 // ENC = 1: the "encoding" of a point is the trilinear sample of a channel-last feature volume [D][H][W][2 L] — the generator-backed
 // geometries (3DConv-net: get_trilinear_feature = F.grid_sample(bilinear, zeros, align_corners = False),
@@ -931,6 +880,15 @@ struct field_bwd_layout {
     int64_t total;
 };
 static int field_wgrad_chunks(int64_t rows) { return (int)((rows + WG_ROWS - 1) / WG_ROWS); }      // blocks of field_wgrad_kernel
+// the same reduction for csrc/field_analytic.hip (field_math.h)
+int asd_field_wgrad_chunks(int64_t rows) { return field_wgrad_chunks(rows); }
+void asd_field_wgrad_launch(const float* da, const float* enc_a, const float* enc_b, int rows_a, int rows_total, float* slabs, hipStream_t s) {
+    hipLaunchKernelGGL((field_wgrad_kernel<128, 32>), dim3(field_wgrad_chunks(rows_total)), dim3(256), 0, s, da, enc_a, enc_b, rows_a, rows_total,
+                       (const int*)nullptr, rows_a, slabs);
+}
+void asd_field_slab_reduce_launch(const float* slabs, int n_slabs, int stride, int len, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3(asd_div_up(len, 32)), dim3(1024), 0, s, slabs, n_slabs, stride, len, out, (const int*)nullptr, 1);
+}
 static bool field_paged_on() {      // ASD_FIELD_PAGED=0: the transposed-lane atomics of asd_scatter_runs for every level, the A/B partner
     static const bool on = !(getenv("ASD_FIELD_PAGED") && atoi(getenv("ASD_FIELD_PAGED")) == 0);
     return on;

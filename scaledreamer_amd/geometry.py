@@ -170,6 +170,32 @@ class _FieldFn(torch.autograd.Function):
         return None, d_grid, dw[0], dw[1], dw[2], dw[3], None, None, None
 
 
+class _AnalyticFieldFn(torch.autograd.Function):
+    """sigma, features, normal = field(points) with normal = -grad sigma / |grad sigma| from the field's own position derivative
+    (normal_type "analytic"); backward is the double backward of the reference's autograd.grad(..., create_graph=True)."""
+
+    @staticmethod
+    def forward(ctx, points, grid, w1d, w2d, w1f, w2f, geom):
+        sigma, feats, normal, enc = ops.field_analytic_fwd(geom._meta, geom._fcfg, grid, w1d, w2d, w1f, w2f, points)
+        ctx.save_for_backward(points, grid, w1d, w2d, w1f, w2f, enc, sigma)
+        ctx.geom = geom
+        ctx.set_materialize_grads(False)
+        return sigma, feats, normal
+
+    @staticmethod
+    def backward(ctx, d_sigma, d_feats, d_normal):
+        points, grid, w1d, w2d, w1f, w2f, enc, sigma = ctx.saved_tensors
+        g = ctx.geom
+        d_grid = torch.zeros_like(grid)
+        if d_sigma is None and d_feats is None and d_normal is None:
+            return None, d_grid, torch.zeros_like(w1d), torch.zeros_like(w2d), torch.zeros_like(w1f), torch.zeros_like(w2f), None
+        dw = ops.field_analytic_bwd(g._meta, g._fcfg, grid, w1d, w2d, w1f, w2f, points, enc, sigma,
+                                    None if d_sigma is None else d_sigma.contiguous(),
+                                    None if d_feats is None else d_feats.contiguous(),
+                                    None if d_normal is None else d_normal.contiguous(), d_grid)
+        return None, d_grid, dw[0], dw[1], dw[2], dw[3], None
+
+
 @register("implicit-volume")
 class ImplicitVolume(BaseImplicitGeometry):
     @dataclass
@@ -209,6 +235,10 @@ class ImplicitVolume(BaseImplicitGeometry):
             self.normal_network = get_mlp(self.encoding.n_output_dims, 3, self.cfg.mlp_network_config)
         self._meta = self.encoding.encoding.encoding.meta
         self._fcfg = self._make_field_cfg()
+        if self.cfg.normal_type == "analytic" and self._fcfg is None:
+            raise NotImplementedError('normal_type "analytic" exists on the fused field kernels only (the composed route\'s encoding has no '
+                                      "derivative with respect to the position); this configuration is kept off them by: "
+                                      + ", ".join(self._fused_blockers))
 
     # ---- fused-kernel eligibility ---------------------------------------------------------------
     def _make_field_cfg(self) -> Optional[_lib.FieldCfg]:
@@ -221,14 +251,22 @@ class ImplicitVolume(BaseImplicitGeometry):
         else:
             bias, bias_value = _lib.ASD_BIAS_CONST, float(c.density_bias)
         mlp = c.mlp_network_config
-        ok = (
-            act >= 0 and bias >= 0 and self._meta.n_levels == 16 and self.encoding.n_output_dims == 32
-            and not self.encoding.include_xyz and isinstance(self.density_network, VanillaMLP)
-            and mlp.get("n_neurons") == 64 and mlp.get("n_hidden_layers") == 1
-            and mlp.get("output_activation", "none") in (None, "none") and c.n_feature_dims in (0, 3)
-            and c.normal_type in (None, "finite_difference") and c.n_input_dims == 3
-        )
-        if not ok:
+        # what keeps a configuration off the fused kernels, by name (configure() quotes them when normal_type "analytic" needs the kernels)
+        blockers = [why for cond, why in (
+            (act >= 0, f"density_activation {c.density_activation!r}"),
+            (bias >= 0, f"density_bias {c.density_bias!r}"),
+            (self._meta.n_levels == 16 and self.encoding.n_output_dims == 32, "a hash grid other than 16 levels x 2 features"),
+            (not self.encoding.include_xyz, "include_xyz"),
+            (isinstance(self.density_network, VanillaMLP), "a density network that is not a VanillaMLP"),
+            (mlp.get("n_neurons") == 64, f"n_neurons {mlp.get('n_neurons')} (the kernels are built for 64)"),
+            (mlp.get("n_hidden_layers") == 1, f"n_hidden_layers {mlp.get('n_hidden_layers')} (the kernels are built for 1)"),
+            (mlp.get("output_activation", "none") in (None, "none"), f"output_activation {mlp.get('output_activation')!r}"),
+            (c.n_feature_dims in (0, 3), f"n_feature_dims {c.n_feature_dims}"),
+            (c.normal_type in (None, "finite_difference", "analytic"), f"normal_type {c.normal_type!r}"),
+            (c.n_input_dims == 3, f"n_input_dims {c.n_input_dims}"),
+        ) if not cond]
+        self._fused_blockers = blockers
+        if blockers:
             return None
         f = _lib.FieldCfg()
         for d in range(3):
@@ -278,7 +316,15 @@ class ImplicitVolume(BaseImplicitGeometry):
         flat = points.reshape(-1, 3).contiguous().float()
         w1d, w2d, w1f, w2f = self._weights()
         grid = self.encoding.encoding.encoding.params
-        if torch.is_grad_enabled() and grid.requires_grad:
+        if output_normal and self.cfg.normal_type == "analytic":
+            if n_dev is not None:
+                raise ValueError('normal_type "analytic" takes no n_dev: the renderer path with a device-side sample count never asks for normals')
+            if torch.is_grad_enabled() and grid.requires_grad:
+                sigma, feats, normal = _AnalyticFieldFn.apply(flat, grid, w1d, w2d, w1f, w2f, self)
+            else:       # detached, as the reference detaches the normal when grad was disabled (implicit_volume.py:189-190)
+                sigma, feats, normal, _ = ops.field_analytic_fwd(self._meta, self._fcfg, grid.detach(), w1d.detach(), w2d.detach(),
+                                                                 w1f.detach(), w2f.detach(), flat)
+        elif torch.is_grad_enabled() and grid.requires_grad:
             sigma, feats, normal = _FieldFn.apply(flat, grid, w1d, w2d, w1f, w2f, self, bool(output_normal), n_dev)
         else:
             sigma, feats, normal, _ = ops.field_fwd(self._meta, self._fcfg, grid.detach(), w1d.detach(), w2d.detach(),

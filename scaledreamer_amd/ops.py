@@ -113,6 +113,45 @@ def field_bwd(meta, cfg: FieldCfg, grid, w1d, w2d, w1f, w2f, points, enc, sigma,
     return dw1d, dw2d, dw1f, dw2f
 
 
+def field_analytic_fwd(meta, cfg: FieldCfg, grid, w1d, w2d, w1f, w2f, points, want_grad: bool = False):
+    """normal_type "analytic": -> (sigma|sdf, features, normal, enc)   or, with want_grad, (sigma, features, normal, grad, enc);
+    grad is the un-normalised d sigma / d points."""
+    _need_cuda(grid, points)
+    points = _c(points)
+    n, dev = points.shape[0], points.device
+    sigma = torch.empty(n, device=dev, dtype=torch.float32)
+    feats = torch.empty((n, cfg.n_feature_dims), device=dev, dtype=torch.float32) if cfg.n_feature_dims > 0 else None
+    normal = torch.empty((n, 3), device=dev, dtype=torch.float32)
+    grad = torch.empty((n, 3), device=dev, dtype=torch.float32) if want_grad else None
+    enc = torch.empty((n, meta.n_levels * 2), device=dev, dtype=torch.float32)
+    check(lib().asd_field_analytic_fwd(C.byref(meta), C.byref(cfg), ptr(grid), ptr(w1d), ptr(w2d), ptr(w1f), ptr(w2f),
+                                       ptr(points), i32(n), ptr(sigma), ptr(feats), ptr(grad), ptr(normal), ptr(enc), stream()))
+    if want_grad:
+        return sigma, feats, normal, grad, enc
+    return sigma, feats, normal, enc
+
+
+def field_analytic_bwd(meta, cfg: FieldCfg, grid, w1d, w2d, w1f, w2f, points, enc, sigma, d_sigma, d_features, d_normal,
+                       d_grid: torch.Tensor, d_grad=None, dws=None):
+    """Accumulates into d_grid (atomics) and, when given, into dws = (dw1d, dw2d, dw1f, dw2f); returns (dw1d, dw2d, dw1f, dw2f)."""
+    points = _c(points)
+    n, dev = points.shape[0], points.device
+    nf = C.c_int64(0)
+    check(lib().asd_field_analytic_bwd_workspace(C.byref(cfg), i32(n), C.byref(nf)))
+    ws = torch.empty(nf.value, device=dev, dtype=torch.float32)
+    H, Cf = cfg.n_hidden, cfg.n_feature_dims
+    if dws is None:
+        dws = (torch.zeros((H, 32), device=dev, dtype=torch.float32), torch.zeros((1, H), device=dev, dtype=torch.float32),
+               torch.zeros((H, 32), device=dev, dtype=torch.float32) if Cf > 0 else None,
+               torch.zeros((Cf, H), device=dev, dtype=torch.float32) if Cf > 0 else None)
+    dw1d, dw2d, dw1f, dw2f = dws
+    k = _Keep()   # converted temporaries must outlive the launch (a freed block would be handed to the next conversion)
+    check(lib().asd_field_analytic_bwd(C.byref(meta), C.byref(cfg), ptr(grid), ptr(w1d), ptr(w2d), ptr(w1f), ptr(w2f),
+                                       ptr(points), ptr(enc), ptr(sigma), i32(n), k(d_sigma), k(d_features), k(d_normal),
+                                       k(d_grad), ptr(d_grid), ptr(dw1d), ptr(dw2d), ptr(dw1f), ptr(dw2f), ptr(ws), stream()))
+    return dw1d, dw2d, dw1f, dw2f
+
+
 # ---- background -------------------------------------------------------------------------------
 def envmap_fwd(meta, grid, w0, w1, w2, dirs) -> torch.Tensor:
     _need_cuda(grid, dirs)

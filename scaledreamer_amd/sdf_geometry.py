@@ -6,7 +6,8 @@ reference checkpoint loads).  Two routes, as `implicit-volume` (geometry.py):
              sphere bias -> forward-difference sdf_grad and normal in one kernel each way) — the same entries the hypernetwork geometry calls
   composed   tensor ops over the HIP hash-grid encoding: ellipsoid bias, finite_difference_laplacian, pred, a deformation network
 Not carried, each raising NotImplementedError with its reason: finite_difference_normal_eps "progressive" (no ProgressiveBandHashGrid),
-shape_init "mesh:..." (needs trimesh and pysdf), normal_type "analytic" (the HIP hash grid has no derivative w.r.t. the position).
+shape_init "mesh:..." (needs trimesh and pysdf), normal_type "analytic" (the derivative of the hash grid w.r.t. the position exists for
+`implicit-volume` only: asd_field_analytic_fwd / _bwd take ASD_FIELD_SDF cfgs, but this geometry is not wired to them).
 """
 from __future__ import annotations
 
@@ -63,8 +64,8 @@ class ImplicitSDF(BaseImplicitGeometry):
         if isinstance(c.shape_init, str) and c.shape_init.startswith("mesh:"):
             raise NotImplementedError('shape_init "mesh:..." needs trimesh and pysdf, which this port does not use')
         if c.normal_type == "analytic":
-            raise NotImplementedError('normal_type "analytic" needs the derivative of the hash grid w.r.t. the position, which the HIP '
-                                      'encoding does not provide; "finite_difference" is the fused route')
+            raise NotImplementedError('normal_type "analytic" needs the derivative of the hash grid w.r.t. the position, which only '
+                                      '`implicit-volume` is wired to (asd_field_analytic_fwd); "finite_difference" is the fused route here')
         self.encoding = get_encoding(c.n_input_dims, c.pos_encoding_config)
         self.sdf_network = get_mlp(self.encoding.n_output_dims, 1, c.mlp_network_config)
         if c.n_feature_dims > 0:
