@@ -66,7 +66,19 @@ static inline int asd_grid_for(int64_t n, int block) {
     return g;
 }
 
+// One thread per (point, level), level-major inside a 256-point tile: a wave stays on one level, so that level's table stays hot.
+// The flat index space covers whole tiles: asd_point_level_grid is the grid of a launch over it, asd_point_level the point and level
+// of thread t (i >= n in the padding of the last tile).
+static inline int asd_point_level_grid(int n, int L) { return asd_grid_for((int64_t)asd_div_up(n, 256) * 256 * L, 256) * 4; }
+
 #ifdef __HIPCC__
+__device__ __forceinline__ void asd_point_level(int64_t t, int L, int64_t& i, int& l) {
+    const int64_t tile = t / (256 * (int64_t)L);
+    const int r = (int)(t - tile * 256 * L);
+    l = r / 256;
+    i = tile * 256 + (r % 256);
+}
+
 // ---- wave64 primitives -------------------------------------------------------------------------
 __device__ __forceinline__ int asd_lane() { return (int)(threadIdx.x & 63); }
 
@@ -143,22 +155,81 @@ __device__ __forceinline__ float asd_silu_fast(float z) { return z * asd_sigmoid
 __device__ __forceinline__ float asd_silu_grad_s(float z, float s) { return fmaf(z, fmaf(-s, s, s), s); }
 __device__ __forceinline__ float asd_silu_grad_fast(float z) { return asd_silu_grad_s(z, asd_sigmoid_fast(z)); }
 
+// ---- a 16-byte aligned row of N floats <-> registers, as N / 4 float4 in ascending order --------
+template <int N>
+__device__ __forceinline__ void asd_row_load(const float* row, float (&v)[N]) {
+    static_assert(N % 4 == 0, "whole float4s");
+    const float4* src = reinterpret_cast<const float4*>(row);
+#pragma unroll
+    for (int q = 0; q < N / 4; ++q) {
+        const float4 t = src[q];
+        v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+    }
+}
+template <int N>
+__device__ __forceinline__ void asd_row_store(float* row, const float (&v)[N]) {
+    static_assert(N % 4 == 0, "whole float4s");
+    float4* dst = reinterpret_cast<float4*>(row);
+#pragma unroll
+    for (int q = 0; q < N / 4; ++q) dst[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+}
+
 // ---- hash grid ---------------------------------------------------------------------------------
 // Table index of integer corner (cx,cy,cz).  Branch-free so that the 8 gathers of a level stay in one
 // basic block: both the dense and the hashed index are formed and selected with a scalar condition.
 // Inputs are clamped to [0,1] by the callers (asd_unit), so a dense index is < 2*size and one
 // conditional subtract implements tcnn's `% hashmap_size`.
+#define ASD_HASH_P1 2654435761u      // tcnn's coherent prime hash: cx ^ cy * P1 ^ cz * P2
+#define ASD_HASH_P2 805459861u
 __device__ __forceinline__ uint32_t asd_grid_index(const asd_grid_meta& m, int l, uint32_t cx, uint32_t cy,
                                                    uint32_t cz) {
     const uint32_t res = m.resolution[l];
     const uint32_t size = m.size[l];
     uint32_t di = cx + cy * res + cz * res * res;
     di -= (di >= size) ? size : 0u;
-    const uint32_t hi = ((cx * 1u) ^ (cy * 2654435761u) ^ (cz * 805459861u)) & (size - 1u);
+    const uint32_t hi = ((cx * 1u) ^ (cy * ASD_HASH_P1) ^ (cz * ASD_HASH_P2)) & (size - 1u);
     return m.dense[l] ? di : hi;
 }
 // out-of-range rule of this implementation: clamp to the unit cube (tcnn wraps through an unsigned cast)
 __device__ __forceinline__ float asd_unit(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
+
+// One level's cell of a point of the unit cube: corner base, trilinear fractions, the level's scale.  THE cell arithmetic of the
+// library: the kernels that gather from or scatter into a hash grid find their cell, weights and indices here (two marked copies are
+// written out: the fine half of asd_scatter_runs below, pg_locate in field_paged.hip), and the results are compared bit for bit with
+// oracle/asd_oracle.c — a change here is a change there.
+struct asd_cell {
+    uint32_t cx, cy, cz;
+    float wx, wy, wz, s;
+};
+__device__ __forceinline__ asd_cell asd_cell_at(float s, float x, float y, float z) {
+    asd_cell q;
+    q.s = s;
+    const float px = fmaf(q.s, x, 0.5f), py = fmaf(q.s, y, 0.5f), pz = fmaf(q.s, z, 0.5f);
+    const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);
+    q.cx = (uint32_t)(int32_t)fx; q.cy = (uint32_t)(int32_t)fy; q.cz = (uint32_t)(int32_t)fz;
+    q.wx = px - fx; q.wy = py - fy; q.wz = pz - fz;
+    return q;
+}
+__device__ __forceinline__ asd_cell asd_cell_of(const asd_grid_meta& m, int l, float x, float y, float z) { return asd_cell_at(m.scale[l], x, y, z); }
+// corner c of a cell (bit 0: x, bit 1: y, bit 2: z): its table index ...
+__device__ __forceinline__ uint32_t asd_corner_index(const asd_grid_meta& m, int l, const asd_cell& q, int c) {
+    return asd_grid_index(m, l, q.cx + (c & 1), q.cy + ((c >> 1) & 1), q.cz + ((c >> 2) & 1));
+}
+// ... its trilinear weight (ax * ay) * az and the weight's derivatives with respect to the three fractions
+__device__ __forceinline__ void asd_corner_weight_grad(const asd_cell& q, int c, float& wt, float& dx, float& dy, float& dz) {
+    const float ax = (c & 1) ? q.wx : 1.f - q.wx;
+    const float ay = (c & 2) ? q.wy : 1.f - q.wy;
+    const float az = (c & 4) ? q.wz : 1.f - q.wz;
+    wt = ax * ay * az;
+    dx = (c & 1) ? ay * az : -(ay * az);
+    dy = (c & 2) ? ax * az : -(ax * az);
+    dz = (c & 4) ? ax * ay : -(ax * ay);
+}
+__device__ __forceinline__ float asd_corner_weight(const asd_cell& q, int c) {
+    float wt, dx, dy, dz;
+    asd_corner_weight_grad(q, c, wt, dx, dy, dz);
+    return wt;
+}
 
 // Gather-interpolate all levels of one point. enc[2L] stays in VGPRs (L is a compile-time constant).
 template <int L>
@@ -167,23 +238,16 @@ __device__ __forceinline__ void asd_encode(const asd_grid_meta& m, const float* 
     x = asd_unit(x); y = asd_unit(y); z = asd_unit(z);
 #pragma unroll
     for (int l = 0; l < L; ++l) {
-        const float s = m.scale[l];
-        const float px = fmaf(s, x, 0.5f), py = fmaf(s, y, 0.5f), pz = fmaf(s, z, 0.5f);
-        const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);
-        const uint32_t cx = (uint32_t)(int32_t)fx, cy = (uint32_t)(int32_t)fy, cz = (uint32_t)(int32_t)fz;
-        const float wx = px - fx, wy = py - fy, wz = pz - fz;
+        const asd_cell q = asd_cell_of(m, l, x, y, z);
         const float2* __restrict__ tab = reinterpret_cast<const float2*>(params) + m.offset[l];
         float2 v[8];
 #pragma unroll
         for (int c = 0; c < 8; ++c)  // issue the 8 independent 8-byte gathers first
-            v[c] = tab[asd_grid_index(m, l, cx + (c & 1), cy + ((c >> 1) & 1), cz + ((c >> 2) & 1))];
+            v[c] = tab[asd_corner_index(m, l, q, c)];
         float f0 = 0.f, f1 = 0.f;
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-            const float ax = (c & 1) ? wx : 1.f - wx;
-            const float ay = (c & 2) ? wy : 1.f - wy;
-            const float az = (c & 4) ? wz : 1.f - wz;
-            const float wt = ax * ay * az;
+            const float wt = asd_corner_weight(q, c);
             f0 = fmaf(wt, v[c].x, f0);
             f1 = fmaf(wt, v[c].y, f1);
         }
@@ -195,34 +259,7 @@ __device__ __forceinline__ void asd_encode(const asd_grid_meta& m, const float* 
     }
 }
 
-// Scatter-add d_enc into the table gradient (fp32 hardware atomics; build with -munsafe-fp-atomics).
-template <int L>
-__device__ __forceinline__ void asd_scatter(const asd_grid_meta& m, float* __restrict__ dparams, float x, float y,
-                                            float z, const float (&denc)[2 * L]) {
-    x = asd_unit(x); y = asd_unit(y); z = asd_unit(z);
-#pragma unroll
-    for (int l = 0; l < L; ++l) {
-        const float g0 = denc[2 * l], g1 = denc[2 * l + 1];
-        if (g0 == 0.f && g1 == 0.f) continue;
-        const float s = m.scale[l];
-        const float px = fmaf(s, x, 0.5f), py = fmaf(s, y, 0.5f), pz = fmaf(s, z, 0.5f);
-        const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);
-        const uint32_t cx = (uint32_t)(int32_t)fx, cy = (uint32_t)(int32_t)fy, cz = (uint32_t)(int32_t)fz;
-        const float wx = px - fx, wy = py - fy, wz = pz - fz;
-        float* __restrict__ tab = dparams + 2u * (size_t)m.offset[l];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const float ax = (c & 1) ? wx : 1.f - wx;
-            const float ay = (c & 2) ? wy : 1.f - wy;
-            const float az = (c & 4) ? wz : 1.f - wz;
-            const float wt = ax * ay * az;
-            const uint32_t idx = asd_grid_index(m, l, cx + (c & 1), cy + ((c >> 1) & 1), cz + ((c >> 2) & 1));
-            atomicAdd(tab + 2u * (size_t)idx, wt * g0);
-            atomicAdd(tab + 2u * (size_t)idx + 1, wt * g1);
-        }
-    }
-}
-// Scatter with wave-level run aggregation and request coalescing.
+// Scatter-add d_enc into the table gradient (fp32 hardware atomics; build with -munsafe-fp-atomics), with wave-level run aggregation and request coalescing.
 //
 // What gfx950 rate-limits is not the fp32 atomic but the REQUEST: the lanes of one atomic instruction that fall into the same
 // 64-byte block travel as one request, and the chip retires ~21 G requests/s whatever their width, scope or table size
@@ -258,14 +295,10 @@ __device__ __forceinline__ void asd_scatter_runs(const asd_grid_meta& m, float* 
 #pragma unroll
     for (int l = 0; l < (NAGG < L ? NAGG : L); ++l) {
         const float g0 = active ? denc[2 * l] : 0.f, g1 = active ? denc[2 * l + 1] : 0.f;
-        const float s = m.scale[l];
-        const float px = fmaf(s, x, 0.5f), py = fmaf(s, y, 0.5f), pz = fmaf(s, z, 0.5f);
-        const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);
-        const uint32_t cx = (uint32_t)(int32_t)fx, cy = (uint32_t)(int32_t)fy, cz = (uint32_t)(int32_t)fz;
-        const float wx = px - fx, wy = py - fy, wz = pz - fz;
+        const asd_cell q = asd_cell_of(m, l, x, y, z);
         float* __restrict__ tab = (l < NPRIV ? priv : dparams) + 2u * (size_t)m.offset[l];
         const uint32_t res = m.resolution[l];
-        const uint32_t key = active ? cx + (cy + cz * res) * res : 0xFFFFFFFFu - (uint32_t)lane;
+        const uint32_t key = active ? q.cx + (q.cy + q.cz * res) * res : 0xFFFFFFFFu - (uint32_t)lane;
         const uint32_t prev = __shfl_up(key, 1, 64);
         const bool head = lane == 0 || prev != key;
         const unsigned long long hm = __ballot(head);
@@ -273,7 +306,7 @@ __device__ __forceinline__ void asd_scatter_runs(const asd_grid_meta& m, float* 
         float v[16];
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-            const float wt = ((c & 1) ? wx : 1.f - wx) * ((c & 2) ? wy : 1.f - wy) * ((c & 4) ? wz : 1.f - wz);
+            const float wt = asd_corner_weight(q, c);
             v[2 * c] = wt * g0;
             v[2 * c + 1] = wt * g1;
         }
@@ -293,7 +326,7 @@ __device__ __forceinline__ void asd_scatter_runs(const asd_grid_meta& m, float* 
         const bool self_f1 = issue && (lane == 63 || ((hm >> (lane + 1)) & 1ull));
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-            const uint32_t idx = asd_grid_index(m, l, cx + (c & 1), cy + ((c >> 1) & 1), cz + ((c >> 2) & 1));
+            const uint32_t idx = asd_corner_index(m, l, q, c);
             const float f1_prev = __shfl_up(v[2 * c + 1], 1, 64);
             // the carrier sits in the head's cell, so it forms the same idx
             const float val = issue ? v[2 * c] : f1_prev;
@@ -315,6 +348,8 @@ __device__ __forceinline__ void asd_scatter_runs(const asd_grid_meta& m, float* 
             const float ga = __shfl(denc[2 * l], src, 64), gb = __shfl(denc[2 * l + 1], src, 64);
             const float g = ft ? gb : ga;
             if (!sact || g == 0.f) continue;
+            // asd_cell_of's arithmetic with this lane's x corner added to cx.  Written out, not built on the helper: with it (three forms
+            // tried) hipcc schedules every kernel that scatters differently (tools/asm_same.py) — keep the two in step
             const float s = m.scale[l];
             const float px = fmaf(s, sx, 0.5f), py = fmaf(s, sy, 0.5f), pz = fmaf(s, sz, 0.5f);
             const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);

@@ -27,27 +27,20 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const asd_grid_meta m
     const int L = (int)m.n_levels;
     const int64_t total = (int64_t)((n + 255) / 256) * 256 * L;  // whole 256-point tiles, level-major inside
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        // level-major inside a block-sized tile of points keeps one level's table hot per wave
-        const int64_t tile = t / (256 * (int64_t)L);
-        const int r = (int)(t - tile * 256 * L);
-        const int l = r / 256;
-        const int64_t i = tile * 256 + (r % 256);
+        int64_t i;
+        int l;
+        asd_point_level(t, L, i, l);
         if (i >= n) continue;
         const float s = m.scale[l];
-        const float px = fmaf(s, asd_unit(x[3 * i]), 0.5f), py = fmaf(s, asd_unit(x[3 * i + 1]), 0.5f),
-                    pz = fmaf(s, asd_unit(x[3 * i + 2]), 0.5f);
-        const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);
-        const uint32_t cx = (uint32_t)(int32_t)fx, cy = (uint32_t)(int32_t)fy, cz = (uint32_t)(int32_t)fz;
-        const float wx = px - fx, wy = py - fy, wz = pz - fz;
+        const asd_cell q = asd_cell_at(s, asd_unit(x[3 * i]), asd_unit(x[3 * i + 1]), asd_unit(x[3 * i + 2]));
         const float2* __restrict__ tab = reinterpret_cast<const float2*>(params) + m.offset[l];
         float2 v[8];
 #pragma unroll
-        for (int c = 0; c < 8; ++c)
-            v[c] = tab[asd_grid_index(m, l, cx + (c & 1), cy + ((c >> 1) & 1), cz + ((c >> 2) & 1))];
+        for (int c = 0; c < 8; ++c) v[c] = tab[asd_corner_index(m, l, q, c)];
         float f0 = 0.f, f1 = 0.f;
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-            const float wt = ((c & 1) ? wx : 1.f - wx) * ((c & 2) ? wy : 1.f - wy) * ((c & 4) ? wz : 1.f - wz);
+            const float wt = asd_corner_weight(q, c);
             f0 = fmaf(wt, v[c].x, f0);
             f1 = fmaf(wt, v[c].y, f1);
         }
@@ -61,24 +54,19 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(const asd_grid_meta m
     const int L = (int)m.n_levels;
     const int64_t total = (int64_t)((n + 255) / 256) * 256 * L;  // whole 256-point tiles, level-major inside
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t tile = t / (256 * (int64_t)L);
-        const int r = (int)(t - tile * 256 * L);
-        const int l = r / 256;
-        const int64_t i = tile * 256 + (r % 256);
+        int64_t i;
+        int l;
+        asd_point_level(t, L, i, l);
         if (i >= n) continue;
         const float2 g = reinterpret_cast<const float2*>(dout)[i * L + l];
         if (g.x == 0.f && g.y == 0.f) continue;
         const float s = m.scale[l];
-        const float px = fmaf(s, asd_unit(x[3 * i]), 0.5f), py = fmaf(s, asd_unit(x[3 * i + 1]), 0.5f),
-                    pz = fmaf(s, asd_unit(x[3 * i + 2]), 0.5f);
-        const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);
-        const uint32_t cx = (uint32_t)(int32_t)fx, cy = (uint32_t)(int32_t)fy, cz = (uint32_t)(int32_t)fz;
-        const float wx = px - fx, wy = py - fy, wz = pz - fz;
+        const asd_cell q = asd_cell_at(s, asd_unit(x[3 * i]), asd_unit(x[3 * i + 1]), asd_unit(x[3 * i + 2]));
         float* __restrict__ tab = dparams + 2u * (size_t)m.offset[l];
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-            const float wt = ((c & 1) ? wx : 1.f - wx) * ((c & 2) ? wy : 1.f - wy) * ((c & 4) ? wz : 1.f - wz);
-            const uint32_t idx = asd_grid_index(m, l, cx + (c & 1), cy + ((c >> 1) & 1), cz + ((c >> 2) & 1));
+            const float wt = asd_corner_weight(q, c);
+            const uint32_t idx = asd_corner_index(m, l, q, c);
             atomicAdd(tab + 2u * (size_t)idx, wt * g.x);
             atomicAdd(tab + 2u * (size_t)idx + 1, wt * g.y);
         }
@@ -176,11 +164,7 @@ __global__ __launch_bounds__(256, 4) void field_fwd_kernel(const asd_grid_meta m
         const float raw = field_raw<L, H, ENC>(m, c, grid, w1d, w2d, px, py, pz, enc);
         const float s = field_act(c, raw);
         sigma[i] = s;
-        if (enc_save) {
-            float4* dst = reinterpret_cast<float4*>(enc_save + (size_t)i * 2 * L);
-#pragma unroll
-            for (int q = 0; q < L / 2; ++q) dst[q] = make_float4(enc[4 * q], enc[4 * q + 1], enc[4 * q + 2], enc[4 * q + 3]);
-        }
+        if (enc_save) asd_row_store(enc_save + (size_t)i * 2 * L, enc);
         if (features) {
             float f[C];
             mlpC<2 * L, H, C>(w1f, w2f, enc, f);
@@ -281,12 +265,7 @@ __global__ __launch_bounds__(256, ASD_FIELD_BWD_BLOCKS) void field_bwd_sample_ke
         px = points[3 * i]; py = points[3 * i + 1]; pz = points[3 * i + 2];
         s = sigma[i];
         ds = d_sigma ? d_sigma[i] : 0.f;
-        const float4* src = reinterpret_cast<const float4*>(enc_save + (size_t)i * NIN);
-#pragma unroll
-        for (int q = 0; q < NIN / 4; ++q) {
-            const float4 v = src[q];
-            enc[4 * q] = v.x; enc[4 * q + 1] = v.y; enc[4 * q + 2] = v.z; enc[4 * q + 3] = v.w;
-        }
+        asd_row_load(enc_save + (size_t)i * NIN, enc);
     }
     const float bx = c.bbox_max[0] - c.bbox_min[0], by = c.bbox_max[1] - c.bbox_min[1], bz = c.bbox_max[2] - c.bbox_min[2];
 
@@ -372,14 +351,7 @@ __global__ __launch_bounds__(256, ASD_FIELD_BWD_BLOCKS) void field_bwd_sample_ke
 #pragma unroll
         for (int k = 0; k < NIN; ++k) denc[k] = 0.f;
         if constexpr (PRE) {
-            if (active) {
-                const float4* src = reinterpret_cast<const float4*>(denc_pre + (size_t)i * NIN);
-#pragma unroll
-                for (int q = 0; q < NIN / 4; ++q) {
-                    const float4 v = src[q];
-                    denc[4 * q] = v.x; denc[4 * q + 1] = v.y; denc[4 * q + 2] = v.z; denc[4 * q + 3] = v.w;
-                }
-            }
+            if (active) asd_row_load(denc_pre + (size_t)i * NIN, denc);
         } else {
         float* da_row = da_out + row * (2 * H);
         // ---- density MLP: da_h = draw * w2[h] * [a_h > 0] ------------------------------------------------------
@@ -810,8 +782,7 @@ int asd_hashgrid_fwd(const asd_grid_meta* meta, const float* params, const float
                      void* stream) {
     if (n == 0) return ASD_OK;
     ASD_CHECK_ARG(meta && params && x && out && n > 0, "null argument");
-    const int64_t total = (int64_t)asd_div_up(n, 256) * 256 * meta->n_levels;
-    hipLaunchKernelGGL(hashgrid_fwd_kernel, dim3(asd_grid_for(total, 256) * 4), dim3(256), 0, (hipStream_t)stream, *meta,
+    hipLaunchKernelGGL(hashgrid_fwd_kernel, dim3(asd_point_level_grid(n, (int)meta->n_levels)), dim3(256), 0, (hipStream_t)stream, *meta,
                        params, x, n, out);
     ASD_LAUNCH_CHECK();
     return ASD_OK;
@@ -821,17 +792,16 @@ int asd_hashgrid_bwd(const asd_grid_meta* meta, const float* x, const float* dou
                      void* stream) {
     if (n == 0) return ASD_OK;
     ASD_CHECK_ARG(meta && x && dout && dparams && n > 0, "null argument");
-    const int64_t total = (int64_t)asd_div_up(n, 256) * 256 * meta->n_levels;
-    hipLaunchKernelGGL(hashgrid_bwd_kernel, dim3(asd_grid_for(total, 256) * 4), dim3(256), 0, (hipStream_t)stream, *meta,
+    hipLaunchKernelGGL(hashgrid_bwd_kernel, dim3(asd_point_level_grid(n, (int)meta->n_levels)), dim3(256), 0, (hipStream_t)stream, *meta,
                        x, dout, n, dparams);
     ASD_LAUNCH_CHECK();
     return ASD_OK;
 }
 
-static int field_supported(const asd_grid_meta* m, const asd_field_cfg* c) {
+int asd_field_supported(const asd_grid_meta* m, const asd_field_cfg* c, const char* what) {
     if (m->n_levels != 16 || c->n_hidden != 64 || !(c->n_feature_dims == 3 || c->n_feature_dims == 0)) {
-        asd_set_error("field kernels are built for 16 levels x 2 features, 64 hidden units, 0/3 feature dims "
-                      "(got %u levels, %d hidden, %d feature dims)", m->n_levels, c->n_hidden, c->n_feature_dims);
+        asd_set_error("%s kernels are built for 16 levels x 2 features, 64 hidden units, 0/3 feature dims "
+                      "(got %u levels, %d hidden, %d feature dims)", what, m->n_levels, c->n_hidden, c->n_feature_dims);
         return 0;
     }
     return 1;
@@ -842,7 +812,7 @@ int asd_field_density(const asd_grid_meta* meta, const asd_field_cfg* cfg, const
                       const int32_t* n_dev, float* sigma, void* stream) {
     if (n == 0) return ASD_OK;
     ASD_CHECK_ARG(meta && cfg && grid_params && w1_density && w2_density && points && sigma && n > 0, "null argument");
-    if (!field_supported(meta, cfg)) return ASD_ERR_UNSUPPORTED;
+    if (!asd_field_supported(meta, cfg, "field")) return ASD_ERR_UNSUPPORTED;
     hipLaunchKernelGGL((field_density_kernel<16, 64>), dim3(asd_grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
                        *meta, *cfg, grid_params, w1_density, w2_density, points, n, n_dev, sigma);
     ASD_LAUNCH_CHECK();
@@ -855,7 +825,7 @@ int asd_field_fwd(const asd_grid_meta* meta, const asd_field_cfg* cfg, const flo
                   float* features, float* normal, float* fd_grad, float* enc_save, void* stream) {
     if (n == 0) return ASD_OK;
     ASD_CHECK_ARG(meta && cfg && grid_params && w1_density && w2_density && points && sigma && n > 0, "null argument");
-    if (!field_supported(meta, cfg)) return ASD_ERR_UNSUPPORTED;
+    if (!asd_field_supported(meta, cfg, "field")) return ASD_ERR_UNSUPPORTED;
     ASD_CHECK_ARG(cfg->n_feature_dims == 0 || !features || (w1_feature && w2_feature), "feature weights missing");
     hipLaunchKernelGGL((field_fwd_kernel<16, 64, 3>), dim3(asd_grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
                        *meta, *cfg, grid_params, w1_density, w2_density, w1_feature, w2_feature, points, n, n_dev,
@@ -882,12 +852,23 @@ struct field_bwd_layout {
 static int field_wgrad_chunks(int64_t rows) { return (int)((rows + WG_ROWS - 1) / WG_ROWS); }      // blocks of field_wgrad_kernel
 // the same reduction for csrc/field_analytic.hip (field_math.h)
 int asd_field_wgrad_chunks(int64_t rows) { return field_wgrad_chunks(rows); }
-void asd_field_wgrad_launch(const float* da, const float* enc_a, const float* enc_b, int rows_a, int rows_total, float* slabs, hipStream_t s) {
-    hipLaunchKernelGGL((field_wgrad_kernel<128, 32>), dim3(field_wgrad_chunks(rows_total)), dim3(256), 0, s, da, enc_a, enc_b, rows_a, rows_total,
-                       (const int*)nullptr, rows_a, slabs);
-}
 void asd_field_slab_reduce_launch(const float* slabs, int n_slabs, int stride, int len, float* out, hipStream_t s) {
     hipLaunchKernelGGL(slab_reduce_kernel, dim3(asd_div_up(len, 32)), dim3(1024), 0, s, slabs, n_slabs, stride, len, out, (const int*)nullptr, 1);
+}
+// The first-layer weight-gradient tail of every field backward (field_math.h).  ONE n_slabs — the blocks of the launch that wrote or writes
+// the slabs — sizes the launch and both reductions.
+void asd_field_wgrad_tail(const float* da, const float* enc_a, const float* enc_b, int rows_a, int rows_total, const int* n_dev, bool slabs_written,
+                          float* slabs, int n_slabs, float* dw1_density, float* dw1_feature, hipStream_t s) {
+    // the matrix-pipe pass has written every block's slab; of field_wgrad_kernel's, with a device-side count and centre rows only, the slabs of
+    // dead chunks are neither written nor summed
+    const int* live = (!slabs_written && n_dev && rows_total == rows_a) ? n_dev : nullptr;
+    if (!slabs_written)
+        hipLaunchKernelGGL((field_wgrad_kernel<128, 32>), dim3(n_slabs), dim3(256), 0, s, da, enc_a, enc_b, rows_a, rows_total, n_dev, rows_a, slabs);
+    // slab layout [h < 64: density | h >= 64: feature][k]; both halves are contiguous H*32 blocks
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3(asd_div_up(64 * 32, 32)), dim3(1024), 0, s, slabs, n_slabs, 128 * 32, 64 * 32, dw1_density, live, WG_ROWS);
+    if (dw1_feature)
+        hipLaunchKernelGGL(slab_reduce_kernel, dim3(asd_div_up(64 * 32, 32)), dim3(1024), 0, s, slabs + 64 * 32, n_slabs, 128 * 32, 64 * 32, dw1_feature,
+                           live, WG_ROWS);
 }
 static bool field_paged_on() {      // ASD_FIELD_PAGED=0: the transposed-lane atomics of asd_scatter_runs for every level, the A/B partner
     static const bool on = !(getenv("ASD_FIELD_PAGED") && atoi(getenv("ASD_FIELD_PAGED")) == 0);
@@ -929,7 +910,7 @@ int asd_field_bwd(const asd_grid_meta* meta, const asd_field_cfg* cfg, const flo
     ASD_CHECK_ARG(meta && cfg && grid_params && w1_density && w2_density && points && enc_save && sigma &&
                       d_grid_params && dw1_density && dw2_density && workspace && n > 0,
                   "null argument");
-    if (!field_supported(meta, cfg)) return ASD_ERR_UNSUPPORTED;
+    if (!asd_field_supported(meta, cfg, "field")) return ASD_ERR_UNSUPPORTED;
     ASD_CHECK_ARG(cfg->n_feature_dims == 3 || !d_features, "d_features given but no feature network");
     ASD_CHECK_ARG(cfg->n_feature_dims == 0 || (dw1_feature && dw2_feature && w1_feature && w2_feature), "feature gradients missing");
     hipStream_t s = (hipStream_t)stream;
@@ -986,16 +967,7 @@ int asd_field_bwd(const asd_grid_meta* meta, const asd_field_cfg* cfg, const flo
         if (rc != ASD_OK) return rc;
     }
     ASD_PROBE_STOP(s);
-    // the matrix-pipe pass has written every block's slab; of field_wgrad_kernel's, with a device-side count and centre rows only, the slabs of
-    // dead chunks are neither written nor summed
-    const int* live = (!L.mfma && n_dev && rows == (int64_t)n) ? n_dev : nullptr;
-    if (!L.mfma) hipLaunchKernelGGL((field_wgrad_kernel<128, 32>), dim3(n_slabs), block, 0, s, da, enc_save, enc_fd, n, (int)rows, n_dev, n, slabs);
-    // slab layout [h < 64: density | h >= 64: feature][k]; both halves are contiguous H*32 blocks
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(asd_div_up(64 * 32, 32)), dim3(1024), 0, s, slabs, n_slabs, 128 * 32, 64 * 32,
-                       dw1_density, live, WG_ROWS);
-    if (cfg->n_feature_dims == 3)
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(asd_div_up(64 * 32, 32)), dim3(1024), 0, s, slabs + 64 * 32, n_slabs, 128 * 32,
-                           64 * 32, dw1_feature, live, WG_ROWS);
+    asd_field_wgrad_tail(da, enc_save, enc_fd, n, (int)rows, n_dev, L.mfma, slabs, n_slabs, dw1_density, cfg->n_feature_dims == 3 ? dw1_feature : nullptr, s);
     ASD_LAUNCH_CHECK();
     return ASD_OK;
 }
@@ -1064,11 +1036,7 @@ int asd_voxfield_bwd(const float* voxel_cl, int32_t D, int32_t H, int32_t W, int
 #undef ASD_VOXFIELD_BWD_LAUNCH
     const int rc = asd_voxel_sample_bwd_rows(denc, D, H, W, C, pts, (int32_t)rows, d_voxel_cl, 128, stream);     // += (atomics), amortized.hip
     if (rc != ASD_OK) return rc;
-    hipLaunchKernelGGL((field_wgrad_kernel<128, 32>), dim3(n_slabs), block, 0, s, da, enc_save, enc_fd, n, (int)rows, (const int*)nullptr, n, slabs);
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(asd_div_up(64 * 32, 32)), dim3(1024), 0, s, slabs, n_slabs, 128 * 32, 64 * 32, dw1_sdf, (const int*)nullptr, WG_ROWS);
-    if (cfg->n_feature_dims == 3)
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(asd_div_up(64 * 32, 32)), dim3(1024), 0, s, slabs + 64 * 32, n_slabs, 128 * 32, 64 * 32, dw1_feature,
-                           (const int*)nullptr, WG_ROWS);
+    asd_field_wgrad_tail(da, enc_save, enc_fd, n, (int)rows, nullptr, false, slabs, n_slabs, dw1_sdf, cfg->n_feature_dims == 3 ? dw1_feature : nullptr, s);
     ASD_LAUNCH_CHECK();
     return ASD_OK;
 }

@@ -82,31 +82,6 @@ __device__ __forceinline__ float an_again(float v) {
     return v;
 }
 
-// one level's cell of a point of the unit cube: corner base, trilinear fractions (asd_encode's arithmetic)
-struct an_cell {
-    uint32_t cx, cy, cz;
-    float wx, wy, wz, s;
-};
-__device__ __forceinline__ an_cell an_cell_of(const asd_grid_meta& m, int l, float x, float y, float z) {
-    an_cell q;
-    q.s = m.scale[l];
-    const float px = fmaf(q.s, x, 0.5f), py = fmaf(q.s, y, 0.5f), pz = fmaf(q.s, z, 0.5f);
-    const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);
-    q.cx = (uint32_t)(int32_t)fx; q.cy = (uint32_t)(int32_t)fy; q.cz = (uint32_t)(int32_t)fz;
-    q.wx = px - fx; q.wy = py - fy; q.wz = pz - fz;
-    return q;
-}
-// the weight of corner c and its derivatives with respect to the three fractions
-__device__ __forceinline__ void an_corner(const an_cell& q, int c, float& wt, float& dx, float& dy, float& dz) {
-    const float ax = (c & 1) ? q.wx : 1.f - q.wx;
-    const float ay = (c & 2) ? q.wy : 1.f - q.wy;
-    const float az = (c & 4) ? q.wz : 1.f - q.wz;
-    wt = ax * ay * az;
-    dx = (c & 1) ? ay * az : -(ay * az);
-    dy = (c & 2) ? ax * az : -(ax * az);
-    dz = (c & 4) ? ax * ay : -(ax * ay);
-}
-
 // gu_k = sum_j g_j D[j][k]; x, y, z already in the unit cube.  gs: this thread's column of the block's LDS copy of g (stride 256 floats), so
 // the level loop stays a loop (fully unrolled, with g in registers, hipcc forms the cells of all 16 levels ahead of the gathers and spills them).
 template <int L>
@@ -115,18 +90,17 @@ __device__ __forceinline__ void an_pos_grad(const asd_grid_meta& m, const float*
     gu[0] = gu[1] = gu[2] = 0.f;
 #pragma unroll 2
     for (int l = 0; l < L; ++l) {
-        const an_cell q = an_cell_of(m, l, x, y, z);
+        const asd_cell q = asd_cell_of(m, l, x, y, z);
         const float2* __restrict__ tab = reinterpret_cast<const float2*>(params) + m.offset[l];
         float2 v[8];
 #pragma unroll
-        for (int c = 0; c < 8; ++c)
-            v[c] = tab[asd_grid_index(m, l, q.cx + (c & 1), q.cy + ((c >> 1) & 1), q.cz + ((c >> 2) & 1))];
+        for (int c = 0; c < 8; ++c) v[c] = tab[asd_corner_index(m, l, q, c)];
         const float ga = gs[(2 * l) * 256], gb = gs[(2 * l + 1) * 256];
         float dx = 0.f, dy = 0.f, dz = 0.f;
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
             float wt, ex, ey, ez;
-            an_corner(q, c, wt, ex, ey, ez);
+            asd_corner_weight_grad(q, c, wt, ex, ey, ez);
             const float gv = fmaf(ga, v[c].x, gb * v[c].y);
             dx = fmaf(ex, gv, dx); dy = fmaf(ey, gv, dy); dz = fmaf(ez, gv, dz);
         }
@@ -140,17 +114,16 @@ __device__ __forceinline__ void an_pos_grad_t(const asd_grid_meta& m, const floa
                                               float gh0, float gh1, float gh2, float* ts) {
 #pragma unroll 2
     for (int l = 0; l < L; ++l) {
-        const an_cell q = an_cell_of(m, l, x, y, z);
+        const asd_cell q = asd_cell_of(m, l, x, y, z);
         const float2* __restrict__ tab = reinterpret_cast<const float2*>(params) + m.offset[l];
         float2 v[8];
 #pragma unroll
-        for (int c = 0; c < 8; ++c)
-            v[c] = tab[asd_grid_index(m, l, q.cx + (c & 1), q.cy + ((c >> 1) & 1), q.cz + ((c >> 2) & 1))];
+        for (int c = 0; c < 8; ++c) v[c] = tab[asd_corner_index(m, l, q, c)];
         float t0 = 0.f, t1 = 0.f;
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
             float wt, ex, ey, ez;
-            an_corner(q, c, wt, ex, ey, ez);
+            asd_corner_weight_grad(q, c, wt, ex, ey, ez);
             const float dwt = q.s * fmaf(gh0, ex, fmaf(gh1, ey, gh2 * ez));
             t0 = fmaf(dwt, v[c].x, t0);
             t1 = fmaf(dwt, v[c].y, t1);
@@ -181,11 +154,7 @@ __global__ __launch_bounds__(256, 4) void field_analytic_fwd_kernel(const asd_gr
         asd_encode<L>(m, grid, ux, uy, uz, enc);
         const float raw = an_mlp1_g<NIN, H>(w1d, w2d, enc, g) + field_bias(c, px, py, pz);
         sigma[i] = field_act(c, raw);
-        if (enc_save) {
-            float4* dst = reinterpret_cast<float4*>(enc_save + (size_t)i * NIN);
-#pragma unroll
-            for (int q = 0; q < NIN / 4; ++q) dst[q] = make_float4(enc[4 * q], enc[4 * q + 1], enc[4 * q + 2], enc[4 * q + 3]);
-        }
+        if (enc_save) asd_row_store(enc_save + (size_t)i * NIN, enc);
         if (C > 0 && features) {
             float f[C > 0 ? C : 1];
             mlpC<NIN, H, (C > 0 ? C : 1)>(w1f, w2f, enc, f);
@@ -242,15 +211,11 @@ __global__ __launch_bounds__(256, 2) void field_analytic_bwd_sample_kernel(
     float enc[NIN];
 #pragma unroll
     for (int k = 0; k < NIN; ++k) enc[k] = 0.f;
-    const float4* enc_src = reinterpret_cast<const float4*>(enc_save + (size_t)(active ? i : 0) * NIN);
+    const float* const enc_row = enc_save + (size_t)(active ? i : 0) * NIN;
     if (active) {
         px = points[3 * (size_t)i]; py = points[3 * (size_t)i + 1]; pz = points[3 * (size_t)i + 2];
         ds = d_sigma ? d_sigma[i] : 0.f;
-#pragma unroll
-        for (int q = 0; q < NIN / 4; ++q) {
-            const float4 v = enc_src[q];
-            enc[4 * q] = v.x; enc[4 * q + 1] = v.y; enc[4 * q + 2] = v.z; enc[4 * q + 3] = v.w;
-        }
+        asd_row_load(enc_row, enc);
     }
     const float ux = (px - c.bbox_min[0]) / bx, uy = (py - c.bbox_min[1]) / by, uz = (pz - c.bbox_min[2]) / bz;
     float* const da_row = da + (size_t)(active ? i : 0) * (2 * H);
@@ -356,21 +321,11 @@ __global__ __launch_bounds__(256, 2) void field_analytic_bwd_sample_kernel(
         an_pos_grad_t<L>(m, grid, an_again(x), an_again(y), an_again(z), gh0, gh1, gh2, gs);
 #pragma unroll
         for (int k = 0; k < NIN; ++k) t[k] = gs[k * 256];
-        if (active) {
-            float4* dt = reinterpret_cast<float4*>(t_out + (size_t)i * NIN);
-#pragma unroll
-            for (int q = 0; q < NIN / 4; ++q) dt[q] = make_float4(t[4 * q], t[4 * q + 1], t[4 * q + 2], t[4 * q + 3]);
-        }
+        if (active) asd_row_store(t_out + (size_t)i * NIN, t);
     }
 
     // ---- density MLP hidden gradients: both rows, and dw2_h = sum_i draw relu(a_h) + m_h (W1 t)_h -------------------------------
-    if (active) {
-#pragma unroll
-        for (int q = 0; q < NIN / 4; ++q) {
-            const float4 v = enc_src[q];
-            enc[4 * q] = v.x; enc[4 * q + 1] = v.y; enc[4 * q + 2] = v.z; enc[4 * q + 3] = v.w;
-        }
-    }
+    if (active) asd_row_load(enc_row, enc);
 #pragma unroll 1
     for (int h0 = 0; h0 < H; h0 += 4) {
         float dav[4], dav2[4];
@@ -414,10 +369,9 @@ __global__ __launch_bounds__(256) void field_analytic_scatter_kernel(const asd_g
     const int L = (int)m.n_levels;
     const int64_t total = (int64_t)((n + 255) / 256) * 256 * L;
     for (int64_t tt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; tt < total; tt += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t tile = tt / (256 * (int64_t)L);
-        const int r = (int)(tt - tile * 256 * L);
-        const int l = r / 256;
-        const int64_t i = tile * 256 + (r % 256);
+        int64_t i;
+        int l;
+        asd_point_level(tt, L, i, l);
         if (i >= n) continue;
         const float2 de = reinterpret_cast<const float2*>(denc)[i * L + l];
         const float2 gg = reinterpret_cast<const float2*>(g)[i * L + l];
@@ -427,14 +381,14 @@ __global__ __launch_bounds__(256) void field_analytic_scatter_kernel(const asd_g
         const float x = asd_unit((points[3 * i] - c.bbox_min[0]) / (c.bbox_max[0] - c.bbox_min[0]));
         const float y = asd_unit((points[3 * i + 1] - c.bbox_min[1]) / (c.bbox_max[1] - c.bbox_min[1]));
         const float z = asd_unit((points[3 * i + 2] - c.bbox_min[2]) / (c.bbox_max[2] - c.bbox_min[2]));
-        const an_cell q = an_cell_of(m, l, x, y, z);
+        const asd_cell q = asd_cell_of(m, l, x, y, z);
         float* __restrict__ tab = d_grid + 2u * (size_t)m.offset[l];
 #pragma unroll
         for (int cn = 0; cn < 8; ++cn) {
             float wt, ex, ey, ez;
-            an_corner(q, cn, wt, ex, ey, ez);
+            asd_corner_weight_grad(q, cn, wt, ex, ey, ez);
             const float dwt = q.s * fmaf(h.x, ex, fmaf(h.y, ey, h.z * ez));
-            const uint32_t idx = asd_grid_index(m, l, q.cx + (cn & 1), q.cy + ((cn >> 1) & 1), q.cz + ((cn >> 2) & 1));
+            const uint32_t idx = asd_corner_index(m, l, q, cn);
             atomicAdd(tab + 2u * (size_t)idx, fmaf(dwt, gg.x, wt * de.x));
             atomicAdd(tab + 2u * (size_t)idx + 1, fmaf(dwt, gg.y, wt * de.y));
         }
@@ -444,15 +398,6 @@ __global__ __launch_bounds__(256) void field_analytic_scatter_kernel(const asd_g
 // ---------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------
-static int analytic_supported(const asd_grid_meta* m, const asd_field_cfg* c) {
-    if (m->n_levels != 16 || c->n_hidden != 64 || !(c->n_feature_dims == 3 || c->n_feature_dims == 0)) {
-        asd_set_error("analytic field kernels are built for 16 levels x 2 features, 64 hidden units, 0/3 feature dims "
-                      "(got %u levels, %d hidden, %d feature dims)", m->n_levels, c->n_hidden, c->n_feature_dims);
-        return 0;
-    }
-    return 1;
-}
-
 // The workspace of asd_field_analytic_bwd, in floats from its start: the size query returns `total`, the pass takes every pointer from here.
 struct analytic_bwd_layout {
     int n_slabs;        // slabs reserved = blocks of field_wgrad_kernel over the 2 n rows
@@ -488,7 +433,7 @@ int asd_field_analytic_fwd(const asd_grid_meta* meta, const asd_field_cfg* cfg, 
                            float* sigma, float* features, float* grad, float* normal, float* enc_save, void* stream) {
     if (n == 0) return ASD_OK;
     ASD_CHECK_ARG(meta && cfg && grid_params && w1_density && w2_density && points && sigma && normal && n > 0, "null argument");
-    if (!analytic_supported(meta, cfg)) return ASD_ERR_UNSUPPORTED;
+    if (!asd_field_supported(meta, cfg, "analytic field")) return ASD_ERR_UNSUPPORTED;
     ASD_CHECK_ARG(cfg->n_feature_dims == 0 || !features || (w1_feature && w2_feature), "feature weights missing");
     hipLaunchKernelGGL((field_analytic_fwd_kernel<16, 64, 3>), dim3(asd_grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, *meta, *cfg,
                        grid_params, w1_density, w2_density, w1_feature, w2_feature, points, n, sigma,
@@ -512,7 +457,7 @@ int asd_field_analytic_bwd(const asd_grid_meta* meta, const asd_field_cfg* cfg, 
     ASD_CHECK_ARG(meta && cfg && grid_params && w1_density && w2_density && points && enc_save && sigma && d_grid_params && dw1_density &&
                       dw2_density && workspace && n > 0,
                   "null argument");
-    if (!analytic_supported(meta, cfg)) return ASD_ERR_UNSUPPORTED;
+    if (!asd_field_supported(meta, cfg, "analytic field")) return ASD_ERR_UNSUPPORTED;
     ASD_CHECK_ARG(cfg->n_feature_dims == 3 || !d_features, "d_features given but no feature network");
     ASD_CHECK_ARG(cfg->n_feature_dims == 0 || (dw1_feature && dw2_feature && w1_feature && w2_feature), "feature gradients missing");
     hipStream_t s = (hipStream_t)stream;
@@ -529,17 +474,12 @@ int asd_field_analytic_bwd(const asd_grid_meta* meta, const asd_field_cfg* cfg, 
                        w1_feature, w2_feature, points, enc_save, n, d_sigma, d_features, d_normal, d_grad, da, t, denc, g, gh, w2part)
     if (cfg->n_feature_dims == 3) ASD_ANALYTIC_BWD_LAUNCH(3); else ASD_ANALYTIC_BWD_LAUNCH(0);
 #undef ASD_ANALYTIC_BWD_LAUNCH
-    const int64_t total = (int64_t)asd_div_up(n, 256) * 256 * meta->n_levels;
-    hipLaunchKernelGGL(field_analytic_scatter_kernel, dim3(asd_grid_for(total, 256) * 4), block, 0, s, *meta, *cfg, points, denc, g, gh, n,
+    hipLaunchKernelGGL(field_analytic_scatter_kernel, dim3(asd_point_level_grid(n, (int)meta->n_levels)), block, 0, s, *meta, *cfg, points, denc, g, gh, n,
                        d_grid_params);
-    asd_field_wgrad_launch(da, enc_save, t, n, rows, slabs, s);
-    // slab layout [h < 64: density | h >= 64: feature][k]; w2part rows [64 density | 3 x 64 feature]
-    asd_field_slab_reduce_launch(slabs, n_slabs, 128 * 32, 64 * 32, dw1_density, s);
+    asd_field_wgrad_tail(da, enc_save, t, n, rows, nullptr, false, slabs, n_slabs, dw1_density, cfg->n_feature_dims == 3 ? dw1_feature : nullptr, s);
+    // w2part rows [64 density | 3 x 64 feature]
     asd_field_slab_reduce_launch(w2part, L.n_blocks, AN_W2N, 64, dw2_density, s);
-    if (cfg->n_feature_dims == 3) {
-        asd_field_slab_reduce_launch(slabs + 64 * 32, n_slabs, 128 * 32, 64 * 32, dw1_feature, s);
-        asd_field_slab_reduce_launch(w2part + 64, L.n_blocks, AN_W2N, 3 * 64, dw2_feature, s);
-    }
+    if (cfg->n_feature_dims == 3) asd_field_slab_reduce_launch(w2part + 64, L.n_blocks, AN_W2N, 3 * 64, dw2_feature, s);
     ASD_LAUNCH_CHECK();
     return ASD_OK;
 }

@@ -65,7 +65,12 @@ __device__ __forceinline__ void mlpC(const float* __restrict__ w1, const float* 
 // (library-internal: not part of include/asd_hip.h)
 extern "C" {
 int asd_field_wgrad_chunks(int64_t rows);
-void asd_field_wgrad_launch(const float* da, const float* enc_a, const float* enc_b, int rows_a, int rows_total, float* slabs,
-                            hipStream_t s);
+// The whole tail: field_wgrad_kernel over n_slabs chunks (unless slabs_written: another pass left n_slabs slabs), then dw1_density += the slabs'
+// density half and, with a feature network (dw1_feature != NULL), dw1_feature += their feature half.  n_dev (optional): device-side count of the
+// live centre rows; rows_a is its bound.
+void asd_field_wgrad_tail(const float* da, const float* enc_a, const float* enc_b, int rows_a, int rows_total, const int* n_dev, bool slabs_written,
+                          float* slabs, int n_slabs, float* dw1_density, float* dw1_feature, hipStream_t s);
 void asd_field_slab_reduce_launch(const float* slabs, int n_slabs, int stride, int len, float* out, hipStream_t s);
+// 1 if the fused field kernels are built for this grid and configuration; otherwise 0 and the error text, which names `what` kernels
+int asd_field_supported(const asd_grid_meta* m, const asd_field_cfg* c, const char* what);
 }

@@ -7,23 +7,21 @@
 // level through HBM and touches the table itself once per PAGE (64 KB read + write per page and launch).
 #include "field_paged.h"
 
-#define PG_P1 2654435761u
-#define PG_P2 805459861u
-
 struct pg_level {      // what a row needs of one level
     uint32_t cx, hy0, hy1, hz0, hz1;
     float wx, wy, wz;
 };
 __device__ __forceinline__ pg_level pg_locate(const asd_grid_meta& m, int l, float x, float y, float z) {
-    // the arithmetic of asd_encode (asd_common.h): same cell, same weights
+    // the arithmetic of asd_cell_of (asd_common.h): same cell, same weights.  Written out, not derived from an asd_cell: with the helper
+    // hipcc orders pg_fill_kernel's conversions differently (tools/asm_same.py) — keep the two in step
     const float s = m.scale[l];
     const float px = fmaf(s, x, 0.5f), py = fmaf(s, y, 0.5f), pz = fmaf(s, z, 0.5f);
     const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);
     const uint32_t cy = (uint32_t)(int32_t)fy, cz = (uint32_t)(int32_t)fz;
     pg_level r;
     r.cx = (uint32_t)(int32_t)fx;
-    r.hy0 = cy * PG_P1; r.hy1 = (cy + 1u) * PG_P1;
-    r.hz0 = cz * PG_P2; r.hz1 = (cz + 1u) * PG_P2;
+    r.hy0 = cy * ASD_HASH_P1; r.hy1 = (cy + 1u) * ASD_HASH_P1;
+    r.hz0 = cz * ASD_HASH_P2; r.hz1 = (cz + 1u) * ASD_HASH_P2;
     r.wx = px - fx; r.wy = py - fy; r.wz = pz - fz;
     return r;
 }
@@ -62,12 +60,7 @@ __global__ __launch_bounds__(256) void pg_fill_kernel(const asd_grid_meta m, con
     for (int q = 0; q < 2 * NF; ++q) rk[q] = 0u;
     if (live) {
         x = upos[3 * rr]; y = upos[3 * rr + 1]; z = upos[3 * rr + 2];
-        const float4* src = reinterpret_cast<const float4*>(g + rr * (2 * NFP));
-#pragma unroll
-        for (int q = 0; q < NFP / 2; ++q) {
-            const float4 v = src[q];
-            gv[4 * q] = v.x; gv[4 * q + 1] = v.y; gv[4 * q + 2] = v.z; gv[4 * q + 3] = v.w;
-        }
+        asd_row_load(g + rr * (2 * NFP), gv);
 #pragma unroll
         for (int f = 0; f < NF; ++f) {
             if (gv[2 * f] == 0.f && gv[2 * f + 1] == 0.f) continue;

@@ -731,3 +731,47 @@ def test_fused_optimizer_table_matches_the_c_struct():
     assert _OPT_DTYPE.itemsize == C.sizeof(OptTensor)
     for name, _ in OptTensor._fields_:
         assert _OPT_DTYPE.fields[name][1] == getattr(OptTensor, name).offset, name
+
+
+# n -> floats, recorded from the library before the field kernels were put on one cell / row / weight-gradient-tail helper (the default paged scatter)
+_FIELD_WS_N = (0, 1, 255, 256, 257, 513)
+_FIELD_WS = {
+    # (entry, feature dims, with normal)
+    ("field", 0, 0): (3933248, 3948864, 4033216, 4033344, 4044864, 4144960),
+    ("field", 0, 1): (3933248, 3949440, 4349376, 4350016, 4366208, 4782976),
+    ("field", 3, 0): (3933248, 3948800, 4008768, 4008768, 4024320, 4099840),
+    ("field", 3, 1): (3933248, 3949440, 4349376, 4350016, 4366208, 4782976),
+    ("voxfield", 0, 0): (0, 4352, 45696, 45824, 46080, 91904),
+    ("voxfield", 0, 1): (0, 4928, 198976, 199680, 204608, 404288),
+    ("voxfield", 3, 0): (0, 4352, 45696, 45824, 46080, 91904),
+    ("voxfield", 3, 1): (0, 4928, 198976, 199680, 204608, 404288),
+    ("analytic", 0, 0): (0, 4864, 95232, 95488, 100352, 195840),
+    ("analytic", 0, 1): (0, 4864, 95232, 95488, 100352, 195840),
+    ("analytic", 3, 0): (0, 4864, 95232, 95488, 100352, 195840),
+    ("analytic", 3, 1): (0, 4864, 95232, 95488, 100352, 195840),
+}
+
+
+@pytest.mark.parametrize("entry,feature_dims,with_normal", sorted(_FIELD_WS))
+def test_field_backward_workspace_sizes_are_pinned(entry, feature_dims, with_normal):
+    """asd_field_bwd_workspace / asd_voxfield_bwd_workspace / asd_field_analytic_bwd_workspace (host arithmetic only: no device needed) around the
+    256-sample block and 512-row chunk edges: the passes carve their workspace from the same layout, so a size that moves is a layout that moved."""
+    import ctypes as C
+    import os
+
+    from scaledreamer_amd import _lib
+
+    assert os.environ.get("ASD_FIELD_PAGED", "1") != "0", "the recorded sizes are those of the default (paged) scatter"
+    L = _lib.lib()
+    cfg = _lib.FieldCfg()
+    cfg.n_hidden, cfg.n_feature_dims = 64, feature_dims
+    got = []
+    for n in _FIELD_WS_N:
+        nf = C.c_int64(-1)
+        if entry == "analytic":
+            _lib.check(L.asd_field_analytic_bwd_workspace(C.byref(cfg), _lib.i32(n), C.byref(nf)))
+        else:
+            fn = L.asd_field_bwd_workspace if entry == "field" else L.asd_voxfield_bwd_workspace
+            _lib.check(fn(C.byref(cfg), _lib.i32(n), _lib.i32(with_normal), C.byref(nf)))
+        got.append(nf.value)
+    assert tuple(got) == _FIELD_WS[(entry, feature_dims, with_normal)]
