@@ -79,8 +79,22 @@ __device__ __forceinline__ void asd_point_level(int64_t t, int L, int64_t& i, in
     i = tile * 256 + (r % 256);
 }
 
+// ---- fp16 / fp32 vectors as the matrix instructions and the 8- / 16-byte accesses take them: THE declarations of the library --------
+typedef _Float16 half_t;
+typedef half_t half4 __attribute__((ext_vector_type(4)));
+typedef half_t half8 __attribute__((ext_vector_type(8)));
+typedef float floatx4 __attribute__((ext_vector_type(4)));
+typedef float floatx16 __attribute__((ext_vector_type(16)));
+
 // ---- wave64 primitives -------------------------------------------------------------------------
 __device__ __forceinline__ int asd_lane() { return (int)(threadIdx.x & 63); }
+
+// max over the 64 lanes, returned in every lane (the __shfl_xor butterfly: the callers reduce once per row or per launch)
+__device__ __forceinline__ float asd_wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
 
 // sum over the 64 lanes, returned in every lane.  DPP row shifts / row broadcasts (VALU only; the __shfl_xor butterfly is six
 // ds_bpermute round trips through the LDS pipe per call, and the field / background backward kernels make hundreds of calls per wave)

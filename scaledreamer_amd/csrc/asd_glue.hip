@@ -18,7 +18,6 @@
 // MVDream (mvdream_asd_guidance.py:181-304) is the same with n_rep = 2, n_neg = 0 and one t per 4-view group.
 #include "asd_common.h"
 
-typedef _Float16 half_t;
 
 namespace {
 

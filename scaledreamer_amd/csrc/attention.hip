@@ -15,10 +15,6 @@
 // XOR-swizzled (K: chunk ^ (row&7) for ds_read_b128, V^T: chunk ^ ((row>>1)&7) for ds_read_b64).
 #include "asd_common.h"
 
-typedef _Float16 half_t;
-typedef half_t half8 __attribute__((ext_vector_type(8)));
-typedef half_t half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 #define GLOBAL_AS __attribute__((address_space(1)))
 #define LDS_AS __attribute__((address_space(3)))
 

@@ -17,8 +17,6 @@
 
 #include "asd_common.h"
 
-typedef _Float16 half_t;
-typedef half_t half8 __attribute__((ext_vector_type(8)));
 
 #define CLIP_BLOCK 256
 #define CLIP_PREC_BITS 22          // PIL's PRECISION_BITS = 32 - 8 - 2

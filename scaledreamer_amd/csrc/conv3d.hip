@@ -1,13 +1,8 @@
 // conv3d.hip — the StyleGAN-3D generator's 3x3x3 convolutions (custom/amortized/extern/stylegan_3dconv_modules.py:64-82 modulated_conv3d,
 // :117-171 SynthesisLayer / SynthesisBlock) on the fp16 matrix pipe at fp32-class accuracy.
 //
-// The reference trains this generator in fp32 (F.conv3d, groups = batch).  gfx950 has no reduced-precision fp32 matrix path (no xf32;
-// v_mfma_f32_*_f32 runs at the vector rate, 1/16 of fp16), so every fp32 operand is SPLIT into two fp16 planes
-//     x * s = hi + lo,   hi = fp16(x * s),  lo = fp16(x * s - hi)        (s: a power of two that puts max|x| into [2^14, 2^15))
-// and a product of two operands is formed from three fp16 MFMA products with fp32 accumulation,
-//     a . b  =  a_hi b_hi + a_hi b_lo + a_lo b_hi      (+ a_lo b_lo ~ 2^-22 |a||b|, dropped),
-// i.e. 22 significant bits per operand (fp32 has 24) at 1/3 of the fp16 MFMA rate instead of 1/16.  Products of fp16 values are exact in
-// fp32, so the only roundings are the two splits and the fp32 accumulation the library path has as well.
+// The reference trains this generator in fp32 (F.conv3d, groups = batch); here every fp32 operand is split into two fp16 planes with one
+// power-of-two scale per tensor and a product is three fp16 MFMA products accumulated in fp32: the scheme and its derivation are in split_f16.h.
 //
 //   forward / input gradient   conv3d_pp_kernel<TN>: the ping-pong LDS-window schedule of gemm_pp.hip (eight waves, two per SIMD, staggered by one
 //                              barrier) carried to three dimensions: a block owns a 16 x 16 voxel patch of one depth slice x BN = 32 TN output
@@ -25,20 +20,9 @@
 #include <cstring>
 
 #include "gemm_tile.h"
+#include "split_f16.h"
 
-// ---- scales ---------------------------------------------------------------------------------------------------------------------
-// amax_bits: bit pattern of max|x| (non-negative floats order like their bit patterns).  scale = 2^(14 - floor(log2 amax)).
-__device__ __forceinline__ float split_scale(unsigned amax_bits) {
-    if (amax_bits == 0u || amax_bits >= 0x7f800000u) return 1.f;       // all zero (or not finite: nothing to save)
-    int se = 14 - ((int)((amax_bits >> 23) & 0xffu) - 127);
-    se = se > 100 ? 100 : (se < -100 ? -100 : se);
-    return __int_as_float((unsigned)(se + 127) << 23);
-}
-__device__ __forceinline__ void split2(float v, half_t& hi, half_t& lo) {
-    hi = (half_t)v;
-    lo = (half_t)(v - (float)hi);
-}
-
+// ---- scales (split_f16.h; one per tensor, top exponent 14, from the bit pattern of max|x| that the absmax passes commit) -----------------
 __device__ __forceinline__ float abs4max(const floatx4 v, float m) {
     return fmaxf(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))), m);
 }
@@ -46,8 +30,7 @@ __device__ __forceinline__ float abs4max(const floatx4 v, float m) {
 // channel (~5 ns each: 81 us for any tensor past the grid cap, whatever its size) — and almost none of them raises the maximum: a wave reads
 // the word first (an L2 load: monotone, so a stale value only costs a redundant atomic) and issues the atomic only if it would change it
 __device__ __forceinline__ void wave_amax_commit(float m, unsigned* out) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    m = asd_wave_max(m);
     if ((threadIdx.x & 63) == 0) {
         const unsigned b = __float_as_uint(m);
         if (b > __hip_atomic_load(out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(out, b);
@@ -67,7 +50,7 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x
     // channel — 100 us for a 28 MB tensor (tools/absmax_time.py)
     __shared__ float part[4];
 #pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));      // asd_wave_max written out: through the helper hipcc orders the tail differently (tools/asm_same.py)
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -80,15 +63,15 @@ static inline int c3_amax_grid(size_t n4) { size_t g = (n4 + 1023) / 1024; retur
 // x fp32 [rows][C] -> hi / lo fp16 [rows][C] (channel-last volume: rows = voxels), 8 channels per thread
 __global__ __launch_bounds__(256) void split_rows_kernel(const float* __restrict__ x, size_t n8, const unsigned* __restrict__ amax,
                                                          half_t* __restrict__ hi, half_t* __restrict__ lo) {
-    const float s = split_scale(*amax);
+    const float s = asd_split_scale_bits<14>(*amax);
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
         const floatx4 a = *(const floatx4*)(x + 8 * i), b = *(const floatx4*)(x + 8 * i + 4);
         half8 h, l;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             half_t u, v;
-            split2(a[r] * s, u, v); h[r] = u; l[r] = v;
-            split2(b[r] * s, u, v); h[4 + r] = u; l[4 + r] = v;
+            asd_split(a[r] * s, u, v); h[r] = u; l[r] = v;
+            asd_split(b[r] * s, u, v); h[4 + r] = u; l[4 + r] = v;
         }
         *(half8*)(hi + 8 * i) = h;
         *(half8*)(lo + 8 * i) = l;
@@ -107,7 +90,7 @@ __global__ __launch_bounds__(256) void split_cm_kernel(const float* __restrict__
     const int row = blockIdx.x, c0 = blockIdx.y * 32;
     const int dp = row / Hp, hp = row - dp * Hp;
     const bool interior = dp >= 1 && dp <= D && hp < H;
-    const float s = split_scale(*amax);
+    const float s = asd_split_scale_bits<14>(*amax);
     const size_t base = (size_t)guard + (size_t)row * Wp;
     const int tid = threadIdx.x;
     for (int w0 = 0; w0 < Wp; w0 += 64) {
@@ -122,8 +105,8 @@ __global__ __launch_bounds__(256) void split_cm_kernel(const float* __restrict__
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 half_t h, l;
-                split2(a[r] * s, h, l); th[cc + r][tid >> 2] = h; tl[cc + r][tid >> 2] = l;
-                split2(b[r] * s, h, l); th[cc + 4 + r][tid >> 2] = h; tl[cc + 4 + r][tid >> 2] = l;
+                asd_split(a[r] * s, h, l); th[cc + r][tid >> 2] = h; tl[cc + r][tid >> 2] = l;
+                asd_split(b[r] * s, h, l); th[cc + 4 + r][tid >> 2] = h; tl[cc + 4 + r][tid >> 2] = l;
             }
         }
         __syncthreads();
@@ -145,7 +128,7 @@ __global__ __launch_bounds__(256) void split_cm_kernel(const float* __restrict__
 //   transpose == 1 (input gradient):  [I][26 - tap][O]   (mirrored taps, channels swapped)
 __global__ __launch_bounds__(256) void pack_w_kernel(const float* __restrict__ w, int O, int I, int transpose, const unsigned* __restrict__ amax,
                                                      half_t* __restrict__ hi, half_t* __restrict__ lo) {
-    const float s = split_scale(*amax);
+    const float s = asd_split_scale_bits<14>(*amax);
     const size_t n = (size_t)O * I * 27;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         // destination-ordered: i = (r * 27 + t) * Cn + c
@@ -155,7 +138,7 @@ __global__ __launch_bounds__(256) void pack_w_kernel(const float* __restrict__ w
         const int t = (int)(q % 27), r = (int)(q / 27);
         const size_t src = transpose ? ((size_t)c * I + r) * 27 + (26 - t) : ((size_t)r * I + c) * 27 + t;
         half_t h, l;
-        split2(w[src] * s, h, l);
+        asd_split(w[src] * s, h, l);
         hi[i] = h; lo[i] = l;
     }
 }
@@ -176,33 +159,6 @@ struct conv3d_kargs {
     int group_m, group_n;
 };
 
-template <int N>
-__device__ __forceinline__ void c3_vm_wait() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void c3_vm_wait_n(int n) {      // wave-uniform n <= 7
-    switch (n) {
-        case 0: c3_vm_wait<0>(); break;
-        case 1: c3_vm_wait<1>(); break;
-        case 2: c3_vm_wait<2>(); break;
-        case 3: c3_vm_wait<3>(); break;
-        case 4: c3_vm_wait<4>(); break;
-        case 5: c3_vm_wait<5>(); break;
-        case 6: c3_vm_wait<6>(); break;
-        default: c3_vm_wait<7>(); break;
-    }
-}
-__device__ __forceinline__ void c3_mfma(floatx4& c, const half8& w, const half8& x) {       // in place (gemm_pp.hip: pp_mfma)
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(w), "v"(x));
-}
-#define C3_PIN() __builtin_amdgcn_sched_barrier(0)
-#define C3_BARRIER()                    \
-    do {                                \
-        C3_PIN();                       \
-        __builtin_amdgcn_s_barrier();   \
-        C3_PIN();                       \
-    } while (0)
-
 template <int TN>
 __global__ __launch_bounds__(512) void conv3d_pp_kernel(const conv3d_kargs p) {
     constexpr int TM = 4, WM = 4, WN = 2, PH = WM * TM, BN = WN * TN * 16, PITCH = 24;
@@ -210,7 +166,7 @@ __global__ __launch_bounds__(512) void conv3d_pp_kernel(const conv3d_kargs p) {
     constexpr int WSLABS = BN / 16, NWL = 2 * WSLABS / 8;            // weight slabs (16 rows x 64 B) per plane; loads per wave and K-step (both planes)
     constexpr int NPP = 3 * WLINES / 2, NPIECE = 2 * NPP;            // window pieces (1 KiB = 16 rows) per plane / per chunk
     constexpr int WROUNDS = (NPIECE + 7) / 8, PPT = (WROUNDS + 3) / 4;   // pieces per wave in each of taps 1..4
-    static_assert(TN % 2 == 0 && NWL >= 1 && NWL + PPT <= 7, "the weight slabs of both planes are dealt to the eight waves; c3_vm_wait_n covers 0..7");
+    static_assert(TN % 2 == 0 && NWL >= 1 && NWL + PPT <= 7, "the weight slabs of both planes are dealt to the eight waves; asd_vm_wait_n covers 0..7");
     extern __shared__ __attribute__((aligned(16))) char smem[];     // [window 0: hi | lo][window 1: hi | lo][weights 0: hi | lo][1][2]
     char* const win = smem;
     char* const wring = smem + 4 * WIN_BYTES;
@@ -316,9 +272,9 @@ __global__ __launch_bounds__(512) void conv3d_pp_kernel(const conv3d_kargs p) {
         }
         load_w(0, 0, 0);
         load_w(0, 1, 1);
-        c3_vm_wait<0>();
-        C3_BARRIER();
-        if (grp == 1) C3_BARRIER();      // the second group runs one barrier behind
+        asd_vm_wait<0>();
+        ASD_BARRIER();
+        if (grp == 1) ASD_BARRIER();      // the second group runs one barrier behind
 
 #pragma unroll 1
         for (int c = 0; c < nch; ++c) {
@@ -337,7 +293,7 @@ __global__ __launch_bounds__(512) void conv3d_pp_kernel(const conv3d_kargs p) {
                 for (int j = 0; j < TN; ++j) { Bh[j] = *(const half8*)(Ws + j * 1024); Bl[j] = *(const half8*)(Ws + W_BYTES + j * 1024); }
 #pragma unroll
                 for (int a = 0; a < TM; ++a) { Ah[a] = *(const half8*)(Ab + a * PITCH * 64); Al[a] = *(const half8*)(Ab + WIN_BYTES + a * PITCH * 64); }
-                C3_PIN();
+                ASD_PIN();
                 int nwin = 0;
                 if (!last && t >= 1 && t <= 4) {
 #pragma unroll
@@ -349,34 +305,34 @@ __global__ __launch_bounds__(512) void conv3d_pp_kernel(const conv3d_kargs p) {
                 if (iss) {
                     if (t + 2 < 9) load_w(c, t + 2, (t + 2) % 3);
                     else load_w(c + 1, t + 2 - 9, (t + 2) % 3);
-                    c3_vm_wait_n(NWL + nwin);          // weights of K-step s + 1 (and every window piece issued before this tap) have landed
+                    asd_vm_wait_n(NWL + nwin);          // weights of K-step s + 1 (and every window piece issued before this tap) have landed
                 } else if (t == 7) {
-                    c3_vm_wait<0>();
+                    asd_vm_wait<0>();
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // reads retired before the partner may refill the slot
-                C3_BARRIER();
+                ASD_BARRIER();
                 __builtin_amdgcn_s_setprio(1);
 #pragma unroll
                 for (int a = 0; a < TM; ++a)
 #pragma unroll
-                    for (int j = 0; j < TN; ++j) c3_mfma(acc[a][j], Bl[j], Ah[a]);
+                    for (int j = 0; j < TN; ++j) asd_mfma_inplace(acc[a][j], Bl[j], Ah[a]);
 #pragma unroll
                 for (int a = 0; a < TM; ++a)
 #pragma unroll
-                    for (int j = 0; j < TN; ++j) c3_mfma(acc[a][j], Bh[j], Al[a]);
+                    for (int j = 0; j < TN; ++j) asd_mfma_inplace(acc[a][j], Bh[j], Al[a]);
 #pragma unroll
                 for (int a = 0; a < TM; ++a)
 #pragma unroll
-                    for (int j = 0; j < TN; ++j) c3_mfma(acc[a][j], Bh[j], Ah[a]);
+                    for (int j = 0; j < TN; ++j) asd_mfma_inplace(acc[a][j], Bh[j], Ah[a]);
                 __builtin_amdgcn_s_setprio(0);
-                C3_BARRIER();
+                ASD_BARRIER();
             }
         }
-        if (grp == 0) C3_BARRIER();      // the first group waits for the second one's last segment
+        if (grp == 0) ASD_BARRIER();      // the first group waits for the second one's last segment
     }
 
     // ---- epilogue: acc[i][j][r] = Y[voxel (b, y0 + wm*TM + i, x0 + (lane&15))][n0 + wn*TN*16 + j*16 + (lane>>4)*4 + r] ------------------
-    const float inv = 1.f / (split_scale(*p.amax_x) * split_scale(*p.amax_w));
+    const float inv = 1.f / (asd_split_scale_bits<14>(*p.amax_x) * asd_split_scale_bits<14>(*p.amax_w));
     const float ns = p.noise ? *p.noise_strength : 0.f;
     float am = 0.f;
 #pragma unroll
@@ -422,7 +378,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
     }
     for (int s = 0; s < n2; ++s) v += s2[(size_t)s * MN + i];
     const int kx = n / Cout, co = n - kx * Cout, t9 = m / Cin, ci = m - t9 * Cin;
-    v *= 1.f / (split_scale(*amax_x) * split_scale(*amax_dy));
+    v *= 1.f / (asd_split_scale_bits<14>(*amax_x) * asd_split_scale_bits<14>(*amax_dy));
     dw[((size_t)co * Cin + ci) * 27 + t9 * 3 + kx] = v;
 }
 

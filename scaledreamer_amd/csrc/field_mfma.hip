@@ -5,7 +5,7 @@
 // behind threestudio/models/networks.py:214-251 VanillaMLP; call site geometry/implicit_volume.py:109-207), which ran at ~18 % of the vector rate
 // and was the larger half of the field-gradient span.  Here a wave owns 64 samples and every product is a
 // v_mfma_f32_32x32x16_f16 in split-fp16 arithmetic (x * s = hi + lo with s a power of two, product = hi hi + hi lo + lo hi, fp32 accumulate: 22
-// significant bits per operand — the scheme of csrc/conv3d.hip / trifield_mfma.hip):
+// significant bits per operand — csrc/split_f16.h):
 //
 //   Z^T  = W1 E^T        [64 h x 64 samples]   samples are the MFMA's N columns, so a lane (sample, half) keeps its own sample's hidden units:
 //                                               the per-sample power-of-two scale of E factors out of the contraction, and only sign(Z^T) is needed
@@ -27,41 +27,14 @@
 // left 186 of 12.6 M table-gradient entries outside 1e-4 of the oracle's: tests/test_gpu_renderer_kernels.py::test_field_backward).
 #include <math.h>
 
-#include "asd_common.h"
-
-typedef _Float16 fm_h;
-typedef fm_h fm_h8 __attribute__((ext_vector_type(8)));
-typedef float fm_f16x __attribute__((ext_vector_type(16)));
-typedef float fm_f4 __attribute__((ext_vector_type(4)));
+#include "split_f16.h"
 
 namespace {
 
-__device__ __forceinline__ float fm_pow2_scale(float amax) {       // 2^(13 - floor(log2 amax)): amax * scale in [2^13, 2^14); 1 for amax == 0
-    if (!(amax > 1e-30f)) return 1.f;              // (zero rows; magnitudes below fp16's reach after any scale contribute nothing)
-    const int e = (int)((__float_as_uint(amax) >> 23) & 255u) - 127;      // floor(log2 amax) for normal numbers
-    return __uint_as_float((unsigned)(127 + 13 - e) << 23);
-}
-__device__ __forceinline__ void fm_split8(const float (&x)[8], float s, fm_h8& hi, fm_h8& lo) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float v = x[j] * s;
-        const fm_h h = (fm_h)v;
-        hi[j] = h;
-        lo[j] = (fm_h)(v - (float)h);
-    }
-}
-__device__ __forceinline__ fm_f16x fm_mma3(const fm_h8 ah, const fm_h8 al, const fm_h8 bh, const fm_h8 bl, fm_f16x acc) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
-    return acc;
-}
-// x: lanes 32-63 <-> y: lanes 0-31 (v_permlane32_swap)
-__device__ __forceinline__ void fm_swap(float& x, float& y) {
-    const auto t = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-    x = __uint_as_float(t[0]);
-    y = __uint_as_float(t[1]);
-}
+// Top exponent 13, not the 14 of the other families: scaled operands stay below 2^14 and a product below 2^28, and the threshold of the
+// ReLU-mask fix-up below (4096.f = 2^12 in scaled units) is the error bound of a 32-term sum of such products with operands good to 2^-22.
+// At 14 the terms, the sums' headroom and that threshold would all move by a factor of four: the value belongs to this kernel's bounds.
+constexpr int FM_TOP = 13;
 
 constexpr int FM_H = 64, FM_K = 32, FM_C = 3;
 
@@ -87,7 +60,7 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
     __shared__ float w2s[4][FM_H];                // w2d, w2f[0..2]
     __shared__ float gs[4][4][64];                // per wave: g_o[s] * inv scale of E (o = 0: draw, 1..3: df) for the Z pass
     __shared__ float red[4][4][FM_H];             // per wave: second-layer weight-gradient sums
-    __shared__ fm_h8 frag[16][2][64];             // weight fragments (hi, lo), lane-linear
+    __shared__ half8 frag[16][2][64];             // weight fragments (hi, lo), lane-linear
     __shared__ float gp[4][4][64];                // per wave: the plain g_o[s]
     __shared__ unsigned mb[4][64][2];             // per wave: every sample's 64-bit ReLU mask of the current head
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -112,11 +85,7 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
 #pragma unroll
     for (int hd = 0; hd < 2; ++hd)
         for (int q = lane; q < FM_H * FM_K; q += 64) wmax[hd] = fmaxf(wmax[hd], fabsf((&w1s[hd][0][0])[q]));
-#pragma unroll
-    for (int hd = 0; hd < 2; ++hd)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) wmax[hd] = fmaxf(wmax[hd], __shfl_xor(wmax[hd], off, 64));
-    const float sw[2] = {fm_pow2_scale(wmax[0]), fm_pow2_scale(wmax[1])};
+    const float sw[2] = {asd_split_scale<FM_TOP>(asd_wave_max(wmax[0])), asd_split_scale<FM_TOP>(asd_wave_max(wmax[1]))};
     // the 16 (hi, lo) fragment pairs live in LDS (32 KB, lane-linear: conflict-free 16-byte reads), not in 128 registers per lane: the kernel then fits
     // two waves per SIMD.  Wave w builds pairs 4 w .. 4 w + 3; index f = ((kind * 2 + hd) * 2 + mt) * 2 + t, kind 0 = wf, 1 = wt.
 #pragma unroll
@@ -126,8 +95,8 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
 #pragma unroll
         for (int j = 0; j < 8; ++j)
             x[j] = kind == 0 ? w1s[hd][32 * mt + l31][16 * t + 8 * half + j] : w1s[hd][32 * mt + 8 * (2 * t + j / 4) + 4 * half + (j & 3)][l31];
-        fm_h8 hi, lo;
-        fm_split8(x, sw[hd], hi, lo);
+        half8 hi, lo;
+        asd_split8(x, sw[hd], hi, lo);
         frag[f][0][lane] = hi;
         frag[f][1][lane] = lo;
     }
@@ -153,7 +122,7 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
     for (int tile = (int)blockIdx.x * 4 + wave; tile < n_tiles; tile += (int)gridDim.x * 4) {
         const int s0 = tile * 64;                 // first sample of the wave's tile
         // ---- the tile's encodings as fragments: ef[nt][ks]: sample 32 nt + l31, k = 16 ks + 8 half + j ------------------------------------
-        fm_h8 efh[2][2], efl[2][2];
+        half8 efh[2][2], efl[2][2];
         float se[2];                               // power-of-two scale of the lane's sample in tile nt (both halves agree)
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
@@ -163,8 +132,8 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 if (i < nn) {
-                    const fm_f4* src = reinterpret_cast<const fm_f4*>(a.enc + (size_t)i * FM_K + 16 * ks + 8 * half);
-                    const fm_f4 v0 = src[0], v1 = src[1];
+                    const floatx4* src = reinterpret_cast<const floatx4*>(a.enc + (size_t)i * FM_K + 16 * ks + 8 * half);
+                    const floatx4 v0 = src[0], v1 = src[1];
                     x[ks][0] = v0[0]; x[ks][1] = v0[1]; x[ks][2] = v0[2]; x[ks][3] = v0[3];
                     x[ks][4] = v1[0]; x[ks][5] = v1[1]; x[ks][6] = v1[2]; x[ks][7] = v1[3];
                 } else {
@@ -175,9 +144,9 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
                 for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(x[ks][j]));
             }
             amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-            se[nt] = fm_pow2_scale(amax);
+            se[nt] = asd_split_scale<FM_TOP>(amax);
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) fm_split8(x[ks], se[nt], efh[nt][ks], efl[nt][ks]);
+            for (int ks = 0; ks < 2; ++ks) asd_split8(x[ks], se[nt], efh[nt][ks], efl[nt][ks]);
         }
         // ---- per-sample output gradients: g[0] = d sigma * act'(raw) (from sigma itself), g[1..3] = d features -------------------------------
         float g[2][4];
@@ -212,7 +181,7 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
         // E^T fragments for the first-layer weight gradient dW1^T = E^T dA (contraction over the tile's samples: ONE scale for the tile).
         // et[st][tp]: row k = l31 (encoding index), slot j <-> sample 32 st + 8 (2 tp + j / 4) + 4 half + j % 4 — the order in which a lane's
         // accumulator registers of Z hold their samples; for a fixed j the 32 lanes of a half read one sample's 128-byte row.
-        fm_h8 eth[2][2], etl[2][2];
+        half8 eth[2][2], etl[2][2];
         float x[2][2][8];
         float amax = 0.f;
 #pragma unroll
@@ -226,13 +195,11 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
                     x[st][tp][j] = v;
                     amax = fmaxf(amax, fabsf(v));
                 }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
-        const float sT = fm_pow2_scale(amax);
+        const float sT = asd_split_scale<FM_TOP>(asd_wave_max(amax));
 #pragma unroll
         for (int st = 0; st < 2; ++st)
 #pragma unroll
-            for (int tp = 0; tp < 2; ++tp) fm_split8(x[st][tp], sT, eth[st][tp], etl[st][tp]);
+            for (int tp = 0; tp < 2; ++tp) asd_split8(x[st][tp], sT, eth[st][tp], etl[st][tp]);
 
 #pragma unroll 1                    // (one head at a time: both heads unrolled side by side need more than the 512 registers of a lone wave)
         for (int hd = 0; hd < 2; ++hd) {
@@ -244,11 +211,11 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt) {
-                    fm_f16x z;
+                    floatx16 z;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) z[r] = 0.f;
 #pragma unroll
-                    for (int ks = 0; ks < 2; ++ks) z = fm_mma3(WF_H(hd, mt, ks), WF_L(hd, mt, ks), efh[nt][ks], efl[nt][ks], z);
+                    for (int ks = 0; ks < 2; ++ks) z = asd_mma3(WF_H(hd, mt, ks), WF_L(hd, mt, ks), efh[nt][ks], efl[nt][ks], z);
                     // ReLU masks.  sign(z) decides, except where |z| is within the error bound of the 22-bit products (2^12 in scaled units: 32 terms
                     // of at most 2^28, operands good to 2^-22): those few units (~1 in 10^4) re-evaluate the pre-activation with the forward
                     // kernel's own fp32 FMA chain (field.hip: mlp1 / mlpC, k ascending from zero), so the masks ARE the forward pass's masks.
@@ -282,12 +249,12 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
                         mword[nt][mt] |= ((pos >> (4 * q)) & 15u) << (8 * q + 4 * half);
                         float gh[4];
                         if (hd == 0) {
-                            const fm_f4 w = *reinterpret_cast<const fm_f4*>(&w2s[0][hb]);
+                            const floatx4 w = *reinterpret_cast<const floatx4*>(&w2s[0][hb]);
 #pragma unroll
                             for (int r = 0; r < 4; ++r) gh[r] = g[nt][0] * w[r];
                         } else {
-                            const fm_f4 w0 = *reinterpret_cast<const fm_f4*>(&w2s[1][hb]), w1 = *reinterpret_cast<const fm_f4*>(&w2s[2][hb]),
-                                        w2 = *reinterpret_cast<const fm_f4*>(&w2s[3][hb]);
+                            const floatx4 w0 = *reinterpret_cast<const floatx4*>(&w2s[1][hb]), w1 = *reinterpret_cast<const floatx4*>(&w2s[2][hb]),
+                                        w2 = *reinterpret_cast<const floatx4*>(&w2s[3][hb]);
 #pragma unroll
                             for (int r = 0; r < 4; ++r) gh[r] = fmaf(g[nt][3], w2[r], fmaf(g[nt][2], w1[r], g[nt][1] * w0[r]));
                         }
@@ -310,12 +277,12 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
                 damax[nt] = fmaxf(damax[nt], __shfl_xor(damax[nt], 32, 64));
-                sd[nt] = fm_pow2_scale(damax[nt]);
+                sd[nt] = asd_split_scale<FM_TOP>(damax[nt]);
             }
             // ---- dE^T += W1^T dA^T: k-step (mt, tp) takes registers 8 tp .. 8 tp + 7 of dA^T[mt][nt] as its B fragment ----------------------------
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
-                fm_f16x d;
+                floatx16 d;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) d[r] = 0.f;
 #pragma unroll
@@ -325,9 +292,9 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
                         float x[8];
 #pragma unroll
                         for (int j = 0; j < 8; ++j) x[j] = da[mt][nt][8 * tp + j];
-                        fm_h8 bh, bl;
-                        fm_split8(x, sd[nt], bh, bl);
-                        d = fm_mma3(WT_H(hd, mt, tp), WT_L(hd, mt, tp), bh, bl, d);
+                        half8 bh, bl;
+                        asd_split8(x, sd[nt], bh, bl);
+                        d = asd_mma3(WT_H(hd, mt, tp), WT_L(hd, mt, tp), bh, bl, d);
                     }
                 const float inv = 1.f / (sw[hd] * sd[nt]);
 #pragma unroll
@@ -341,11 +308,11 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
                 float dzmax = 0.f;
 #pragma unroll
                 for (int st = 0; st < 2; ++st) {
-                    fm_f16x z;
+                    floatx16 z;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) z[r] = 0.f;
 #pragma unroll
-                    for (int ks = 0; ks < 2; ++ks) z = fm_mma3(efh[st][ks], efl[st][ks], WF_H(hd, ht, ks), WF_L(hd, ht, ks), z);
+                    for (int ks = 0; ks < 2; ++ks) z = asd_mma3(efh[st][ks], efl[st][ks], WF_H(hd, ht, ks), WF_L(hd, ht, ks), z);
                     // z[4 q + r] = scaled pre-activation of (sample 32 st + 8 q + 4 half + r, hidden unit 32 ht + l31)
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
@@ -354,22 +321,22 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
 #pragma unroll
                         for (int r = 0; r < 4; ++r) mk |= ((mb[wave][sb + r][ht] >> l31) & 1u) << r;
                         if (hd == 0) {
-                            const fm_f4 gv = *reinterpret_cast<const fm_f4*>(&gs[wave][0][sb]);
+                            const floatx4 gv = *reinterpret_cast<const floatx4*>(&gs[wave][0][sb]);
 #pragma unroll
                             for (int r = 0; r < 4; ++r) dw2[0][ht] = fmaf(fmaxf(z[4 * q + r], 0.f), gv[r], dw2[0][ht]);
-                            const fm_f4 gq = *reinterpret_cast<const fm_f4*>(&gp[wave][0][sb]);
+                            const floatx4 gq = *reinterpret_cast<const floatx4*>(&gp[wave][0][sb]);
                             const float w = w2s[0][32 * ht + l31];
 #pragma unroll
                             for (int r = 0; r < 4; ++r) daz[st][4 * q + r] = ((mk >> r) & 1u) ? gq[r] * w : 0.f;
                         } else {
 #pragma unroll
                             for (int o = 1; o < 4; ++o) {
-                                const fm_f4 gv = *reinterpret_cast<const fm_f4*>(&gs[wave][o][sb]);
+                                const floatx4 gv = *reinterpret_cast<const floatx4*>(&gs[wave][o][sb]);
 #pragma unroll
                                 for (int r = 0; r < 4; ++r) dw2[o][ht] = fmaf(fmaxf(z[4 * q + r], 0.f), gv[r], dw2[o][ht]);
                             }
-                            const fm_f4 g1 = *reinterpret_cast<const fm_f4*>(&gp[wave][1][sb]), g2 = *reinterpret_cast<const fm_f4*>(&gp[wave][2][sb]),
-                                        g3 = *reinterpret_cast<const fm_f4*>(&gp[wave][3][sb]);
+                            const floatx4 g1 = *reinterpret_cast<const floatx4*>(&gp[wave][1][sb]), g2 = *reinterpret_cast<const floatx4*>(&gp[wave][2][sb]),
+                                        g3 = *reinterpret_cast<const floatx4*>(&gp[wave][3][sb]);
                             const float w0 = w2s[1][32 * ht + l31], w1 = w2s[2][32 * ht + l31], w2 = w2s[3][32 * ht + l31];
 #pragma unroll
                             for (int r = 0; r < 4; ++r) daz[st][4 * q + r] = ((mk >> r) & 1u) ? fmaf(g3[r], w2, fmaf(g2[r], w1, g1[r] * w0)) : 0.f;
@@ -378,10 +345,9 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
                         for (int r = 0; r < 4; ++r) dzmax = fmaxf(dzmax, fabsf(daz[st][4 * q + r]));
                     }
                 }
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) dzmax = fmaxf(dzmax, __shfl_xor(dzmax, off, 64));
-                const float sD = fm_pow2_scale(dzmax);
-                fm_f16x d;
+                dzmax = asd_wave_max(dzmax);
+                const float sD = asd_split_scale<FM_TOP>(dzmax);
+                floatx16 d;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) d[r] = 0.f;
 #pragma unroll
@@ -391,9 +357,9 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
                         float x[8];
 #pragma unroll
                         for (int j = 0; j < 8; ++j) x[j] = daz[st][8 * tp + j];
-                        fm_h8 bh, bl;
-                        fm_split8(x, sD, bh, bl);
-                        d = fm_mma3(eth[st][tp], etl[st][tp], bh, bl, d);
+                        half8 bh, bl;
+                        asd_split8(x, sD, bh, bl);
+                        d = asd_mma3(eth[st][tp], etl[st][tp], bh, bl, d);
                     }
                 // d[4 q + r] = scaled dW1[hidden unit 32 ht + l31][k = 8 q + 4 half + r]
                 const float inv = 1.f / (sT * sD);
@@ -408,14 +374,14 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
         }
         // ---- dE rows --------------------------------------------------------------------------------------------------------------------------------
 #pragma unroll
-        for (int r = 0; r < 16; ++r) fm_swap(dencT[0][r], dencT[1][r]);
+        for (int r = 0; r < 16; ++r) asd_half_swap(dencT[0][r], dencT[1][r]);
         const int i = s0 + lane;
         if (i < nn) {
             float* dst = a.denc_out + (size_t)i * FM_K;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                *reinterpret_cast<fm_f4*>(dst + 8 * q) = fm_f4{dencT[0][4 * q], dencT[0][4 * q + 1], dencT[0][4 * q + 2], dencT[0][4 * q + 3]};
-                *reinterpret_cast<fm_f4*>(dst + 8 * q + 4) = fm_f4{dencT[1][4 * q], dencT[1][4 * q + 1], dencT[1][4 * q + 2], dencT[1][4 * q + 3]};
+                *reinterpret_cast<floatx4*>(dst + 8 * q) = floatx4{dencT[0][4 * q], dencT[0][4 * q + 1], dencT[0][4 * q + 2], dencT[0][4 * q + 3]};
+                *reinterpret_cast<floatx4*>(dst + 8 * q + 4) = floatx4{dencT[1][4 * q], dencT[1][4 * q + 1], dencT[1][4 * q + 2], dencT[1][4 * q + 3]};
             }
         }
     }
@@ -429,15 +395,15 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int o = (32 * ht + l31) * FM_K + 8 * q + 4 * half;
-                fm_f4 va = fm_f4{dw1a[ht][4 * q], dw1a[ht][4 * q + 1], dw1a[ht][4 * q + 2], dw1a[ht][4 * q + 3]};
-                fm_f4 vb = fm_f4{dw1b[ht][4 * q], dw1b[ht][4 * q + 1], dw1b[ht][4 * q + 2], dw1b[ht][4 * q + 3]};
+                floatx4 va = floatx4{dw1a[ht][4 * q], dw1a[ht][4 * q + 1], dw1a[ht][4 * q + 2], dw1a[ht][4 * q + 3]};
+                floatx4 vb = floatx4{dw1b[ht][4 * q], dw1b[ht][4 * q + 1], dw1b[ht][4 * q + 2], dw1b[ht][4 * q + 3]};
                 if (add) {
-                    const fm_f4 pa = *reinterpret_cast<fm_f4*>(buf + o), pb = *reinterpret_cast<fm_f4*>(buf + FM_H * FM_K + o);
+                    const floatx4 pa = *reinterpret_cast<floatx4*>(buf + o), pb = *reinterpret_cast<floatx4*>(buf + FM_H * FM_K + o);
                     va[0] += pa[0]; va[1] += pa[1]; va[2] += pa[2]; va[3] += pa[3];
                     vb[0] += pb[0]; vb[1] += pb[1]; vb[2] += pb[2]; vb[3] += pb[3];
                 }
-                *reinterpret_cast<fm_f4*>(buf + o) = va;
-                *reinterpret_cast<fm_f4*>(buf + FM_H * FM_K + o) = vb;
+                *reinterpret_cast<floatx4*>(buf + o) = va;
+                *reinterpret_cast<floatx4*>(buf + FM_H * FM_K + o) = vb;
             }
     };
     if (wave < 2) put(false);
@@ -447,8 +413,8 @@ __global__ __launch_bounds__(256, 1) void field_bwd_mlp_mfma_kernel(const FmArgs
     const float* b0 = reinterpret_cast<const float*>(&frag[0][0][0]);
     float* slab = a.dw1_slabs + (size_t)blockIdx.x * (2 * FM_H * FM_K);
     for (int q = tid; q < 2 * FM_H * FM_K / 4; q += 256) {
-        const fm_f4 x = reinterpret_cast<const fm_f4*>(b0)[q], y = reinterpret_cast<const fm_f4*>(b0 + 2 * FM_H * FM_K)[q];
-        reinterpret_cast<fm_f4*>(slab)[q] = fm_f4{x[0] + y[0], x[1] + y[1], x[2] + y[2], x[3] + y[3]};
+        const floatx4 x = reinterpret_cast<const floatx4*>(b0)[q], y = reinterpret_cast<const floatx4*>(b0 + 2 * FM_H * FM_K)[q];
+        reinterpret_cast<floatx4*>(slab)[q] = floatx4{x[0] + y[0], x[1] + y[1], x[2] + y[2], x[3] + y[3]};
     }
     // ---- second-layer weight gradients: halves, waves, one atomic per weight and block -----------------------------------------------------------------
 #pragma unroll

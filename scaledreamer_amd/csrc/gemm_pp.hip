@@ -21,37 +21,7 @@
 //   * split-K slices the 32-channel chunks; epilogue, wide rows, GroupNorm records: tile_epilogue of gemm_tile.h.
 #include "gemm_tile.h"
 
-template <int N>
-__device__ __forceinline__ void pp_vm_wait() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// wave-uniform n (scalar branches); n <= 7
-__device__ __forceinline__ void pp_vm_wait_n(int n) {
-    switch (n) {
-        case 0: pp_vm_wait<0>(); break;
-        case 1: pp_vm_wait<1>(); break;
-        case 2: pp_vm_wait<2>(); break;
-        case 3: pp_vm_wait<3>(); break;
-        case 4: pp_vm_wait<4>(); break;
-        case 5: pp_vm_wait<5>(); break;
-        case 6: pp_vm_wait<6>(); break;
-        default: pp_vm_wait<7>(); break;
-    }
-}
-// accumulate IN PLACE.  Through the builtin hipcc gives most MFMAs of the unrolled tap loop a destination different from their
-// accumulator operand (a rotating set of 40-60 extra registers: 227 VGPRs at 128 accumulators, spills inside the loop at 160).  No
-// dependent MFMA follows within a phase (every accumulator is used once per phase), the epilogue reads them after two barriers.
-__device__ __forceinline__ void pp_mfma(floatx4& c, const half8& w, const half8& x) {
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(w), "v"(x));
-}
 #define PP_PRIO(x) __builtin_amdgcn_s_setprio(x)
-#define PP_PIN() __builtin_amdgcn_sched_barrier(0)
-#define PP_BARRIER()                    \
-    do {                                \
-        PP_PIN();                       \
-        __builtin_amdgcn_s_barrier();   \
-        PP_PIN();                       \
-    } while (0)
 
 template <int TM, int TN>
 __global__ __launch_bounds__(512) void conv3x3_pp_kernel(const asd_gemm_args p) {
@@ -62,7 +32,7 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(const asd_gemm_args p) 
     constexpr int WROUNDS = (NPIECE + 7) / 8, PPT = (WROUNDS + 3) / 4;   // pieces per wave in each of taps 1..4
     constexpr int NPH = (TM * TN >= 24) ? 2 : 1;                     // phases per K-step
     static_assert(WLINES % 2 == 0 && (NPH == 1 || (TN > TM ? TN : TM) % 2 == 0), "window lines are loaded in pairs; the long side of the wave tile splits over the phases");
-    static_assert(NWL + PPT <= 7, "pp_vm_wait_n covers 0..7");
+    static_assert(NWL + PPT <= 7, "asd_vm_wait_n covers 0..7");
     extern __shared__ __attribute__((aligned(16))) char smem[];     // [window 0 | window 1 | weights 0 | 1 | 2]
     char* const win = smem;
     char* const wring = smem + 2 * WIN_BYTES;
@@ -168,9 +138,9 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(const asd_gemm_args p) 
         }
         load_w(c0, 0, 0);
         load_w(c0, 1, 1);
-        pp_vm_wait<0>();
-        PP_BARRIER();
-        if (grp == 1) PP_BARRIER();      // the second group runs one barrier behind
+        asd_vm_wait<0>();
+        ASD_BARRIER();
+        if (grp == 1) ASD_BARRIER();      // the second group runs one barrier behind
 
 #pragma unroll 1
         for (int c = c0; c < c1; ++c) {
@@ -194,7 +164,7 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(const asd_gemm_args p) 
                 for (int j = 0; j < NB; ++j) B[j] = *(const half8*)(Ws + j * 1024);
 #pragma unroll
                 for (int a = 0; a < NA; ++a) A[a] = *(const half8*)(Ab + a * PITCH * 64);
-                PP_PIN();
+                ASD_PIN();
                 int nwin = 0;
                 if (NPH == 1 && !last && t >= 1 && t <= 4) {
 #pragma unroll
@@ -206,20 +176,20 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(const asd_gemm_args p) 
                 if (iss) {
                     if (t + 2 < 9) load_w(c, t + 2, (t + 2) % 3);
                     else load_w(c + 1, t + 2 - 9, (t + 2) % 3);
-                    pp_vm_wait_n(NWL + (NPH == 1 ? nwin : nwin_prev));      // weights of K-step s + 1 have landed
+                    asd_vm_wait_n(NWL + (NPH == 1 ? nwin : nwin_prev));      // weights of K-step s + 1 have landed
                 } else if (t == 7) {
-                    pp_vm_wait<0>();
+                    asd_vm_wait<0>();
                 }
                 if (NPH == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // reads retired before the partner may refill the slot
-                PP_BARRIER();
+                ASD_BARRIER();
                 PP_PRIO(1);
 #pragma unroll
                 for (int a = 0; a < NA; ++a)
 #pragma unroll
                     for (int j = 0; j < NB; ++j)
-                        pp_mfma(acc[a][j], B[j], A[a]);
+                        asd_mfma_inplace(acc[a][j], B[j], A[a]);
                 PP_PRIO(0);
-                PP_BARRIER();
+                ASD_BARRIER();
                 // ---------------- phase 2: the other half of the long side ------------------------------------------------------
                 if constexpr (NPH == 2) {
                     if constexpr (SPLIT_N) {
@@ -229,7 +199,7 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(const asd_gemm_args p) 
 #pragma unroll
                         for (int a = 0; a < NA; ++a) A[a] = *(const half8*)(Ab + (NA + a) * PITCH * 64);
                     }
-                    PP_PIN();
+                    ASD_PIN();
                     if (!last && t >= 1 && t <= 4) {
 #pragma unroll
                         for (int k = 0; k < PPT; ++k) {
@@ -237,21 +207,21 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(const asd_gemm_args p) 
                             if (pc < NPIECE) { load_piece(pc, c + 1, wnext); ++nwin; }
                         }
                     }
-                    PP_BARRIER();
+                    ASD_BARRIER();
                     PP_PRIO(1);
 #pragma unroll
                     for (int a = 0; a < NA; ++a)
 #pragma unroll
                         for (int j = 0; j < NB; ++j) {
-                            pp_mfma(SPLIT_N ? acc[a][NB + j] : acc[NA + a][j], B[j], A[a]);
+                            asd_mfma_inplace(SPLIT_N ? acc[a][NB + j] : acc[NA + a][j], B[j], A[a]);
                         }
                     PP_PRIO(0);
-                    PP_BARRIER();
+                    ASD_BARRIER();
                 }
                 nwin_prev = nwin;
             }
         }
-        if (grp == 0) PP_BARRIER();      // the first group waits for the second one's last segment
+        if (grp == 0) ASD_BARRIER();      // the first group waits for the second one's last segment
     }
 
     // acc[i][j][r] = C[pixel (y0 + wm*TM + i, x0 + (lane&15))][n0 + wn*TN*16 + j*16 + (lane>>4)*4 + r]

@@ -1,12 +1,7 @@
-// gemm_tile.h — device helpers shared by the MFMA GEMM / convolution kernels of gemm.hip and gemm_pp.hip: fragment types,
-// XCD-aware block order, GroupNorm statistics in the epilogue, the common tile epilogue.
+// gemm_tile.h — device helpers shared by the MFMA GEMM / convolution kernels of gemm.hip, gemm_pp.hip and conv3d.hip: XCD-aware block
+// order, GroupNorm statistics in the epilogue, the common tile epilogue, the counted waits / in-place MFMA / barriers of the ping-pong schedule.
 #pragma once
 #include "asd_common.h"
-
-typedef _Float16 half_t;
-typedef half_t half8 __attribute__((ext_vector_type(8)));
-typedef half_t half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 // The rows of the tile table (asd_gemm_tiles of gemm.hip, which asserts these names against its rows) that a selection rule names:
 // 0-based, a caller's asd_gemm_args.tile_cfg is the index + 1
@@ -314,3 +309,35 @@ __device__ __forceinline__ void ring_wait(int ahead) {
         else ring_wait<PER, MAX - 1>(ahead);
     }
 }
+
+// ---- the ping-pong schedule (gemm_pp.hip, conv3d.hip) ----------------------------------------------------------------------------------
+template <int N>
+__device__ __forceinline__ void asd_vm_wait() {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+// wave-uniform n (scalar branches); n <= 7
+__device__ __forceinline__ void asd_vm_wait_n(int n) {
+    switch (n) {
+        case 0: asd_vm_wait<0>(); break;
+        case 1: asd_vm_wait<1>(); break;
+        case 2: asd_vm_wait<2>(); break;
+        case 3: asd_vm_wait<3>(); break;
+        case 4: asd_vm_wait<4>(); break;
+        case 5: asd_vm_wait<5>(); break;
+        case 6: asd_vm_wait<6>(); break;
+        default: asd_vm_wait<7>(); break;
+    }
+}
+// accumulate IN PLACE.  Through the builtin hipcc gives most MFMAs of the unrolled tap loop a destination different from their
+// accumulator operand (a rotating set of 40-60 extra registers: 227 VGPRs at 128 accumulators, spills inside the loop at 160).  No
+// dependent MFMA follows within a phase (every accumulator is used once per phase), the epilogue reads them after two barriers.
+__device__ __forceinline__ void asd_mfma_inplace(floatx4& c, const half8& w, const half8& x) {
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(w), "v"(x));
+}
+#define ASD_PIN() __builtin_amdgcn_sched_barrier(0)
+#define ASD_BARRIER()                   \
+    do {                                \
+        ASD_PIN();                      \
+        __builtin_amdgcn_s_barrier();   \
+        ASD_PIN();                      \
+    } while (0)

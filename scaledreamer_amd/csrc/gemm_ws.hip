@@ -25,7 +25,6 @@
 
 #include "gemm_tile.h"
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
 
 #define WS_A_BYTES(NB) ((NB) * 64 * 64)          // B x 64 pixels x 32 channels

@@ -22,7 +22,6 @@
 
 namespace {
 
-typedef _Float16 half_t;
 
 struct WSpec { std::string name; int rows, cols; };
 

@@ -8,8 +8,6 @@
 #include "asd_common.h"
 #include <type_traits>
 
-typedef _Float16 half_t;
-typedef half_t half8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ float silu_f(float v) { return asd_silu_fast(v); }   // v_exp + v_rcp, no IEEE division (asd_common.h)
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }

@@ -3,7 +3,6 @@
 #pragma once
 #include "asd_common.h"
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 #define TF_H 64
 #define TF_NIN 96
 

@@ -4,7 +4,7 @@
 // 64 rows (16 samples x {centre, +x, +y, +z} with a finite-difference normal, 64 samples without) and every layer is a product
 //        Z^T [units x rows] = W [units x k] * X^T [k x rows]           (v_mfma_f32_16x16x32_f16, A = weight fragment, B = activation fragment)
 // evaluated in split-fp16 arithmetic: x * s = hi + lo (s a power of two), W * sW = hi + lo, product = hi*hi + hi*lo + lo*hi accumulated
-// in fp32 (~22 bits; the scheme of conv3d.hip).  Scales are powers of two taken on the device from max|planes|, max|W| and from norm
+// in fp32 (~22 bits; split_f16.h).  Scales are powers of two taken on the device from max|planes|, max|W| and from norm
 // bounds of the weights (|h1| <= max_j sum_c |W1[j][c]| * max|planes|: interpolation is convex), so nothing overflows fp16 by
 // construction and no pass over activations is needed.
 //
@@ -17,19 +17,10 @@
 // weight images (40 KB per head for the forward chain).
 #include <stdlib.h>
 
+#include "split_f16.h"
 #include "trifield_common.h"
 #include "trifield_mfma.h"
 
-typedef _Float16 half_t;
-typedef half_t half8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float tfm_scale_for(float amax) {          // 2^(14 - floor(log2 amax)): amax * scale in [2^14, 2^15)
-    const unsigned b = __float_as_uint(amax);
-    if (b == 0u || b >= 0x7f800000u) return 1.f;
-    int se = 14 - ((int)((b >> 23) & 0xffu) - 127);
-    se = se > 100 ? 100 : (se < -100 ? -100 : se);
-    return __uint_as_float((unsigned)(se + 127) << 23);
-}
 // x = hi + lo: hi = fp16(x) (v_cvt_pk_f16_f32, two per instruction), lo = fp16(x - hi) as ONE mixed-precision fma per element (v_fma_mix{lo,hi}_f16:
 // fp16 hi * -1 + fp32 x, rounded once to fp16) — the compiler's form is cvt back + subtract + cvt: 2.5 instructions per element instead of 1.5
 typedef half_t half2_ __attribute__((ext_vector_type(2)));
@@ -74,18 +65,13 @@ __device__ __forceinline__ float tfm_relu(float x) {
     asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(x));
     return r;
 }
-__device__ __forceinline__ floatx4 tfm_mma3(const half8 ah, const half8 al, const half8 bh, const half8 bl, floatx4 acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acc, 0, 0, 0);
-    return acc;
-}
 // sum over the four 16-lane rows of the wave (lanes l, l^16, l^32, l^48 hold the same row of the tile)
 __device__ __forceinline__ float tfm_rows_sum(float v) {
     auto t = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     v = __uint_as_float(t[0]) + __uint_as_float(t[1]);
-    t = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(t[0]) + __uint_as_float(t[1]);
+    float w = v;
+    asd_half_swap(v, w);
+    return v + w;
 }
 // k order of a fragment built from two accumulator blocks
 __host__ __device__ __forceinline__ int tfm_perm(int t, int g, int e) { return 32 * t + (e < 4 ? 4 * g + e : 16 + 4 * g + e - 4); }
@@ -108,8 +94,7 @@ __global__ __launch_bounds__(256) void tfm_pad_kernel(const float* __restrict__ 
         }
         *(floatx4*)(padded + 4 * q) = t;
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    m = asd_wave_max(m);
     if ((threadIdx.x & 63) == 0 && __float_as_uint(m) > __hip_atomic_load(amax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(amax, __float_as_uint(m));
 }
 
@@ -166,13 +151,13 @@ __global__ __launch_bounds__(256) void tfm_prep_kernel(const float* __restrict__
             const float aw1 = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])), aw2 = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
             const float amax_planes = __uint_as_float(((const unsigned*)prep)[0]);
             float* s = prep + 16 + 16 * head;
-            s[TFM_S_E] = tfm_scale_for(amax_planes);
-            s[TFM_S_W1] = tfm_scale_for(aw1);
-            s[TFM_S_W2] = tfm_scale_for(aw2);
-            s[TFM_S_H1] = tfm_scale_for(r1 * amax_planes * 1.0001f);
-            s[TFM_S_V2] = tfm_scale_for(b * 1.0001f);
-            s[TFM_S_U1] = tfm_scale_for(c2 * 1.0001f);
-            s[TFM_S_H2] = tfm_scale_for(r2 * r1 * amax_planes * 1.0002f);
+            s[TFM_S_E] = asd_split_scale<14>(amax_planes);
+            s[TFM_S_W1] = asd_split_scale<14>(aw1);
+            s[TFM_S_W2] = asd_split_scale<14>(aw2);
+            s[TFM_S_H1] = asd_split_scale<14>(r1 * amax_planes * 1.0001f);
+            s[TFM_S_V2] = asd_split_scale<14>(b * 1.0001f);
+            s[TFM_S_U1] = asd_split_scale<14>(c2 * 1.0001f);
+            s[TFM_S_H2] = asd_split_scale<14>(r2 * r1 * amax_planes * 1.0002f);
             sc[1] = s[TFM_S_W1]; sc[2] = s[TFM_S_W2];
         }
     }
@@ -356,7 +341,7 @@ __device__ __forceinline__ void tfm_layer2(const half8* a2h, const half8* a2l, i
         for (int t = 0; t < 2; ++t) {
             const half8 ah = a2h[(mb * 2 + t) * 64 + lane], al = a2l[(mb * 2 + t) * 64 + lane];
 #pragma unroll
-            for (int nb = 0; nb < NB; ++nb) z[mb][nb] = tfm_mma3(ah, al, bh[t][nb], bl[t][nb], z[mb][nb]);
+            for (int nb = 0; nb < NB; ++nb) z[mb][nb] = asd_mma3(ah, al, bh[t][nb], bl[t][nb], z[mb][nb]);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -456,13 +441,13 @@ __global__ __launch_bounds__(256, 2) void tfm_fwd_kernel(const tf_geom g, const 
 #pragma unroll
             for (int mb = 0; mb < 4; ++mb) {
                 const half8 ah = img_p[TFM_OFF_A1H / 8 + (mb * 3 + plane) * 64 + lane], al = img_p[TFM_OFF_A1L / 8 + (mb * 3 + plane) * 64 + lane];
-                acc[mb][nb] = tfm_mma3(ah, al, bh, bl, acc[mb][nb]);
+                acc[mb][nb] = asd_mma3(ah, al, bh, bl, acc[mb][nb]);
             }
             if (nb == 0 && feat) {
 #pragma unroll
                 for (int mb = 0; mb < 4; ++mb) {
                     const half8 ah = img_f[TFM_OFF_A1H / 8 + (mb * 3 + plane) * 64 + lane], al = img_f[TFM_OFF_A1L / 8 + (mb * 3 + plane) * 64 + lane];
-                    accf[mb][0] = tfm_mma3(ah, al, bh, bl, accf[mb][0]);
+                    accf[mb][0] = asd_mma3(ah, al, bh, bl, accf[mb][0]);
                 }
             }
         }, [](int, int) {});
@@ -645,7 +630,7 @@ __global__ __launch_bounds__(256, 2) void tfm_bwd_data_kernel(const tfm_bwd_args
 #pragma unroll
             for (int mb = 0; mb < 4; ++mb) {
                 const half8 ah = img[TFM_OFF_A1H / 8 + (mb * 3 + plane) * 64 + lane], al = img[TFM_OFF_A1L / 8 + (mb * 3 + plane) * 64 + lane];
-                acc[mb][nb] = tfm_mma3(ah, al, bh, bl, acc[mb][nb]);
+                acc[mb][nb] = asd_mma3(ah, al, bh, bl, acc[mb][nb]);
             }
         }, [](int, int) {});
         tfm_merge<FD>(acc);
@@ -721,7 +706,7 @@ __global__ __launch_bounds__(256, 2) void tfm_bwd_data_kernel(const tfm_bwd_args
             for (int t = 0; t < 2; ++t) {
                 const half8 ah = img[TFM_OFF_A1TH / 8 + (mb * 2 + t) * 64 + lane], al = img[TFM_OFF_A1TL / 8 + (mb * 2 + t) * 64 + lane];
 #pragma unroll
-                for (int nb = 0; nb < 4; ++nb) d[nb] = tfm_mma3(ah, al, vh[t][nb], vl[t][nb], d[nb]);
+                for (int nb = 0; nb < 4; ++nb) d[nb] = asd_mma3(ah, al, vh[t][nb], vl[t][nb], d[nb]);
             }
             if (FD) { d[1] += d[0]; d[2] += d[0]; d[3] += d[0]; }
 #pragma unroll
@@ -822,7 +807,7 @@ __global__ __launch_bounds__(256, 1) void tfm_bwd_weights_kernel(const tfm_bwd_a
 #pragma unroll
                 for (int mb = 0; mb < 4; ++mb) {
                     const half8 ah = img[TFM_OFF_A1H / 8 + (mb * 3 + plane) * 64 + lane], al = img[TFM_OFF_A1L / 8 + (mb * 3 + plane) * 64 + lane];
-                    zt[mb][nb] = tfm_mma3(ah, al, bh, bl, zt[mb][nb]);
+                    zt[mb][nb] = asd_mma3(ah, al, bh, bl, zt[mb][nb]);
                 }
             }, [&](int plane, int nb) __attribute__((always_inline)) {
                 const half8 z = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -858,7 +843,7 @@ __global__ __launch_bounds__(256, 1) void tfm_bwd_weights_kernel(const tfm_bwd_a
                 for (int r = 0; r < 4; ++r) m2t |= (unsigned long long)(zt[mb][nb][r] > 0.f) << ((mb * 4 + nb) * 4 + r);
         float gm = fmaxf(fmaxf(fabsf(G[0]), fabsf(G[1])), fmaxf(fabsf(G[2]), fabsf(G[3])));
 #pragma unroll
-        for (int off = 1; off < 64; off <<= 1) gm = fmaxf(gm, __shfl_xor(gm, off, 64));
+        for (int off = 1; off < 64; off <<= 1) gm = fmaxf(gm, __shfl_xor(gm, off, 64));       // (not asd_wave_max, which descends: this kernel spills, its code stays)
         gm = tfm_pow2_above(gm) * (FD ? 8.f : 1.f);      // FD: the centre block's operand sums up to seven terms
         if (gm > S) {                                    // wave-uniform, rare: the accumulators move to the new scale
             const float f = S / gm;                      // 0 for the first tile (the accumulators are zero)
@@ -909,7 +894,7 @@ __global__ __launch_bounds__(256, 1) void tfm_bwd_weights_kernel(const tfm_bwd_a
             for (int t = 0; t < 2; ++t) {
                 const half8 ah = img[TFM_OFF_A2H / 8 + (mb * 2 + t) * 64 + lane], al = img[TFM_OFF_A2L / 8 + (mb * 2 + t) * 64 + lane];
 #pragma unroll
-                for (int nb = 0; nb < 4; ++nb) zn[nb] = tfm_mma3(h1h[t][nb], h1l[t][nb], ah, al, zn[nb]);
+                for (int nb = 0; nb < 4; ++nb) zn[nb] = asd_mma3(h1h[t][nb], h1l[t][nb], ah, al, zn[nb]);
             }
             if (FD) { zn[1] += zn[0]; zn[2] += zn[0]; zn[3] += zn[0]; }
 #pragma unroll
@@ -988,7 +973,7 @@ __global__ __launch_bounds__(256, 1) void tfm_bwd_weights_kernel(const tfm_bwd_a
 #pragma unroll
             for (int mj = 0; mj < 4; ++mj)
 #pragma unroll
-                for (int kk = 0; kk < 2; ++kk) dw2[mj][mi] = tfm_mma3(gvh[mj][kk], gvl[mj][kk], hh[kk], hl[kk], dw2[mj][mi]);
+                for (int kk = 0; kk < 2; ++kk) dw2[mj][mi] = asd_mma3(gvh[mj][kk], gvl[mj][kk], hh[kk], hl[kk], dw2[mj][mi]);
             __builtin_amdgcn_sched_barrier(0);
         }
         // ---- v2 in the chain layout (from the mask): the row operand of u1 = v2 W2 in the swapped orientation
@@ -1025,7 +1010,7 @@ __global__ __launch_bounds__(256, 1) void tfm_bwd_weights_kernel(const tfm_bwd_a
             for (int t = 0; t < 2; ++t) {
                 const half8 ah = img[TFM_OFF_A2TH / 8 + (mb * 2 + t) * 64 + lane], al = img[TFM_OFF_A2TL / 8 + (mb * 2 + t) * 64 + lane];
 #pragma unroll
-                for (int nb = 0; nb < 4; ++nb) zn[nb] = tfm_mma3(vh[t][nb], vl[t][nb], ah, al, zn[nb]);
+                for (int nb = 0; nb < 4; ++nb) zn[nb] = asd_mma3(vh[t][nb], vl[t][nb], ah, al, zn[nb]);
             }
             if (FD) { zn[1] += zn[0]; zn[2] += zn[0]; zn[3] += zn[0]; }
 #pragma unroll
@@ -1075,7 +1060,7 @@ __global__ __launch_bounds__(256, 1) void tfm_bwd_weights_kernel(const tfm_bwd_a
 #pragma unroll
                 for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-                    for (int kk = 0; kk < 2; ++kk) dw1[mi][2 * plane + hf] = tfm_mma3(gvh[mi][kk], gvl[mi][kk], eh[kk], el[kk], dw1[mi][2 * plane + hf]);
+                    for (int kk = 0; kk < 2; ++kk) dw1[mi][2 * plane + hf] = asd_mma3(gvh[mi][kk], gvl[mi][kk], eh[kk], el[kk], dw1[mi][2 * plane + hf]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }

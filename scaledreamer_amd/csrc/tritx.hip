@@ -8,7 +8,7 @@
 // gfx950 has no reduced-precision fp32 matrix path (v_mfma_f32_*_f32 runs at the vector rate, 1/16 of fp16), so every fp32 operand is
 // split into two fp16 planes, x * s = hi + lo with s a power of two PER ROW of the operand as the product sees it (the contraction runs
 // along the row, so the scales factor out), and a product is hi.hi + hi.lo + lo.hi accumulated in fp32: 22 bits per operand at a third
-// of the fp16 rate (csrc/conv3d.hip's arithmetic).  Linear layers run the three products as ONE K-concatenated fp16 GEMM
+// of the fp16 rate (csrc/split_f16.h).  Linear layers run the three products as ONE K-concatenated fp16 GEMM
 // ([hi | hi | lo] x [hi | lo | hi]^T, gemm_f16_kernel with an fp32 result) followed by an fp32 epilogue (row and column scales, bias,
 // GELU, residual); attention is its own flash kernel on 32x32x16 MFMAs (attention part below).
 //
@@ -24,41 +24,21 @@
 
 #include "asd_common.h"
 #include "gemm_tile.h"      // ASD_CFG_*: the names of the tile table's rows
+#include "split_f16.h"
 
 namespace {
 
-typedef _Float16 h16;
-typedef __attribute__((ext_vector_type(4))) _Float16 h16x4;
-
-// power-of-two scale that puts `amax` into [2^14, 2^15); 1 for an all-zero row
-__device__ __forceinline__ float tx_scale_for(float amax) {
-    if (!(amax > 0.f)) return 1.f;
-    int e;
-    (void)frexpf(amax, &e);                 // amax = m * 2^e, m in [0.5, 1)
-    e = 15 - e;
-    e = e > 100 ? 100 : (e < -100 ? -100 : e);
-    return ldexpf(1.f, e);
-}
-__device__ __forceinline__ float tx_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 __device__ __forceinline__ float tx_wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
-}
-__device__ __forceinline__ void tx_split(float xs, h16& hi, h16& lo) {
-    hi = (h16)xs;
-    lo = (h16)(xs - (float)hi);
 }
 
 // ---- operand planes -------------------------------------------------------------------------------------------------------------------
 // rows of X [R, C] (ld) -> plane [R, 3 C] fp16: LAYOUT 0 (the A side of a product) [hi | hi | lo], 1 (the W side) [hi | lo | hi];
 // inv[r] = 1 / scale of row r.  One wave per row.
 template <int LAYOUT>
-__global__ __launch_bounds__(256) void tx_split_rows_kernel(const float* __restrict__ x, int R, int C, int ld, h16* __restrict__ plane,
+__global__ __launch_bounds__(256) void tx_split_rows_kernel(const float* __restrict__ x, int R, int C, int ld, half_t* __restrict__ plane,
                                                             float* __restrict__ inv) {
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (r >= R) return;
@@ -68,17 +48,17 @@ __global__ __launch_bounds__(256) void tx_split_rows_kernel(const float* __restr
         const float4 v = *reinterpret_cast<const float4*>(row + c);
         amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
     }
-    const float s = tx_scale_for(tx_wave_max(amax));
+    const float s = asd_split_scale<14, 126>(asd_wave_max(amax));
     if (lane == 0) inv[r] = 1.f / s;
-    h16* dst = plane + (size_t)r * 3 * C;
+    half_t* dst = plane + (size_t)r * 3 * C;
     for (int c = lane * 4; c < C; c += 256) {
         const float4 v = *reinterpret_cast<const float4*>(row + c);
-        h16 h0, h1, h2, h3, l0, l1, l2, l3;
-        tx_split(v.x * s, h0, l0); tx_split(v.y * s, h1, l1); tx_split(v.z * s, h2, l2); tx_split(v.w * s, h3, l3);
-        const h16x4 hi = {h0, h1, h2, h3}, lo = {l0, l1, l2, l3};
-        *reinterpret_cast<h16x4*>(dst + c) = hi;
-        *reinterpret_cast<h16x4*>(dst + C + c) = LAYOUT == 0 ? hi : lo;
-        *reinterpret_cast<h16x4*>(dst + 2 * C + c) = LAYOUT == 0 ? lo : hi;
+        half_t h0, h1, h2, h3, l0, l1, l2, l3;
+        asd_split(v.x * s, h0, l0); asd_split(v.y * s, h1, l1); asd_split(v.z * s, h2, l2); asd_split(v.w * s, h3, l3);
+        const half4 hi = {h0, h1, h2, h3}, lo = {l0, l1, l2, l3};
+        *reinterpret_cast<half4*>(dst + c) = hi;
+        *reinterpret_cast<half4*>(dst + C + c) = LAYOUT == 0 ? hi : lo;
+        *reinterpret_cast<half4*>(dst + 2 * C + c) = LAYOUT == 0 ? lo : hi;
     }
 }
 
@@ -119,20 +99,20 @@ __global__ __launch_bounds__(256) void tx_colstat_kernel(const float* __restrict
 // X [R, C] -> plane of X^T: [C, 3 Rp] fp16 (Rp >= R, zero beyond R), per-row (= column of X) scales from colmax; 64 x 64 tiles through LDS
 template <int LAYOUT>
 __global__ __launch_bounds__(256) void tx_split_cols_kernel(const float* __restrict__ x, int R, int C, int ld, int Rp,
-                                                            const unsigned* __restrict__ colmax, h16* __restrict__ plane,
+                                                            const unsigned* __restrict__ colmax, half_t* __restrict__ plane,
                                                             float* __restrict__ inv) {
-    __shared__ h16 thi[64][66], tlo[64][66];      // [col][row], padded
+    __shared__ half_t thi[64][66], tlo[64][66];      // [col][row], padded
     const int c0 = blockIdx.x * 64, r0 = blockIdx.y * 64;
     const int cl = threadIdx.x & 63, q = threadIdx.x >> 6;
     const int c = c0 + cl;
-    const float s = c < C ? tx_scale_for(__uint_as_float(colmax[c])) : 1.f;
+    const float s = c < C ? asd_split_scale_bits<14, 126>(colmax[c]) : 1.f;
     if (blockIdx.y == 0 && q == 0 && c < C) inv[c] = 1.f / s;
 #pragma unroll 4
     for (int i = 0; i < 16; ++i) {
         const int rl = q * 16 + i, r = r0 + rl;
         const float v = (r < R && c < C) ? x[(size_t)r * ld + c] : 0.f;
-        h16 hi, lo;
-        tx_split(v * s, hi, lo);
+        half_t hi, lo;
+        asd_split(v * s, hi, lo);
         thi[cl][rl] = hi; tlo[cl][rl] = lo;
     }
     __syncthreads();
@@ -142,8 +122,8 @@ __global__ __launch_bounds__(256) void tx_split_cols_kernel(const float* __restr
     for (int i = 0; i < 16; ++i) {
         const int col = q * 16 + i;
         if (c0 + col >= C) continue;
-        h16* dst = plane + (size_t)(c0 + col) * 3 * Rp + r0 + rl;
-        const h16 hi = thi[col][rl], lo = tlo[col][rl];
+        half_t* dst = plane + (size_t)(c0 + col) * 3 * Rp + r0 + rl;
+        const half_t hi = thi[col][rl], lo = tlo[col][rl];
         dst[0] = hi;
         dst[Rp] = LAYOUT == 0 ? hi : lo;
         dst[2 * (size_t)Rp] = LAYOUT == 0 ? lo : hi;
@@ -195,19 +175,19 @@ __global__ __launch_bounds__(256) void tx_epilogue_kernel(const float* __restric
 
 // the A-operand planes of a row that a wave holds in registers (float4 v[i] = columns 4 lane + 256 i): what tx_split_rows_kernel<0> would
 // write, without the row going through memory again
-__device__ __forceinline__ void tx_row_planes(const float4 (&v)[4], int D, int lane, float amax_lane, h16* __restrict__ dst, float* __restrict__ inv) {
-    const float s = tx_scale_for(tx_wave_max(amax_lane));
+__device__ __forceinline__ void tx_row_planes(const float4 (&v)[4], int D, int lane, float amax_lane, half_t* __restrict__ dst, float* __restrict__ inv) {
+    const float s = asd_split_scale<14, 126>(asd_wave_max(amax_lane));
     if (lane == 0) *inv = 1.f / s;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int c = lane * 4 + 256 * i;
         if (c < D) {
-            h16 h0, h1, h2, h3, l0, l1, l2, l3;
-            tx_split(v[i].x * s, h0, l0); tx_split(v[i].y * s, h1, l1); tx_split(v[i].z * s, h2, l2); tx_split(v[i].w * s, h3, l3);
-            const h16x4 hi = {h0, h1, h2, h3}, lo = {l0, l1, l2, l3};
-            *reinterpret_cast<h16x4*>(dst + c) = hi;
-            *reinterpret_cast<h16x4*>(dst + D + c) = hi;
-            *reinterpret_cast<h16x4*>(dst + 2 * D + c) = lo;
+            half_t h0, h1, h2, h3, l0, l1, l2, l3;
+            asd_split(v[i].x * s, h0, l0); asd_split(v[i].y * s, h1, l1); asd_split(v[i].z * s, h2, l2); asd_split(v[i].w * s, h3, l3);
+            const half4 hi = {h0, h1, h2, h3}, lo = {l0, l1, l2, l3};
+            *reinterpret_cast<half4*>(dst + c) = hi;
+            *reinterpret_cast<half4*>(dst + D + c) = hi;
+            *reinterpret_cast<half4*>(dst + 2 * D + c) = lo;
         }
     }
 }
@@ -216,7 +196,7 @@ __device__ __forceinline__ void tx_row_planes(const float4 (&v)[4], int D, int l
 __global__ __launch_bounds__(256) void tx_layernorm_fwd_kernel(const float* __restrict__ x, int M, int D, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, float eps, float* __restrict__ y,
                                                                float* __restrict__ stats /*[M,2] mean, rstd*/,
-                                                               h16* __restrict__ plane /* optional: the row's A-operand planes [M, 3D] (hi | hi | lo) */,
+                                                               half_t* __restrict__ plane /* optional: the row's A-operand planes [M, 3D] (hi | hi | lo) */,
                                                                float* __restrict__ inv /* ... and 1 / its scale */) {
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (r >= M) return;
@@ -264,7 +244,7 @@ __global__ __launch_bounds__(256) void tx_layernorm_fwd_kernel(const float* __re
 __global__ __launch_bounds__(256) void tx_layernorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ stats,
                                                                const float* __restrict__ gamma, int M, int D, const float* __restrict__ dres,
                                                                float* __restrict__ dx, float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                               h16* __restrict__ plane /* optional: A-operand planes of the dx rows [M, 3D] */,
+                                                               half_t* __restrict__ plane /* optional: A-operand planes of the dx rows [M, 3D] */,
                                                                float* __restrict__ inv) {
     const int lane = threadIdx.x & 63, wave = blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = gridDim.x * 4;
     float4 g4[4], ag[4], ab[4];
@@ -343,8 +323,6 @@ __global__ __launch_bounds__(256) void tx_layernorm_bwd_kernel(const float* __re
 // l ^ 32, and — after conversion to fp16 hi / lo — those same registers ARE the B operand of O^T = V^T P^T in a permuted key order
 // (k-step u, position p of half h is key 16 u + (p & 3) + 8 (p >> 2) + 4 h), in which the V^T fragments are loaded: P never moves.
 #define TX_HD 48
-typedef __attribute__((ext_vector_type(8))) _Float16 h16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 struct tx_absmax_args { const float* x[4]; int L[4], ld[4]; };
 // max |x| per (tensor, head): grid (blocks of 256 rows, H, tensors); 12 float4 lanes per row, one atomic per block
@@ -362,7 +340,7 @@ __global__ __launch_bounds__(256) void tx_attn_absmax_kernel(const tx_absmax_arg
             m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
         }
     }
-    m = tx_wave_max(m);
+    m = asd_wave_max(m);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) atomicMax(amax + z * H + h, __float_as_uint(fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]))));
@@ -370,32 +348,32 @@ __global__ __launch_bounds__(256) void tx_attn_absmax_kernel(const tx_absmax_arg
 
 // row-major planes [H][Lp][48] (rows >= L zero): hi, lo
 __global__ __launch_bounds__(256) void tx_attn_prep_rows_kernel(const float* __restrict__ x, int L, int Lp, int ld, int H, const unsigned* __restrict__ amax,
-                                                                h16* __restrict__ hi, h16* __restrict__ lo) {
+                                                                half_t* __restrict__ hi, half_t* __restrict__ lo) {
     const int h = blockIdx.y;
-    const float s = tx_scale_for(__uint_as_float(amax[h]));
+    const float s = asd_split_scale_bits<14, 126>(amax[h]);
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;      // one thread per 4 elements
     const int r = (int)(t / (TX_HD / 4)), c = (int)(t % (TX_HD / 4)) * 4;
     if (r >= Lp) return;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (r < L) v = *reinterpret_cast<const float4*>(x + (size_t)r * ld + h * TX_HD + c);
-    h16 h0, h1, h2, h3, l0, l1, l2, l3;
-    tx_split(v.x * s, h0, l0); tx_split(v.y * s, h1, l1); tx_split(v.z * s, h2, l2); tx_split(v.w * s, h3, l3);
+    half_t h0, h1, h2, h3, l0, l1, l2, l3;
+    asd_split(v.x * s, h0, l0); asd_split(v.y * s, h1, l1); asd_split(v.z * s, h2, l2); asd_split(v.w * s, h3, l3);
     const size_t o = ((size_t)h * Lp + r) * TX_HD + c;
-    *reinterpret_cast<h16x4*>(hi + o) = h16x4{h0, h1, h2, h3};
-    *reinterpret_cast<h16x4*>(lo + o) = h16x4{l0, l1, l2, l3};
+    *reinterpret_cast<half4*>(hi + o) = half4{h0, h1, h2, h3};
+    *reinterpret_cast<half4*>(lo + o) = half4{l0, l1, l2, l3};
 }
 
 // transposed planes [H][48][Lp] (columns >= L zero): 64 rows of x per block through LDS
 __global__ __launch_bounds__(256) void tx_attn_prep_cols_kernel(const float* __restrict__ x, int L, int Lp, int ld, int H, const unsigned* __restrict__ amax,
-                                                                h16* __restrict__ hi, h16* __restrict__ lo) {
-    __shared__ h16 thi[TX_HD][66], tlo[TX_HD][66];
+                                                                half_t* __restrict__ hi, half_t* __restrict__ lo) {
+    __shared__ half_t thi[TX_HD][66], tlo[TX_HD][66];
     const int h = blockIdx.y, r0 = blockIdx.x * 64;
-    const float s = tx_scale_for(__uint_as_float(amax[h]));
+    const float s = asd_split_scale_bits<14, 126>(amax[h]);
     for (int t = threadIdx.x; t < 64 * TX_HD; t += 256) {
         const int rl = t / TX_HD, c = t % TX_HD;
         const float v = r0 + rl < L ? x[(size_t)(r0 + rl) * ld + h * TX_HD + c] : 0.f;
-        h16 a, b;
-        tx_split(v * s, a, b);
+        half_t a, b;
+        asd_split(v * s, a, b);
         thi[c][rl] = a; tlo[c][rl] = b;
     }
     __syncthreads();
@@ -408,16 +386,6 @@ __global__ __launch_bounds__(256) void tx_attn_prep_cols_kernel(const float* __r
     }
 }
 
-__device__ __forceinline__ f32x16 tx_mfma(const h16x8 a, const h16x8 b, const f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-// hi.hi + hi.lo + lo.hi
-__device__ __forceinline__ f32x16 tx_mfma3(const h16x8 ah, const h16x8 al, const h16x8 bh, const h16x8 bl, f32x16 c) {
-    c = tx_mfma(ah, bh, c);
-    c = tx_mfma(ah, bl, c);
-    c = tx_mfma(al, bh, c);
-    return c;
-}
 __device__ __forceinline__ int tx_row_of(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }     // C / D row of register r
 
 // ---- streamed tiles through LDS: the four waves of a block walk the same sequence of 32-token tiles -----------------------------------
@@ -445,31 +413,26 @@ struct TxStage {
         _Pragma("unroll") for (int k_ = 0; k_ < (NR_); ++k_)                                                                          \
             *reinterpret_cast<uint4*>((LDS) + k_ * TX_RT + (threadIdx.x / 6) * TX_RP + (threadIdx.x % 6) * 8) = (ST).r[k_];         \
         _Pragma("unroll") for (int k_ = 0; k_ < (NT_); ++k_) {                                                                        \
-            h16* d_ = (LDS) + (NR_) * TX_RT + k_ * TX_TT + (threadIdx.x >> 2) * TX_TP + (threadIdx.x & 3) * 8;                       \
+            half_t* d_ = (LDS) + (NR_) * TX_RT + k_ * TX_TT + (threadIdx.x >> 2) * TX_TP + (threadIdx.x & 3) * 8;                       \
             *reinterpret_cast<uint2*>(d_) = make_uint2((ST).r[(NR_) + k_].x, (ST).r[(NR_) + k_].y);                                   \
             *reinterpret_cast<uint2*>(d_ + 4) = make_uint2((ST).r[(NR_) + k_].z, (ST).r[(NR_) + k_].w);                             \
         }                                                                                                                             \
     }
-__device__ __forceinline__ h16x8 tx_lds_row(const h16* tile, int row, int t, int half) {       // A / B fragment of k-step t from a row-major tile
-    return *reinterpret_cast<const h16x8*>(tile + row * TX_RP + 16 * t + 8 * half);
+__device__ __forceinline__ half8 tx_lds_row(const half_t* tile, int row, int t, int half) {       // A / B fragment of k-step t from a row-major tile
+    return *reinterpret_cast<const half8*>(tile + row * TX_RP + 16 * t + 8 * half);
 }
-__device__ __forceinline__ h16x8 tx_lds_perm(const h16* tile, int d, int u, int half) {        // permuted-order fragment from a transposed tile
-    const h16x4 a = *reinterpret_cast<const h16x4*>(tile + d * TX_TP + 16 * u + 4 * half), b = *reinterpret_cast<const h16x4*>(tile + d * TX_TP + 16 * u + 4 * half + 8);
-    return h16x8{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+__device__ __forceinline__ half8 tx_lds_perm(const half_t* tile, int d, int u, int half) {        // permuted-order fragment from a transposed tile
+    const half4 a = *reinterpret_cast<const half4*>(tile + d * TX_TP + 16 * u + 4 * half), b = *reinterpret_cast<const half4*>(tile + d * TX_TP + 16 * u + 4 * half + 8);
+    return half8{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
 }
 
 // 2^x on v_exp_f32 alone (arguments here are <= 0 or -inf: no range reduction / denormal fix-up needed)
 __device__ __forceinline__ float tx_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-// the value of lane l ^ 32 (v_permlane32_swap: VALU, no LDS round trip)
-__device__ __forceinline__ float tx_other_half(float v) {
-    auto t = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(((threadIdx.x >> 5) & 1) ? t[0] : t[1]);
-}
 #define TX_PSCALE 16384.f       // probabilities (<= 1) are split at 2^14
 
 // O [Lq, ldo] (fp32), lse2 [H][Lq] = log2 sum_j 2^(s2_ij), s2 = (q . k) log2(e) / sqrt(48).  grid (ceil(Lq / 128), H), 4 waves x 32 queries
-__global__ __launch_bounds__(256, 3) void tx_attn_fwd_kernel(const h16* __restrict__ qh, const h16* __restrict__ ql, const h16* __restrict__ kh,
-                                                          const h16* __restrict__ kl, const h16* __restrict__ vth, const h16* __restrict__ vtl,
+__global__ __launch_bounds__(256, 3) void tx_attn_fwd_kernel(const half_t* __restrict__ qh, const half_t* __restrict__ ql, const half_t* __restrict__ kh,
+                                                          const half_t* __restrict__ kl, const half_t* __restrict__ vth, const half_t* __restrict__ vtl,
                                                           const unsigned* __restrict__ amax /*[3][H]: q, k, v*/, int Lq, int Lqp, int Lk, int Lkp, int H,
                                                           float* __restrict__ o, int ldo, float* __restrict__ lse2,
                                                           float* __restrict__ part /* gridDim.z > 1: [z][Lq][H 48] unnormalised O, then [z][H][Lq] m, [z][H][Lq] l */) {
@@ -477,34 +440,34 @@ __global__ __launch_bounds__(256, 3) void tx_attn_fwd_kernel(const h16* __restri
     const int q0 = blockIdx.x * 128 + wave * 32;       // (waves past Lq work on zero rows of the padded planes and store nothing: every wave meets the barriers)
     const int j = lane & 31, half = lane >> 5;
     const float c1 = 1.4426950408889634f * 0.14433756729740643f /* log2(e) / sqrt(48) */ /
-                     (tx_scale_for(__uint_as_float(amax[h])) * tx_scale_for(__uint_as_float(amax[H + h])));
-    const float cv = 1.f / (tx_scale_for(__uint_as_float(amax[2 * H + h])) * TX_PSCALE);
+                     (asd_split_scale_bits<14, 126>(amax[h]) * asd_split_scale_bits<14, 126>(amax[H + h]));
+    const float cv = 1.f / (asd_split_scale_bits<14, 126>(amax[2 * H + h]) * TX_PSCALE);
     // Q fragments: B operand of S^T = K Q^T — lane (query j, half): d = 16 t + 8 half .. + 7
-    h16x8 bqh[3], bql[3];
+    half8 bqh[3], bql[3];
     {
         const size_t qrow = ((size_t)h * Lqp + q0 + j) * TX_HD + 8 * half;
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
-            bqh[t] = *reinterpret_cast<const h16x8*>(qh + qrow + 16 * t);
-            bql[t] = *reinterpret_cast<const h16x8*>(ql + qrow + 16 * t);
+            bqh[t] = *reinterpret_cast<const half8*>(qh + qrow + 16 * t);
+            bql[t] = *reinterpret_cast<const half8*>(ql + qrow + 16 * t);
         }
     }
-    f32x16 ot[2];
+    floatx16 ot[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { ot[0][r] = 0.f; ot[1][r] = 0.f; }
     float m = -INFINITY, l = 0.f;
-    const h16* kbase_h = kh + (size_t)h * Lkp * TX_HD, * kbase_l = kl + (size_t)h * Lkp * TX_HD;
-    const h16* vbase_h = vth + (size_t)h * TX_HD * Lkp, * vbase_l = vtl + (size_t)h * TX_HD * Lkp;
+    const half_t* kbase_h = kh + (size_t)h * Lkp * TX_HD, * kbase_l = kl + (size_t)h * Lkp * TX_HD;
+    const half_t* vbase_h = vth + (size_t)h * TX_HD * Lkp, * vbase_l = vtl + (size_t)h * TX_HD * Lkp;
     // streamed per key block: K rows (hi, lo) and V^T (hi, lo), double-buffered in LDS
     constexpr int STAGE = 2 * TX_RT + 2 * TX_TT;
-    __shared__ __attribute__((aligned(16))) h16 lds[2 * STAGE];
+    __shared__ __attribute__((aligned(16))) half_t lds[2 * STAGE];
     TxStage<2, 2> st_regs;
     // the key range is cut over blockIdx.z (more, shorter blocks: 1.5 waves per SIMD otherwise); the pieces meet in tx_attn_fwd_combine_kernel
     const int k_per = ((Lk + (int)gridDim.z - 1) / (int)gridDim.z + 31) & ~31;
     const int k_begin = (int)blockIdx.z * k_per, k_end = min(Lk, k_begin + k_per);
     if (k_begin < k_end) {
-        const h16* const rs[2] = {kbase_h + (size_t)k_begin * TX_HD, kbase_l + (size_t)k_begin * TX_HD};
-        const h16* const ts[2] = {vbase_h + k_begin, vbase_l + k_begin};
+        const half_t* const rs[2] = {kbase_h + (size_t)k_begin * TX_HD, kbase_l + (size_t)k_begin * TX_HD};
+        const half_t* const ts[2] = {vbase_h + k_begin, vbase_l + k_begin};
         TX_STAGE_LOAD(st_regs, 2, 2, rs, ts, Lkp);
         TX_STAGE_STORE(st_regs, 2, 2, lds);
     }
@@ -513,16 +476,16 @@ __global__ __launch_bounds__(256, 3) void tx_attn_fwd_kernel(const h16* __restri
     for (int k0 = k_begin; k0 < k_end; k0 += 32, buf ^= 1) {
         const bool more = k0 + 32 < k_end;
         if (more) {
-            const h16* const rs[2] = {kbase_h + (size_t)(k0 + 32) * TX_HD, kbase_l + (size_t)(k0 + 32) * TX_HD};
-            const h16* const ts[2] = {vbase_h + k0 + 32, vbase_l + k0 + 32};
+            const half_t* const rs[2] = {kbase_h + (size_t)(k0 + 32) * TX_HD, kbase_l + (size_t)(k0 + 32) * TX_HD};
+            const half_t* const ts[2] = {vbase_h + k0 + 32, vbase_l + k0 + 32};
             TX_STAGE_LOAD(st_regs, 2, 2, rs, ts, Lkp);
         }
-        const h16* tile = lds + buf * STAGE;
-        f32x16 st;
+        const half_t* tile = lds + buf * STAGE;
+        floatx16 st;
 #pragma unroll
         for (int r = 0; r < 16; ++r) st[r] = 0.f;
 #pragma unroll
-        for (int t = 0; t < 3; ++t) st = tx_mfma3(tx_lds_row(tile, j, t, half), tx_lds_row(tile + TX_RT, j, t, half), bqh[t], bql[t], st);
+        for (int t = 0; t < 3; ++t) st = asd_mma3(tx_lds_row(tile, j, t, half), tx_lds_row(tile + TX_RT, j, t, half), bqh[t], bql[t], st);
         float mb = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -531,20 +494,20 @@ __global__ __launch_bounds__(256, 3) void tx_attn_fwd_kernel(const h16* __restri
             st[r] = s2;
             mb = fmaxf(mb, s2);
         }
-        mb = fmaxf(mb, tx_other_half(mb));
+        mb = fmaxf(mb, asd_other_half(mb));
         const float m_new = fmaxf(m, mb);
         const float alpha = tx_exp2(m - m_new);           // m = -inf on the first block: 0
         float lb = 0.f;
-        h16x8 ph[2], pl[2];
+        half8 ph[2], pl[2];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const float p = tx_exp2(st[r] - m_new);
             lb += p;
-            h16 a, b;
-            tx_split(p * TX_PSCALE, a, b);
+            half_t a, b;
+            asd_split(p * TX_PSCALE, a, b);
             ph[r >> 3][r & 7] = a; pl[r >> 3][r & 7] = b;
         }
-        lb += tx_other_half(lb);
+        lb += asd_other_half(lb);
         l = l * alpha + lb;
         m = m_new;
 #pragma unroll
@@ -555,15 +518,15 @@ __global__ __launch_bounds__(256, 3) void tx_attn_fwd_kernel(const h16* __restri
             const int d = 32 * mt + j;
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                h16x8 ah, al;
+                half8 ah, al;
                 if (d < TX_HD) {
                     ah = tx_lds_perm(tile + 2 * TX_RT, d, u, half);
                     al = tx_lds_perm(tile + 2 * TX_RT + TX_TT, d, u, half);
                 } else {
-                    ah = h16x8{0, 0, 0, 0, 0, 0, 0, 0};
+                    ah = half8{0, 0, 0, 0, 0, 0, 0, 0};
                     al = ah;
                 }
-                ot[mt] = tx_mfma3(ah, al, ph[u], pl[u], ot[mt]);
+                ot[mt] = asd_mma3(ah, al, ph[u], pl[u], ot[mt]);
             }
         }
         if (more) { TX_STAGE_STORE(st_regs, 2, 2, lds + (buf ^ 1) * STAGE); }
@@ -645,14 +608,14 @@ __global__ __launch_bounds__(256) void tx_attn_rowdot_kernel(const float* __rest
 }
 
 // 8 halves of a transposed plane row at the permuted positions of k-step u: columns c0 + 16 u + 4 half + {0..3} and + 8
-__device__ __forceinline__ h16x8 tx_load_perm(const h16* __restrict__ rowp, int c0, int u, int half) {
-    const h16x4 a = *reinterpret_cast<const h16x4*>(rowp + c0 + 16 * u + 4 * half), b = *reinterpret_cast<const h16x4*>(rowp + c0 + 16 * u + 4 * half + 8);
-    return h16x8{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+__device__ __forceinline__ half8 tx_load_perm(const half_t* __restrict__ rowp, int c0, int u, int half) {
+    const half4 a = *reinterpret_cast<const half4*>(rowp + c0 + 16 * u + 4 * half), b = *reinterpret_cast<const half4*>(rowp + c0 + 16 * u + 4 * half + 8);
+    return half8{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
 }
 
 struct tx_attn_bwd_args {
-    const h16 *qh, *ql, *kh, *kl, *vh, *vl, *doh, *dol;     // row-major planes [H][Lp][48]
-    const h16 *qth, *qtl, *doth, *dotl, *kth, *ktl;         // transposed planes [H][48][Lp]
+    const half_t *qh, *ql, *kh, *kl, *vh, *vl, *doh, *dol;     // row-major planes [H][Lp][48]
+    const half_t *qth, *qtl, *doth, *dotl, *kth, *ktl;         // transposed planes [H][48][Lp]
     const unsigned* amax;                                   // [4][H]: q, k, v, dO
     const float *lse2, *dsum;                               // [H][Lq]
     int Lq, Lqp, Lk, Lkp, H;
@@ -662,7 +625,7 @@ struct tx_attn_bwd_args {
 };
 // static bound of |P (dP - D)| per head: |dP_ij| <= 48 max|dO| max|V|, |D_i| <= 48 max|dO| max|O| and |O| <= max|V| (convex combination)
 __device__ __forceinline__ float tx_ds_scale(const unsigned* amax, int H, int h) {
-    return tx_scale_for(96.f * __uint_as_float(amax[3 * H + h]) * __uint_as_float(amax[2 * H + h]));
+    return asd_split_scale<14, 126>(96.f * __uint_as_float(amax[3 * H + h]) * __uint_as_float(amax[2 * H + h]));
 }
 
 // dK, dV: a wave owns 32 keys and walks the query blocks.  S = Q K^T (rows = queries, column = the lane's key), P = 2^(S2 - lse2),
@@ -671,27 +634,27 @@ __global__ __launch_bounds__(256, 2) void tx_attn_bwd_kv_kernel(const tx_attn_bw
     const int h = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int k0 = blockIdx.x * 128 + wave * 32;        // (waves past Lk work on zero rows of the padded planes and store nothing)
     const int j = lane & 31, half = lane >> 5, H = a.H;
-    const float sq = tx_scale_for(__uint_as_float(a.amax[h])), sk = tx_scale_for(__uint_as_float(a.amax[H + h]));
-    const float sv = tx_scale_for(__uint_as_float(a.amax[2 * H + h])), sdo = tx_scale_for(__uint_as_float(a.amax[3 * H + h]));
+    const float sq = asd_split_scale_bits<14, 126>(a.amax[h]), sk = asd_split_scale_bits<14, 126>(a.amax[H + h]);
+    const float sv = asd_split_scale_bits<14, 126>(a.amax[2 * H + h]), sdo = asd_split_scale_bits<14, 126>(a.amax[3 * H + h]);
     const float sds = tx_ds_scale(a.amax, H, h);
     const float c1 = 1.4426950408889634f * 0.14433756729740643f / (sq * sk), cdp = 1.f / (sdo * sv);
     // resident B operands: K^T and V^T columns = this lane's key, d range 16 t + 8 half .. + 7
-    h16x8 bkh[3], bkl[3], bvh[3], bvl[3];
+    half8 bkh[3], bkl[3], bvh[3], bvl[3];
     {
         const size_t krow = ((size_t)h * a.Lkp + k0 + j) * TX_HD + 8 * half;
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
-            bkh[t] = *reinterpret_cast<const h16x8*>(a.kh + krow + 16 * t); bkl[t] = *reinterpret_cast<const h16x8*>(a.kl + krow + 16 * t);
-            bvh[t] = *reinterpret_cast<const h16x8*>(a.vh + krow + 16 * t); bvl[t] = *reinterpret_cast<const h16x8*>(a.vl + krow + 16 * t);
+            bkh[t] = *reinterpret_cast<const half8*>(a.kh + krow + 16 * t); bkl[t] = *reinterpret_cast<const half8*>(a.kl + krow + 16 * t);
+            bvh[t] = *reinterpret_cast<const half8*>(a.vh + krow + 16 * t); bvl[t] = *reinterpret_cast<const half8*>(a.vl + krow + 16 * t);
         }
     }
-    f32x16 dvt[2], dkt[2];
+    floatx16 dvt[2], dkt[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { dvt[0][r] = dvt[1][r] = dkt[0][r] = dkt[1][r] = 0.f; }
-    const h16 *qbh = a.qh + (size_t)h * a.Lqp * TX_HD, *qbl = a.ql + (size_t)h * a.Lqp * TX_HD;
-    const h16 *dbh = a.doh + (size_t)h * a.Lqp * TX_HD, *dbl = a.dol + (size_t)h * a.Lqp * TX_HD;
-    const h16 *qtbh = a.qth + (size_t)h * TX_HD * a.Lqp, *qtbl = a.qtl + (size_t)h * TX_HD * a.Lqp;
-    const h16 *dtbh = a.doth + (size_t)h * TX_HD * a.Lqp, *dtbl = a.dotl + (size_t)h * TX_HD * a.Lqp;
+    const half_t *qbh = a.qh + (size_t)h * a.Lqp * TX_HD, *qbl = a.ql + (size_t)h * a.Lqp * TX_HD;
+    const half_t *dbh = a.doh + (size_t)h * a.Lqp * TX_HD, *dbl = a.dol + (size_t)h * a.Lqp * TX_HD;
+    const half_t *qtbh = a.qth + (size_t)h * TX_HD * a.Lqp, *qtbl = a.qtl + (size_t)h * TX_HD * a.Lqp;
+    const half_t *dtbh = a.doth + (size_t)h * TX_HD * a.Lqp, *dtbl = a.dotl + (size_t)h * TX_HD * a.Lqp;
     const float *lse = a.lse2 + (size_t)h * a.Lq, *dsm = a.dsum + (size_t)h * a.Lq;
     const bool key_ok = k0 + j < a.Lk;
     // the query range is cut over blockIdx.z (balance: four short blocks per slot instead of 384 long ones on 512 slots; the
@@ -700,7 +663,7 @@ __global__ __launch_bounds__(256, 2) void tx_attn_bwd_kv_kernel(const tx_attn_bw
     const int q_begin = (int)blockIdx.z * q_per, q_end = min(a.Lq, q_begin + q_per);
     // streamed per query block: Q and dO rows (row-major) and Q^T, dO^T (transposed), hi / lo each, double-buffered in LDS
     constexpr int STAGE = 4 * TX_RT + 4 * TX_TT;
-    __shared__ __attribute__((aligned(16))) h16 lds[2 * STAGE];
+    __shared__ __attribute__((aligned(16))) half_t lds[2 * STAGE];
     __shared__ float row_stats[2][64];            // [stage][lse2 of the tile's 32 queries | D of the same]
     TxStage<4, 4> st_regs;
     float stat_reg = 0.f;
@@ -714,8 +677,8 @@ __global__ __launch_bounds__(256, 2) void tx_attn_bwd_kv_kernel(const tx_attn_bw
     if (q_begin < q_end) {
         stat_load(q_begin);
         if (stat_i >= 0) row_stats[0][stat_i] = stat_reg;
-        const h16* const rs[4] = {qbh + (size_t)q_begin * TX_HD, qbl + (size_t)q_begin * TX_HD, dbh + (size_t)q_begin * TX_HD, dbl + (size_t)q_begin * TX_HD};
-        const h16* const ts[4] = {qtbh + q_begin, qtbl + q_begin, dtbh + q_begin, dtbl + q_begin};
+        const half_t* const rs[4] = {qbh + (size_t)q_begin * TX_HD, qbl + (size_t)q_begin * TX_HD, dbh + (size_t)q_begin * TX_HD, dbl + (size_t)q_begin * TX_HD};
+        const half_t* const ts[4] = {qtbh + q_begin, qtbl + q_begin, dtbh + q_begin, dtbl + q_begin};
         TX_STAGE_LOAD(st_regs, 4, 4, rs, ts, a.Lqp);
         TX_STAGE_STORE(st_regs, 4, 4, lds);
     }
@@ -725,21 +688,21 @@ __global__ __launch_bounds__(256, 2) void tx_attn_bwd_kv_kernel(const tx_attn_bw
         const bool more = q0 + 32 < q_end;
         if (more) {
             const size_t ro = (size_t)(q0 + 32) * TX_HD;
-            const h16* const rs[4] = {qbh + ro, qbl + ro, dbh + ro, dbl + ro};
-            const h16* const ts[4] = {qtbh + q0 + 32, qtbl + q0 + 32, dtbh + q0 + 32, dtbl + q0 + 32};
+            const half_t* const rs[4] = {qbh + ro, qbl + ro, dbh + ro, dbl + ro};
+            const half_t* const ts[4] = {qtbh + q0 + 32, qtbl + q0 + 32, dtbh + q0 + 32, dtbl + q0 + 32};
             TX_STAGE_LOAD(st_regs, 4, 4, rs, ts, a.Lqp);
             stat_load(q0 + 32);
         }
-        const h16* tile = lds + buf * STAGE;
-        f32x16 s, dp;
+        const half_t* tile = lds + buf * STAGE;
+        floatx16 s, dp;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
-            s = tx_mfma3(tx_lds_row(tile, j, t, half), tx_lds_row(tile + TX_RT, j, t, half), bkh[t], bkl[t], s);
-            dp = tx_mfma3(tx_lds_row(tile + 2 * TX_RT, j, t, half), tx_lds_row(tile + 3 * TX_RT, j, t, half), bvh[t], bvl[t], dp);
+            s = asd_mma3(tx_lds_row(tile, j, t, half), tx_lds_row(tile + TX_RT, j, t, half), bkh[t], bkl[t], s);
+            dp = asd_mma3(tx_lds_row(tile + 2 * TX_RT, j, t, half), tx_lds_row(tile + 3 * TX_RT, j, t, half), bvh[t], bvl[t], dp);
         }
-        h16x8 ph[2], pl[2], gh[2], gl[2];
+        half8 ph[2], pl[2], gh[2], gl[2];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int ql = tx_row_of(r, half), qi = q0 + ql;
@@ -748,28 +711,28 @@ __global__ __launch_bounds__(256, 2) void tx_attn_bwd_kv_kernel(const tx_attn_bw
                 p = tx_exp2(s[r] * c1 - row_stats[buf][ql]);
                 g = p * (dp[r] * cdp - row_stats[buf][32 + ql]);
             }
-            h16 x, y;
-            tx_split(p * TX_PSCALE, x, y);
+            half_t x, y;
+            asd_split(p * TX_PSCALE, x, y);
             ph[r >> 3][r & 7] = x; pl[r >> 3][r & 7] = y;
-            tx_split(g * sds, x, y);
+            asd_split(g * sds, x, y);
             gh[r >> 3][r & 7] = x; gl[r >> 3][r & 7] = y;
         }
-        const h16* tt = tile + 4 * TX_RT;        // Q^T hi, lo, dO^T hi, lo
+        const half_t* tt = tile + 4 * TX_RT;        // Q^T hi, lo, dO^T hi, lo
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
             const int d = 32 * mt + j;
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                h16x8 ah, al, ch, cl;
+                half8 ah, al, ch, cl;
                 if (d < TX_HD) {
                     ch = tx_lds_perm(tt, d, u, half); cl = tx_lds_perm(tt + TX_TT, d, u, half);
                     ah = tx_lds_perm(tt + 2 * TX_TT, d, u, half); al = tx_lds_perm(tt + 3 * TX_TT, d, u, half);
                 } else {
-                    ah = h16x8{0, 0, 0, 0, 0, 0, 0, 0};
+                    ah = half8{0, 0, 0, 0, 0, 0, 0, 0};
                     al = ah; ch = ah; cl = ah;
                 }
-                dvt[mt] = tx_mfma3(ah, al, ph[u], pl[u], dvt[mt]);
-                dkt[mt] = tx_mfma3(ch, cl, gh[u], gl[u], dkt[mt]);
+                dvt[mt] = asd_mma3(ah, al, ph[u], pl[u], dvt[mt]);
+                dkt[mt] = asd_mma3(ch, cl, gh[u], gl[u], dkt[mt]);
             }
         }
         if (more) {
@@ -800,37 +763,37 @@ __global__ __launch_bounds__(256, 2) void tx_attn_bwd_q_kernel(const tx_attn_bwd
     const int h = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int q0 = blockIdx.x * 128 + wave * 32;        // (waves past Lq: zero rows, nothing stored)
     const int j = lane & 31, half = lane >> 5, H = a.H;
-    const float sq = tx_scale_for(__uint_as_float(a.amax[h])), sk = tx_scale_for(__uint_as_float(a.amax[H + h]));
-    const float sv = tx_scale_for(__uint_as_float(a.amax[2 * H + h])), sdo = tx_scale_for(__uint_as_float(a.amax[3 * H + h]));
+    const float sq = asd_split_scale_bits<14, 126>(a.amax[h]), sk = asd_split_scale_bits<14, 126>(a.amax[H + h]);
+    const float sv = asd_split_scale_bits<14, 126>(a.amax[2 * H + h]), sdo = asd_split_scale_bits<14, 126>(a.amax[3 * H + h]);
     const float sds = tx_ds_scale(a.amax, H, h);
     const float c1 = 1.4426950408889634f * 0.14433756729740643f / (sq * sk), cdp = 1.f / (sdo * sv);
-    h16x8 bqh[3], bql[3], bdh[3], bdl[3];
+    half8 bqh[3], bql[3], bdh[3], bdl[3];
     {
         const size_t qrow = ((size_t)h * a.Lqp + q0 + j) * TX_HD + 8 * half;
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
-            bqh[t] = *reinterpret_cast<const h16x8*>(a.qh + qrow + 16 * t); bql[t] = *reinterpret_cast<const h16x8*>(a.ql + qrow + 16 * t);
-            bdh[t] = *reinterpret_cast<const h16x8*>(a.doh + qrow + 16 * t); bdl[t] = *reinterpret_cast<const h16x8*>(a.dol + qrow + 16 * t);
+            bqh[t] = *reinterpret_cast<const half8*>(a.qh + qrow + 16 * t); bql[t] = *reinterpret_cast<const half8*>(a.ql + qrow + 16 * t);
+            bdh[t] = *reinterpret_cast<const half8*>(a.doh + qrow + 16 * t); bdl[t] = *reinterpret_cast<const half8*>(a.dol + qrow + 16 * t);
         }
     }
     const bool q_ok = q0 + j < a.Lq;
     const float lse = q_ok ? a.lse2[(size_t)h * a.Lq + q0 + j] : 0.f, dsm = q_ok ? a.dsum[(size_t)h * a.Lq + q0 + j] : 0.f;
-    f32x16 dqt[2];
+    floatx16 dqt[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { dqt[0][r] = dqt[1][r] = 0.f; }
-    const h16 *kbh = a.kh + (size_t)h * a.Lkp * TX_HD, *kbl = a.kl + (size_t)h * a.Lkp * TX_HD;
-    const h16 *vbh = a.vh + (size_t)h * a.Lkp * TX_HD, *vbl = a.vl + (size_t)h * a.Lkp * TX_HD;
-    const h16 *ktbh = a.kth + (size_t)h * TX_HD * a.Lkp, *ktbl = a.ktl + (size_t)h * TX_HD * a.Lkp;
+    const half_t *kbh = a.kh + (size_t)h * a.Lkp * TX_HD, *kbl = a.kl + (size_t)h * a.Lkp * TX_HD;
+    const half_t *vbh = a.vh + (size_t)h * a.Lkp * TX_HD, *vbl = a.vl + (size_t)h * a.Lkp * TX_HD;
+    const half_t *ktbh = a.kth + (size_t)h * TX_HD * a.Lkp, *ktbl = a.ktl + (size_t)h * TX_HD * a.Lkp;
     // streamed per key block: K and V rows (row-major) and K^T (transposed), hi / lo each
     constexpr int STAGE = 4 * TX_RT + 2 * TX_TT;
-    __shared__ __attribute__((aligned(16))) h16 lds[2 * STAGE];
+    __shared__ __attribute__((aligned(16))) half_t lds[2 * STAGE];
     TxStage<4, 2> st_regs;
     const int k_per = ((a.Lk + (int)gridDim.z - 1) / (int)gridDim.z + 31) & ~31;
     const int k_begin = (int)blockIdx.z * k_per, k_end = min(a.Lk, k_begin + k_per);
     if (k_begin < k_end) {
         const size_t ro = (size_t)k_begin * TX_HD;
-        const h16* const rs[4] = {kbh + ro, kbl + ro, vbh + ro, vbl + ro};
-        const h16* const ts[2] = {ktbh + k_begin, ktbl + k_begin};
+        const half_t* const rs[4] = {kbh + ro, kbl + ro, vbh + ro, vbl + ro};
+        const half_t* const ts[2] = {ktbh + k_begin, ktbl + k_begin};
         TX_STAGE_LOAD(st_regs, 4, 2, rs, ts, a.Lkp);
         TX_STAGE_STORE(st_regs, 4, 2, lds);
     }
@@ -840,20 +803,20 @@ __global__ __launch_bounds__(256, 2) void tx_attn_bwd_q_kernel(const tx_attn_bwd
         const bool more = k0 + 32 < k_end;
         if (more) {
             const size_t ro = (size_t)(k0 + 32) * TX_HD;
-            const h16* const rs[4] = {kbh + ro, kbl + ro, vbh + ro, vbl + ro};
-            const h16* const ts[2] = {ktbh + k0 + 32, ktbl + k0 + 32};
+            const half_t* const rs[4] = {kbh + ro, kbl + ro, vbh + ro, vbl + ro};
+            const half_t* const ts[2] = {ktbh + k0 + 32, ktbl + k0 + 32};
             TX_STAGE_LOAD(st_regs, 4, 2, rs, ts, a.Lkp);
         }
-        const h16* tile = lds + buf * STAGE;
-        f32x16 st, dpt;
+        const half_t* tile = lds + buf * STAGE;
+        floatx16 st, dpt;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { st[r] = 0.f; dpt[r] = 0.f; }
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
-            st = tx_mfma3(tx_lds_row(tile, j, t, half), tx_lds_row(tile + TX_RT, j, t, half), bqh[t], bql[t], st);
-            dpt = tx_mfma3(tx_lds_row(tile + 2 * TX_RT, j, t, half), tx_lds_row(tile + 3 * TX_RT, j, t, half), bdh[t], bdl[t], dpt);
+            st = asd_mma3(tx_lds_row(tile, j, t, half), tx_lds_row(tile + TX_RT, j, t, half), bqh[t], bql[t], st);
+            dpt = asd_mma3(tx_lds_row(tile + 2 * TX_RT, j, t, half), tx_lds_row(tile + 3 * TX_RT, j, t, half), bdh[t], bdl[t], dpt);
         }
-        h16x8 gh[2], gl[2];
+        half8 gh[2], gl[2];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             float g = 0.f;
@@ -861,24 +824,24 @@ __global__ __launch_bounds__(256, 2) void tx_attn_bwd_q_kernel(const tx_attn_bwd
                 const float p = tx_exp2(st[r] * c1 - lse);
                 g = p * (dpt[r] * cdp - dsm);
             }
-            h16 x, y;
-            tx_split(g * sds, x, y);
+            half_t x, y;
+            asd_split(g * sds, x, y);
             gh[r >> 3][r & 7] = x; gl[r >> 3][r & 7] = y;
         }
-        const h16* tt = tile + 4 * TX_RT;
+        const half_t* tt = tile + 4 * TX_RT;
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
             const int d = 32 * mt + j;
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                h16x8 ah, al;
+                half8 ah, al;
                 if (d < TX_HD) {
                     ah = tx_lds_perm(tt, d, u, half); al = tx_lds_perm(tt + TX_TT, d, u, half);
                 } else {
-                    ah = h16x8{0, 0, 0, 0, 0, 0, 0, 0};
+                    ah = half8{0, 0, 0, 0, 0, 0, 0, 0};
                     al = ah;
                 }
-                dqt[mt] = tx_mfma3(ah, al, gh[u], gl[u], dqt[mt]);
+                dqt[mt] = asd_mma3(ah, al, gh[u], gl[u], dqt[mt]);
             }
         }
         if (more) { TX_STAGE_STORE(st_regs, 4, 2, lds + (buf ^ 1) * STAGE); }
@@ -1014,7 +977,7 @@ TxWgradWs tx_wgrad_ws(int M, int N, int K) {
 
 // planeA [M, 3K] . planeW [N, 3K]^T (fp32 result of the three fp16 products): *res / *nslab tell the epilogue where the result is — c32
 // [M, N] (nslab 1) or the unreduced split-K slabs [nslab][M][N] in `slabs` (the layouts above reserve them where the plan splits)
-int tx_gemm(const h16* pa, const h16* pw, int M, int N, int K3, float* c32, float* slabs, const float** res, int* nslab, hipStream_t s) {
+int tx_gemm(const half_t* pa, const half_t* pw, int M, int N, int K3, float* c32, float* slabs, const float** res, int* nslab, hipStream_t s) {
     asd_gemm_args a;
     memset(&a, 0, sizeof(a));
     a.A = pa; a.W = pw; a.C = c32;
@@ -1041,13 +1004,13 @@ int asd_tx_pack_weight(const float* w, int32_t N, int32_t K, void* plane_w, floa
     hipStream_t s = (hipStream_t)stream;
     if (plane_w) {
         ASD_CHECK_ARG(inv_w, "inv_w missing");
-        hipLaunchKernelGGL((tx_split_rows_kernel<1>), dim3(asd_div_up(N, 4)), dim3(256), 0, s, w, N, K, K, (h16*)plane_w, inv_w);
+        hipLaunchKernelGGL((tx_split_rows_kernel<1>), dim3(asd_div_up(N, 4)), dim3(256), 0, s, w, N, K, K, (half_t*)plane_w, inv_w);
     }
     if (plane_wt) {      // rows of W^T = columns of W [N, K]: K rows of 3 * Np halfs
         ASD_CHECK_ARG(inv_wt && ws, "inv_wt / ws missing");
         unsigned* colmax = tx_zeroed(reinterpret_cast<unsigned*>(ws), (size_t)K, s);
         hipLaunchKernelGGL(tx_colstat_kernel, dim3(asd_div_up(K, 64), asd_div_up(N, 256)), dim3(256), 0, s, w, N, K, K, 256, colmax, (float*)nullptr);
-        hipLaunchKernelGGL((tx_split_cols_kernel<1>), dim3(asd_div_up(K, 64), tx_rp(N) / 64), dim3(256), 0, s, w, N, K, K, tx_rp(N), colmax, (h16*)plane_wt, inv_wt);
+        hipLaunchKernelGGL((tx_split_cols_kernel<1>), dim3(asd_div_up(K, 64), tx_rp(N) / 64), dim3(256), 0, s, w, N, K, K, tx_rp(N), colmax, (half_t*)plane_wt, inv_wt);
     }
     ASD_LAUNCH_CHECK();
     return ASD_OK;
@@ -1065,12 +1028,12 @@ static int tx_linear_core(const float* x, int32_t M, int32_t K, int32_t ldx, con
     ASD_CHECK_ARG(K % 64 == 0 && N % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && (mode == 0 || aux), "K % 64, N % 4, leading dimensions % 4; aux for GELU modes");
     hipStream_t s = (hipStream_t)stream;
     const TxLinearWs L = tx_linear_ws(M, N, K);
-    h16* pa = reinterpret_cast<h16*>(ws + L.planes);
+    half_t* pa = reinterpret_cast<half_t*>(ws + L.planes);
     float *ia = ws + L.inv, *c32 = ws + L.c32;
     if (!planes_ready) hipLaunchKernelGGL((tx_split_rows_kernel<0>), dim3(asd_div_up(M, 4)), dim3(256), 0, s, x, M, K, ldx, pa, ia);
     const float* res;
     int nslab;
-    const int rc = tx_gemm(pa, (const h16*)plane_w, M, N, 3 * K, c32, ws + L.slabs, &res, &nslab, s);
+    const int rc = tx_gemm(pa, (const half_t*)plane_w, M, N, 3 * K, c32, ws + L.slabs, &res, &nslab, s);
     if (rc != ASD_OK) return rc;
     hipLaunchKernelGGL(tx_epilogue_kernel, dim3(asd_grid_for((int64_t)M * N / 4, 256)), dim3(256), 0, s, res, nslab, M, N, ia, inv_w, bias, mode, aux, N, residual, ldr, y, ldy);
     ASD_LAUNCH_CHECK();
@@ -1088,12 +1051,12 @@ int64_t asd_tx_wgrad_workspace(int32_t M, int32_t N, int32_t K) { return tx_wgra
 // known without looking at x (LayerNorm outputs: sqrt(D - 1) |gamma_c| + |beta_c|; ...) — either spares the statistics pass over x
 // accumulate: dw += the product (the epilogue reads the old value as its residual: no staging buffer, no add launch), db += its column sums
 static int tx_wgrad_core(const float* dy, int32_t ldy, const float* x, int32_t ldx, int32_t M, int32_t N, int32_t K, float* dw, float* db, float* ws,
-                         const h16* x_planes, const float* x_inv, const unsigned* x_bound, void* stream, bool accumulate = false) {
+                         const half_t* x_planes, const float* x_inv, const unsigned* x_bound, void* stream, bool accumulate = false) {
     ASD_CHECK_ARG(dy && (x || x_planes) && dw && ws && M > 0 && N > 0 && K > 0 && N % 4 == 0 && K % 4 == 0, "bad argument");
     hipStream_t s = (hipStream_t)stream;
     const int Mp = tx_rp(M);
     const TxWgradWs L = tx_wgrad_ws(M, N, K);
-    h16 *pa = reinterpret_cast<h16*>(ws + L.dyt), *pw = reinterpret_cast<h16*>(ws + L.xt);
+    half_t *pa = reinterpret_cast<half_t*>(ws + L.dyt), *pw = reinterpret_cast<half_t*>(ws + L.xt);
     float *ia = ws + L.inv_dy, *iw = ws + L.inv_x, *c32 = ws + L.c32;
     unsigned* cmax_a = tx_zeroed(reinterpret_cast<unsigned*>(ws + L.cmax), (size_t)L.cmax_words, s);
     unsigned* cmax_w = cmax_a + L.cmax_x;
@@ -1117,7 +1080,7 @@ int asd_tx_linear_wgrad(const float* dy, int32_t ldy, const float* x, int32_t ld
     return tx_wgrad_core(dy, ldy, x, ldx, M, N, K, dw, db, ws, nullptr, nullptr, nullptr, stream);
 }
 
-static int tx_layernorm_fwd_core(const float* x, int32_t M, int32_t D, const float* gamma, const float* beta, float eps, float* y, float* stats, h16* plane, float* inv,
+static int tx_layernorm_fwd_core(const float* x, int32_t M, int32_t D, const float* gamma, const float* beta, float eps, float* y, float* stats, half_t* plane, float* inv,
                                  void* stream) {
     ASD_CHECK_ARG(x && gamma && beta && y && stats && M > 0 && D > 0 && D % 4 == 0 && D <= 1024, "LayerNorm: D % 4 == 0, D <= 1024");
     hipLaunchKernelGGL(tx_layernorm_fwd_kernel, dim3(asd_div_up(M, 4)), dim3(256), 0, (hipStream_t)stream, x, M, D, gamma, beta, eps, y, stats, plane, inv);
@@ -1130,7 +1093,7 @@ int asd_tx_layernorm_fwd(const float* x, int32_t M, int32_t D, const float* gamm
 
 // dx = LayerNorm input gradient (+ dres); dgamma / dbeta are ACCUMULATED (+=: the caller zeroes them once per backward pass)
 static int tx_layernorm_bwd_core(const float* dy, const float* x, const float* stats, const float* gamma, int32_t M, int32_t D, const float* dres, float* dx,
-                                 float* dgamma, float* dbeta, h16* plane, float* inv, void* stream) {
+                                 float* dgamma, float* dbeta, half_t* plane, float* inv, void* stream) {
     ASD_CHECK_ARG(dy && x && stats && gamma && dx && dgamma && dbeta && M > 0 && D > 0 && D % 4 == 0 && D <= 1024, "LayerNorm: D % 4 == 0, D <= 1024");
     constexpr int rows_per_wave = 8;      // tools/tritx_time.py: 81 / 44 / 29 / 28 / 40 us at 1 / 2 / 4 / 8 / 16 rows per wave (the per-block atomics of dgamma / dbeta dominate)
     int grid = asd_div_up(M, 4 * rows_per_wave);
@@ -1183,7 +1146,7 @@ int asd_tx_attention_fwd(const float* q, int32_t ldq, const float* k, int32_t ld
     const TxAttnWs L = tx_attn_ws(Lq, Lk, H);
     const int Lqp = L.Lqp, Lkp = L.Lkp, zk = L.ksplit;
     const size_t nq = (size_t)H * Lqp * TX_HD, nk = (size_t)H * Lkp * TX_HD;
-    h16 *qh = reinterpret_cast<h16*>(ws + L.planes), *ql = qh + nq, *kh = qh + 2 * nq, *kl = kh + nk, *vth = kh + 2 * nk, *vtl = kh + 3 * nk;
+    half_t *qh = reinterpret_cast<half_t*>(ws + L.planes), *ql = qh + nq, *kh = qh + 2 * nq, *kl = kh + nk, *vth = kh + 2 * nk, *vtl = kh + 3 * nk;
     unsigned* amax = tx_zeroed(reinterpret_cast<unsigned*>(ws + L.amax), (size_t)8 * H, s);
     {
         tx_absmax_args m;
@@ -1212,8 +1175,8 @@ int asd_tx_attention_bwd(const float* q, int32_t ldq, const float* k, int32_t ld
     const int Lqp = L.Lqp, Lkp = L.Lkp, qsplit = L.qsplit, ksplit = L.ksplit;
     const size_t nq = (size_t)H * Lqp * TX_HD, nk = (size_t)H * Lkp * TX_HD;
     tx_attn_bwd_args a;
-    h16 *qh = reinterpret_cast<h16*>(ws + L.planes), *ql = qh + nq, *doh = qh + 2 * nq, *dol = qh + 3 * nq, *qth = qh + 4 * nq, *qtl = qh + 5 * nq, *doth = qh + 6 * nq, *dotl = qh + 7 * nq;
-    h16 *kh = qh + 8 * nq, *kl = kh + nk, *vh = kh + 2 * nk, *vl = kh + 3 * nk, *kth = kh + 4 * nk, *ktl = kh + 5 * nk;
+    half_t *qh = reinterpret_cast<half_t*>(ws + L.planes), *ql = qh + nq, *doh = qh + 2 * nq, *dol = qh + 3 * nq, *qth = qh + 4 * nq, *qtl = qh + 5 * nq, *doth = qh + 6 * nq, *dotl = qh + 7 * nq;
+    half_t *kh = qh + 8 * nq, *kl = kh + nk, *vh = kh + 2 * nk, *vl = kh + 3 * nk, *kth = kh + 4 * nk, *ktl = kh + 5 * nk;
     unsigned* amax = tx_zeroed(reinterpret_cast<unsigned*>(ws + L.amax), (size_t)8 * H, s);
     float* dsum = ws + L.dsum;
     {
@@ -1419,8 +1382,8 @@ int asd_tritx_pack(const asd_tritx_desc* desc, const float* const* params, float
     tx_memset0(colmax, (size_t)d.O * 4, s);
     hipLaunchKernelGGL(tx_colstat_kernel, dim3(asd_div_up(d.O, 64), asd_div_up(d.D, 256)), dim3(256), 0, s, V, d.D, d.O, d.O, 256, colmax, (float*)nullptr);
     hipLaunchKernelGGL((tx_split_cols_kernel<1>), dim3(asd_div_up(d.O, 64), tx_rp(d.D) / 64), dim3(256), 0, s, V, d.D, d.O, d.O, tx_rp(d.D), colmax,
-                       reinterpret_cast<h16*>(packed + hd.dc_w), packed + hd.dc_iw);
-    hipLaunchKernelGGL((tx_split_rows_kernel<1>), dim3(asd_div_up(d.D, 4)), dim3(256), 0, s, V, d.D, d.O, d.O, reinterpret_cast<h16*>(packed + hd.dc_t), packed + hd.dc_it);
+                       reinterpret_cast<half_t*>(packed + hd.dc_w), packed + hd.dc_iw);
+    hipLaunchKernelGGL((tx_split_rows_kernel<1>), dim3(asd_div_up(d.D, 4)), dim3(256), 0, s, V, d.D, d.O, d.O, reinterpret_cast<half_t*>(packed + hd.dc_t), packed + hd.dc_it);
     ASD_LAUNCH_CHECK();
     return ASD_OK;
 }
@@ -1441,7 +1404,7 @@ int asd_tritx_fwd(const asd_tritx_desc* desc, const float* const* params, const 
     struct PoolGuard { ~PoolGuard() { tx_pool = {nullptr, 0, false}; } } pool_guard;
     unsigned* pool = reinterpret_cast<unsigned*>(workspace + W.pool);
     const TxLinearWs LN = tx_linear_ws(d.T, d.D, d.D);      // where a Linear over [T, D] rows looks for its operand planes and row scales
-    h16* const lp = reinterpret_cast<h16*>(ws + LN.planes);
+    half_t* const lp = reinterpret_cast<half_t*>(ws + LN.planes);
     float* const li = ws + LN.inv;
     for (int n = 0; n < batch; ++n) {
         tx_memset0(pool, (size_t)tx_pool_words(d) * 4, s);
@@ -1498,7 +1461,7 @@ int asd_tritx_bwd(const asd_tritx_desc* desc, const float* const* params, const 
     const int64_t TD = (int64_t)d.T * d.D;
     float *dxa = workspace + W.dxa, *dxb = workspace + W.dxb, *dn = workspace + W.dn, *dob = workspace + W.dob;
     float *dqkv = workspace + W.dqkv, *dkv = workspace + W.dkv, *du = workspace + W.du, *dy = workspace + W.dy;
-    h16* cond_planes = reinterpret_cast<h16*>(workspace + W.cond_planes);
+    half_t* cond_planes = reinterpret_cast<half_t*>(workspace + W.cond_planes);
     float* cond_inv = workspace + W.cond_inv;
     unsigned* cond_max = reinterpret_cast<unsigned*>(workspace + W.cond_max);
     // LayerNorm gradients accumulate over layers' rows and the batch, bias gradients are atomic column sums: zero them once — or take the
@@ -1515,11 +1478,11 @@ int asd_tritx_bwd(const asd_tritx_desc* desc, const float* const* params, const 
     struct PoolGuard { ~PoolGuard() { tx_pool = {nullptr, 0, false}; } } pool_guard;
     unsigned* pool = reinterpret_cast<unsigned*>(workspace + W.pool);
     // weight gradients of batch element n > 0 are added to those of the elements before it — in the product's own epilogue (residual = dw)
-    const h16* xpl = nullptr;          // precomputed transposed planes of x (+ scales) / column bounds of x for the NEXT wgrad call
+    const half_t* xpl = nullptr;          // precomputed transposed planes of x (+ scales) / column bounds of x for the NEXT wgrad call
     const float* xinv = nullptr;
     const unsigned* xbound = nullptr;
     auto wgrad = [&](const float* dyp, int ldy, const float* xp, int ldx, int M, int N, int K, float* dw, float* db, bool acc) -> int {
-        const h16* pl = xpl; const float* pi = xinv; const unsigned* pb = xbound;
+        const half_t* pl = xpl; const float* pi = xinv; const unsigned* pb = xbound;
         xpl = nullptr; xinv = nullptr; xbound = nullptr;
         return tx_wgrad_core(dyp, ldy, xp, ldx, M, N, K, dw, db, ws, pl, pi, pb, stream, acc);
     };
@@ -1548,7 +1511,7 @@ int asd_tritx_bwd(const asd_tritx_desc* desc, const float* const* params, const 
         // (every LayerNorm backward leaves the operand planes of its dx where the next input-gradient Linear looks for them: that Linear runs
         // BEFORE the weight gradient that shares dx with it, whose workspace would overwrite the planes)
         const TxLinearWs LN = tx_linear_ws(d.T, d.D, d.D);
-        h16* const lp = reinterpret_cast<h16*>(ws + LN.planes);
+        half_t* const lp = reinterpret_cast<half_t*>(ws + LN.planes);
         float* const li = ws + LN.inv;
         TXS(tx_layernorm_bwd_core(dn, xf, stF, params[20 * d.layers + 1], d.T, d.D, nullptr, dx, GH[1], GH[2], lp, li, stream));
         for (int l = d.layers - 1; l >= 0; --l) {

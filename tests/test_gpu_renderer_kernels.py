@@ -135,6 +135,51 @@ def test_field_backward(oracle, with_normal, n, geom):
             np.testing.assert_allclose(a.cpu().numpy() / scale, b / scale, rtol=1e-4, atol=1e-4)
 
 
+@pytest.mark.parametrize("case", ["zero_gradients", "zero_encoding_row"])
+def test_field_backward_zero_operands(oracle, case):
+    """The guard of the matrix-pipe MLP backward's power-of-two scales (csrc/field_mfma.hip, split_f16.h: max|.| == 0 gives scale 1) at
+    n = 257 (four whole tiles and a tile of one sample).  zero_gradients: d_sigma = d_features = 0 — every gradient is exactly zero.
+    zero_encoding_row: the grid is zero in every cell that one sample touches, so its encoding row is all zero — test_field_backward's
+    tolerances against the float64 oracle."""
+    from scaledreamer_amd import ops
+
+    n, j = 257, 100
+    om, hm = _metas(oracle, GEOM)
+    oc = oracle.field_cfg()
+    hc = _hip_cfg(oc)
+    rng = np.random.default_rng(13)
+    grid = rng.uniform(-0.1, 0.1, om.n_params).astype(np.float32)
+    w = _weights(rng)
+    pts = rng.uniform(-0.7, 0.7, (n, 3)).astype(np.float32)
+    ds = rng.normal(size=n).astype(np.float32)
+    df = rng.normal(size=(n, 3)).astype(np.float32)
+    if case == "zero_gradients":
+        ds[:] = 0
+        df[:] = 0
+    else:
+        # the table entries sample j reads: where the gradient of its encoding lands
+        unit = oracle.field_fwd(om, oc, grid, *w, pts[j:j + 1], want_normal=False)
+        touched = oracle.field_bwd(om, oc, grid, *w, pts[j:j + 1], np.ones(1, np.float32), np.ones((1, 3), np.float32), None)[0] != 0
+        assert touched.sum() >= 8 * om.n_levels and np.abs(unit[3]).max() > 0
+        grid[touched] = 0
+    dg, dw = _dev(grid), [_dev(a) for a in w]
+    sig, feat, nrm, enc = ops.field_fwd(hm, hc, dg, *dw, _dev(pts), want_normal=False)
+    if case == "zero_encoding_row":
+        assert (enc[j] == 0).all() and (enc != 0).any(1).sum() == n - 1
+    d_grid = torch.zeros(om.n_params, device="cuda")
+    got = ops.field_bwd(hm, hc, dg, *dw, _dev(pts), enc, sig, _dev(ds), _dev(df), None, d_grid)
+    if case == "zero_gradients":
+        assert (d_grid == 0).all()
+        for a in got:
+            assert (a == 0).all()
+        return
+    want = oracle.field_bwd(om, oc, grid, *w, pts, ds, df, None)
+    np.testing.assert_allclose(d_grid.cpu().numpy(), want[0], rtol=1e-4, atol=1e-4)
+    for a, b in zip(got, want[1:]):
+        scale = max(1.0, float(np.abs(b).max()))
+        np.testing.assert_allclose(a.cpu().numpy() / scale, b / scale, rtol=1e-4, atol=1e-4)
+
+
 @pytest.mark.parametrize("paged", ["1", "0"])
 def test_field_backward_crowded_points_and_both_scatter_forms(oracle, paged):
     """The fine levels of the hash-grid gradient go through the paged scatter (csrc/field_paged.hip: items binned by 64 KB table page,

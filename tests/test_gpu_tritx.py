@@ -95,6 +95,104 @@ def test_linear_weight_gradient(M, N, K):
     assert rel(db, dy.double().sum(0)) < 1e-5
 
 
+# ---- the power-of-two scale at its edges (csrc/split_f16.h: asd_split_scale) -------------------------------------------------------------
+# max|row| of individual operand rows: exactly 2^k and one ulp below it (the scale's exponent steps there), a denormal, zero
+EDGE_KINDS = {"2^-20": 2.0 ** -20, "2^-20-ulp": float(np.nextafter(np.float32(2.0 ** -20), np.float32(0))),
+              "2^0": 1.0, "2^0-ulp": float(np.nextafter(np.float32(1), np.float32(0))),
+              "2^15": 2.0 ** 15, "2^15-ulp": float(np.nextafter(np.float32(2.0 ** 15), np.float32(0))),
+              "denormal": 2.0 ** -130, "zero": 0.0}
+
+
+def _edge_rows(rng, rows, cols):
+    """fp32 [rows, cols] whose row r has max|.| == the (r mod 8)-th value of EDGE_KINDS exactly, and that index per row"""
+    a = rng.standard_normal((rows, cols)).astype(np.float32)
+    a /= np.abs(a).max(1, keepdims=True)                  # the largest element of a row is +-1 exactly
+    kind = np.arange(rows) % len(EDGE_KINDS)
+    a *= np.array(list(EDGE_KINDS.values()), dtype=np.float32)[kind][:, None]      # one rounding per element; +-1 takes the value exactly
+    assert (np.abs(a).max(1) == np.array(list(EDGE_KINDS.values()), dtype=np.float32)[kind]).all()
+    return a, kind
+
+
+def _edge_errors(out, ref, kind_rows, kind_cols):
+    """{kind: worst error of the output rows (columns) that came from an operand row of that kind, relative to that row's (column's) own
+    largest reference value}; out rows of a zero operand row must be exactly zero (their entry is 0.0 then, inf otherwise)"""
+    out = out.double().cpu().numpy()                      # ref: float64 numpy, formed on the host (no flush of the denormal inputs)
+    assert np.isfinite(out).all()
+    res = {}
+    for name, k in zip(EDGE_KINDS, range(len(EDGE_KINDS))):
+        worst = 0.0
+        for axis, kinds in ((1, kind_rows), (0, kind_cols)):
+            sel = np.nonzero(kinds == k)[0]
+            o, r = (out[sel], ref[sel]) if axis == 1 else (out[:, sel], ref[:, sel])
+            if name == "zero":
+                worst = max(worst, 0.0 if (o == 0).all() else np.inf)
+            else:
+                worst = max(worst, float((np.abs(o - r).max(axis) / np.abs(r).max(axis)).max()))
+        res[name] = worst
+    return res
+
+
+_edge_cache = {}
+
+
+def _edge_linear(which):
+    """the two products once per session: (errors by kind, tolerance of the neighbouring test)"""
+    if which in _edge_cache:
+        return _edge_cache[which]
+    L = _lib()
+    rng = np.random.default_rng(7)
+    if which == "forward":
+        M, K, N = 200, 64, 128
+        x, kx = _edge_rows(rng, M, K)
+        w, kw = _edge_rows(rng, N, K)
+        pw, iw, _, _ = pack_weight(torch.from_numpy(w).cuda(), True, False)
+        res = _edge_errors(linear(torch.from_numpy(x).cuda(), pw, iw, N), x.astype(np.float64) @ w.astype(np.float64).T, kx, kw), 4e-6
+    else:
+        M, K, N = 130, 64, 128
+        dyt, kd = _edge_rows(rng, N, M)                   # rows of the operands as the contraction over M sees them: columns of dy and of x
+        xt, kx = _edge_rows(rng, K, M)
+        dy, x = torch.from_numpy(dyt.T.copy()).cuda(), torch.from_numpy(xt.T.copy()).cuda()
+        dw, db = torch.empty(N, K, device="cuda"), torch.empty(N, device="cuda")
+        ws = _ws(L.lib().asd_tx_wgrad_workspace(L.i32(M), L.i32(N), L.i32(K)))
+        L.check(L.lib().asd_tx_linear_wgrad(L.ptr(dy), L.i32(N), L.ptr(x), L.i32(K), L.i32(M), L.i32(N), L.i32(K), L.ptr(dw), L.ptr(db), L.ptr(ws), L.stream()))
+        assert torch.isfinite(db).all() and (db[torch.from_numpy(kd == list(EDGE_KINDS).index("zero")).cuda()] == 0).all()
+        res = _edge_errors(dw, dyt.astype(np.float64) @ xt.astype(np.float64).T, kd, kx), 5e-6
+    _edge_cache[which] = res
+    return res
+
+
+@pytest.mark.parametrize("kind", list(EDGE_KINDS))
+@pytest.mark.parametrize("which", ["forward", "weight_gradient"])
+def test_linear_rows_at_the_edges_of_the_scale(which, kind):
+    """(M, K, N) = (200, 64, 128) forward, (130, 64, 128) weight gradient; operand rows with max|.| at EDGE_KINDS, float64 reference, the
+    neighbouring tests' tolerance relative to each row's own range (the float64 reference rounded to fp32 passes every case on the CPU).
+
+    `denormal`: tritx.hip's per-row scales may reach 2^126 (asd_split_scale<14, 126>), which puts a row with maximum 2^-130 at 2^-4, inside
+    fp16; clamped at 2^100 such a row was split at 2^-30, both planes were zero and the error was 1.0 of the row's own range.
+    Measured on an MI355X (worst error by kind, tolerance 4e-6 / 5e-6):
+        forward          2^-20 2.1e-7, -ulp 2.7e-7, 2^0 2.5e-7, -ulp 3.0e-7, 2^15 3.1e-7, -ulp 2.7e-7, denormal 3.2e-7, zero exact
+        weight gradient  2^-20 4.6e-7, -ulp 4.4e-7, 2^0 4.3e-7, -ulp 4.6e-7, 2^15 3.4e-7, -ulp 6.5e-7, denormal 6.0e-7, zero exact"""
+    errs, tol = _edge_linear(which)
+    print(which, errs)
+    assert errs[kind] < tol, errs
+
+
+def test_attention_forward_with_an_all_zero_key_head():
+    """max|K| of a head is zero: its scale is 1, every score is 0 and the output is the mean of V over the keys"""
+    Lq, Lk, H = 100, 50, 2
+    g = torch.Generator(device="cuda").manual_seed(Lq + Lk + 1)
+    q = torch.randn(Lq, H * 48, device="cuda", generator=g) * 2.0
+    k = torch.randn(Lk, H * 48, device="cuda", generator=g) * 1.7
+    v = torch.randn(Lk, H * 48, device="cuda", generator=g) * 1.7
+    k[:, 48:] = 0
+    o, lse, _ = attention_fwd(q, k, v, H)
+    assert torch.isfinite(o).all() and torch.isfinite(lse).all()
+    assert rel(o[:, 48:], v[:, 48:].double().mean(0, keepdim=True).expand(Lq, 48)) < 3e-6
+    ref_o, ref_lse = _attn_ref(q, k, v, H)
+    assert rel(o, ref_o) < 3e-6
+    assert float((lse.double() - ref_lse).abs().max()) < 1e-5
+
+
 def test_layernorm_forward_backward():
     L = _lib()
     M, D = 3072, 768
