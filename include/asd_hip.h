@@ -668,7 +668,9 @@ int64_t asd_vae_enc_workspace_bytes(asd_vae_enc* h, int32_t batch, int32_t H, in
 /* x_nhwc32: fp16 [batch,H,W,32] image in [-1,1], channels >= in_channels zero; moments_nhwc: fp32 [batch,H/8,W/8,2*embed_dim] */
 int asd_vae_enc_fwd(asd_vae_enc* h, const void* x_nhwc32, int32_t batch, int32_t H, int32_t W, void* workspace, int64_t workspace_bytes,
                     float* moments_nhwc, int32_t tune, void* stream);
-/* d_moments_nhwc: fp32 like moments; dx_nhwc32: fp16 [batch,H,W,32], channels < in_channels hold the image gradient */
+/* d_moments_nhwc: fp32 like moments; dx_nhwc32: fp16 [batch,H,W,32], channels < in_channels hold the image gradient.
+ * batch, H, W, tune: shape must be the forward's; the forward's layout is recorded per workspace (another shape, or fewer
+ * workspace_bytes than the forward was given, is ASD_ERR_ARG before anything is launched).  May be called again on the same workspace. */
 int asd_vae_enc_bwd(asd_vae_enc* h, const float* d_moments_nhwc, int32_t batch, int32_t H, int32_t W, void* workspace,
                     int64_t workspace_bytes, void* dx_nhwc32, int32_t tune, void* stream);
 

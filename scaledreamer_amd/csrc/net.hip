@@ -49,12 +49,6 @@ struct Run {                // state of one pass over a schedule
     size_t scratch_bytes = 0, scratch_need = 0;
     const void* zero_page = nullptr;
     int status = ASD_OK;
-    // GroupNorm-statistics records written by producers' epilogues (asd_gemm_args.gn_partials): their count depends on the GEMM
-    // plan, so a pass that must reproduce another pass's allocation sequence (the VAE backward replaying its forward) replays the
-    // logged counts instead of asking the plan table again
-    std::vector<int>* rec_log = nullptr;
-    const std::vector<int>* rec_replay = nullptr;
-    size_t rec_pos = 0;
 };
 
 struct Act {                // an activation and, when its producer left them, its GroupNorm statistics records
@@ -71,6 +65,7 @@ struct GnNext {             // the GroupNorm that consumes a layer's output, whe
 };
 
 struct Net {
+    virtual ~Net() = default;       // handles are destroyed through this base (net_destroy)
     std::vector<WSpec> specs;
     std::map<std::string, int> index;
     std::vector<const void*> ptr;
@@ -97,10 +92,6 @@ struct GemmOpt {
     const void* residual = nullptr; int ldr = 0; int act = 0; int out_f32 = 0;
     int gn_rows = 0;        // > 0: the output feeds a GroupNorm over all N channels with this many rows per batch element
     Act* out = nullptr;     // receives the records' location when gn_rows > 0
-    // backward form (the output is the gradient dy reaching a GroupNorm with input gn_x): records of {sum g, sum g * xhat}
-    const half_t* gn_x = nullptr; const float* gn_fstats = nullptr; const half_t* gn_gamma = nullptr; const half_t* gn_beta = nullptr;
-    int gn_silu = 0;
-    bool gn_bwd_form = false;   // set with gn_x (dry passes carry null pointers: the record count must still be the backward form's)
     // LayerNorm folded into this GEMM (asd_gemm_args.ln_mode): 1 = the rows of A are normalised (statistics reduced in the main loop,
     // optionally exported to ln_stats), 2 = the rows of the W operand are (statistics read from ln_stats)
     int ln_mode = 0; const float* ln_sc = nullptr; float* ln_stats = nullptr;
@@ -109,12 +100,9 @@ struct GemmOpt {
     const GnNext* gn_next = nullptr;
 };
 
-void set_gn_bwd(asd_gemm_args& g, const GemmOpt& o) {
-    g.gn_bwd_x = o.gn_x; g.gn_bwd_fstats = o.gn_fstats; g.gn_bwd_gamma = o.gn_gamma; g.gn_bwd_beta = o.gn_beta;
-    g.gn_eps = 1e-6f; g.gn_silu = o.gn_silu;
-}
-
-void launch_gemm(Run& r, asd_gemm_args& g, Act* gn_out = nullptr, bool gn_bwd_form = false, const GnNext* gn_next = nullptr) {
+// Records are the forward form only: the schedules do not ask a dgrad launch for the two reductions of the GroupNorm input gradient
+// (asd_gemm_args.gn_bwd_*, still offered by the GEMM) — measured twice, the stand-alone statistics passes win: DESIGN.md 4.15.
+void launch_gemm(Run& r, asd_gemm_args& g, Act* gn_out = nullptr, const GnNext* gn_next = nullptr) {
     g.zero_page = r.zero_page;
     g.split_k = 0;          // auto: tuned plan of this shape (asd_gemm_plan_*), else cost model
     g.tile_cfg = 0;
@@ -127,17 +115,7 @@ void launch_gemm(Run& r, asd_gemm_args& g, Act* gn_out = nullptr, bool gn_bwd_fo
     }
     const size_t need = (size_t)asd_gemm_workspace_bytes(&g);
     if (need > r.scratch_need) r.scratch_need = need;
-    // The backward form of the records (the two reductions of the GroupNorm input gradient from the dgrad launch's epilogue) is NOT used by
-    // the schedules since round 3 (the GEMM still offers it: asd_gemm_args.gn_bwd_*): on the ping-pong kernel the epilogue's silu'(z) over
-    // the whole tile is not hidden behind another block's main loop — the VAE's eleven dgrad launches grew by 22-53 us each (0.39 ms per step) for 0.33 ms of statistics passes saved; same-box
-    // A/B 15.58 vs 15.64 ms per step.
-    // Re-decided when silu' lost its IEEE division (asd_silu_grad_fast: ~10 VALU instead of ~25 per element): still not used.
-    // Same box, four alternating runs of 300 steps: stand-alone statistics passes 13.748 / 13.700 / 13.698 / 13.690 ms per step, reductions in
-    // the dgrad epilogue 13.894 / 13.874 / 13.881 / 13.888 ms (+0.175 ms, every pair the same sign; the parent commit on that box 13.92 ms).
-    // The statistics passes got cheaper by the same change (statistics + apply at 512^2 x 128: 83 -> 70 us), the un-hidden epilogue
-    // arithmetic of the eleven ping-pong launches (x reload, two FMAs, v_exp, v_rcp per output and the tile reduction) did not become free.
-    if (gn_bwd_form) { gn_out = nullptr; g.gn_bwd_x = nullptr; g.gn_bwd_fstats = nullptr; g.gn_bwd_gamma = nullptr; g.gn_bwd_beta = nullptr; }
-    if (gn_next && gn_next->gamma && gn_out && g.gn_rows > 0 && g.N % 32 == 0 && !r.rec_replay && !r.rec_log) {
+    if (gn_next && gn_next->gamma && gn_out && g.gn_rows > 0 && g.N % 32 == 0) {
         // GroupNorm applied by the producer: decided by shape and plan only (dry passes carry null pointers)
         asd_gemm_args q = g;
         q.gn_cg = g.N / 32; q.gn_apply = 1;
@@ -155,17 +133,10 @@ void launch_gemm(Run& r, asd_gemm_args& g, Act* gn_out = nullptr, bool gn_bwd_fo
     if (gn_out && g.gn_rows > 0 && g.N % 32 == 0) {     // statistics records of the output, produced in the epilogue when the plan allows
         g.gn_cg = g.N / 32;
         const int batch = g.M / g.gn_rows;
-        int nrec;
-        if (r.rec_replay) nrec = r.rec_pos < r.rec_replay->size() ? (*r.rec_replay)[r.rec_pos++] : 0;
-        else {
-            asd_gemm_args q = g;             // the answer depends on shape, plan and form only (dry passes carry null pointers)
-            q.gn_bwd_x = nullptr;
-            nrec = asd_gemm_gn_records(&q);
-        }
+        const int nrec = asd_gemm_gn_records(&g);     // the answer depends on shape and plan only (dry passes carry null pointers)
         // while tuning, the plan (and with it the record count) of this shape may still change between the sizing pass and the
         // launch: reserve the upper bound (64 x 64 tiles)
         const int reserve = r.tune ? (g.gn_rows / 64 + 1) * (g.N / 64 + 1) : nrec;
-        if (r.rec_log) r.rec_log->push_back(nrec);
         float* buf = (nrec > 0 || r.tune) ? r.mem.floats((size_t)batch * (reserve > nrec ? reserve : nrec) * 64) : nullptr;
         if (nrec > 0) { g.gn_partials = buf; gn_out->rec = buf; gn_out->nrec = nrec; }
     }
@@ -184,9 +155,8 @@ void gemm(Run& r, const void* A, int M, int lda, const void* W, int N, int K, in
     g.residual = o.residual; g.ldr = o.ldr; g.act = o.act; g.out_f32 = o.out_f32;
     g.gn_rows = o.gn_rows;
     g.ln_mode = o.ln_mode; g.ln_sc = o.ln_sc; g.ln_stats = o.ln_stats; g.ln_eps = 1e-5f;
-    if (o.gn_x) set_gn_bwd(g, o);
     if (o.out) { *o.out = Act{}; o.out->p = (const half_t*)C; }
-    launch_gemm(r, g, o.out, o.gn_bwd_form, o.gn_next);
+    launch_gemm(r, g, o.out, o.gn_next);
 }
 
 // 3x3 convolution on NHWC [B,Hin,Win,Cin] with packed weights [Cout, 9*Cin]; upsample: 0 plain, 1 nearest-2x fused, 2 transposed stride-2,
@@ -200,9 +170,8 @@ void conv3x3(Run& r, const void* x, int B, int Hin, int Win, int Cin, const void
     g.residual = o.residual; g.ldr = o.ldr; g.act = o.act; g.out_f32 = o.out_f32;
     g.conv = 1; g.Hin = Hin; g.Win = Win; g.Cin = Cin; g.Hout = Hout; g.Wout = Wout; g.stride = stride; g.pad = pad; g.upsample = upsample;
     g.gn_rows = o.gn_rows;
-    if (o.gn_x) set_gn_bwd(g, o);
     if (o.out) { *o.out = Act{}; o.out->p = (const half_t*)y; }
-    launch_gemm(r, g, o.out, o.gn_bwd_form, o.gn_next);
+    launch_gemm(r, g, o.out, o.gn_next);
 }
 
 #define LEAF(call)                                              \
@@ -244,21 +213,21 @@ struct UNet : Net {
 };
 
 #define ASD_LN_FOLD_MIN_C 1024      // transformer blocks at least this wide fold their LayerNorms (weights.py: LN_FOLD_MIN_C)
-void u_norm(UNet& n, const std::string& p, int c) { n.add(p + ".weight", 1, c); n.add(p + ".bias", 1, c); }
+void w_norm(Net& n, const std::string& p, int c) { n.add(p + ".weight", 1, c); n.add(p + ".bias", 1, c); }
 void u_lin(UNet& n, const std::string& p, int cin, int cout, bool bias = true) { n.add(p + ".weight", cout, cin); if (bias) n.add(p + ".bias", 1, cout); }
 void u_conv(UNet& n, const std::string& p, int cin, int cout) { n.add(p + ".weight", cout, 9 * pad32(cin)); n.add(p + ".bias", 1, cout); }
 
 void u_res(UNet& n, const std::string& p, int cin, int cout) {
-    u_norm(n, p + ".in_layers.0", cin);
+    w_norm(n, p + ".in_layers.0", cin);
     u_conv(n, p + ".in_layers.2", cin, cout);
-    u_norm(n, p + ".out_layers.0", cout);
+    w_norm(n, p + ".out_layers.0", cout);
     u_conv(n, p + ".out_layers.3", cout, cout);
     if (cin != cout) u_lin(n, p + ".skip_connection", cin, cout);
     n.emb_off[p] = n.emb_total;           // its emb_layers.1 lives in emb_all (all ResBlocks' projections are one GEMM per forward)
     n.emb_total += cout;
 }
 void u_attn(UNet& n, const std::string& p, int c) {
-    u_norm(n, p + ".norm", c);
+    w_norm(n, p + ".norm", c);
     u_lin(n, p + ".proj_in", c, c);
     for (int dd = 0; dd < n.d.transformer_depth; ++dd) {
         const std::string b = p + ".transformer_blocks." + std::to_string(dd);
@@ -269,7 +238,7 @@ void u_attn(UNet& n, const std::string& p, int c) {
         // norm where a row block has few N tiles and the launch is latency bound, and LOSES where M = 20480 / 5120 (the 2560-column GEGLU
         // projection has 40 N tiles per row block: 64.6 -> 130 us), so the wide levels keep the LayerNorm kernel.
         const bool fold = c >= ASD_LN_FOLD_MIN_C;
-        if (!fold) for (const char* nm : {".norm1", ".norm2", ".norm3"}) u_norm(n, b + nm, c);
+        if (!fold) for (const char* nm : {".norm1", ".norm2", ".norm3"}) w_norm(n, b + nm, c);
         n.add(b + ".attn1.to_qk.weight", 2 * c, c);            // q | k rows fused
         if (fold) n.add(b + ".attn1.to_qk.ln_sc", 1, 4 * 2 * c);
         n.add(b + ".attn1.to_v.weight", c, c);
@@ -348,7 +317,7 @@ void unet_build(UNet& n) {
             n.outputs.push_back(b);
         }
     }
-    u_norm(n, "out.0", ch);
+    w_norm(n, "out.0", ch);
     u_conv(n, "out.2", mc, d.out_channels);
     n.add("emb_all.weight", n.emb_total, emb);
     n.add("emb_all.bias", 1, n.emb_total);
@@ -613,41 +582,123 @@ void unet_run(UNet& n, Run& r, const half_t* x, const float* t, const half_t* ct
 }
 
 // ================================================================================================================================
-// VAE encoder: forward with the activations its input gradient needs kept in the workspace, and that backward pass
+// VAE: what encoder and decoder share
 // ================================================================================================================================
-struct VLayer { int kind; std::string name; int cin, cout; };   // 0 conv_in, 1 res, 2 down, 3 attn, 4 out (norm_out + conv_out*quant_conv)
+// kind: 0 conv_in, 1 res, 2 down, 3 attn, 4 out (norm_out + conv_out [* quant_conv]), 5 nearest-2x + conv
+struct VLayer { int kind; std::string name; int cin, cout; };
 
-struct Vae : Net {
+struct VaeNet : Net {
     asd_vae_desc d;
     std::vector<VLayer> plan;
-    std::map<const void*, size_t> scratch_of;      // workspace -> split-K scratch size its last forward laid it out with
-    std::map<const void*, std::vector<int>> recs_of;   // workspace -> GroupNorm record counts of that forward, in allocation order
-    // the last shape whose forward + backward layout was sized and found to fit (valid while the plan table does not change)
-    struct Sized { int batch = 0, H = 0, W = 0, tune = 0; uint64_t gen = 0; int64_t bytes = 0, need = 0; size_t scratch = 0; } sized;
-    std::map<const void*, uint64_t> gen_of;        // workspace -> plan generation of its last forward
+    bool grads = false;     // the weight table also holds the input-gradient forms (".bwd" / ".wt"): the encoder
 };
 
-// conv: forward weights [cout, 9*pad32(cin)], input-gradient weights [pad32(cin), 9*pad32(cout)] (roles swapped, taps flipped for
-// stride 1; the stride-2 gradient is FOUR 2x2 convolutions over the low-resolution gradient image, one per input-pixel parity — the
-// kernel's upsample == 3 form, weights.py: _pack_stride2_dgrad_conv3x3), bias
-void v_conv(Vae& n, const std::string& p, int cin, int cout, bool stride2 = false) {
+// conv: forward weights [cout, 9*pad32(cin)], bias and, with n.grads, input-gradient weights [pad32(cin), 9*pad32(cout)] (roles swapped,
+// taps flipped for stride 1; the stride-2 gradient is FOUR 2x2 convolutions over the low-resolution gradient image, one per input-pixel
+// parity — the kernel's upsample == 3 form, weights.py: _pack_stride2_dgrad_conv3x3)
+void v_conv(VaeNet& n, const std::string& p, int cin, int cout, bool stride2 = false) {
     n.add(p + ".fwd", cout, 9 * pad32(cin));
-    if (stride2) n.add(p + ".bwd", 4 * pad32(cin), 4 * pad32(cout));    // parity form: [4 parities][cin][2 x 2 tap slots x cout]
-    else n.add(p + ".bwd", pad32(cin), 9 * pad32(cout));
+    if (n.grads && stride2) n.add(p + ".bwd", 4 * pad32(cin), 4 * pad32(cout));    // parity form: [4 parities][cin][2 x 2 tap slots x cout]
+    else if (n.grads) n.add(p + ".bwd", pad32(cin), 9 * pad32(cout));
     n.add(p + ".bias", 1, cout);
 }
-void v_norm(Vae& n, const std::string& p, int c) { n.add(p + ".weight", 1, c); n.add(p + ".bias", 1, c); }
-void v_res(Vae& n, const std::string& p, int cin, int cout) {
-    v_norm(n, p + ".norm1", cin);
+void v_lin(VaeNet& n, const std::string& p, int cin, int cout) {
+    n.add(p + ".w", cout, cin);
+    if (n.grads) n.add(p + ".wt", cin, cout);
+    n.add(p + ".b", 1, cout);
+}
+void v_res(VaeNet& n, const std::string& p, int cin, int cout) {
+    w_norm(n, p + ".norm1", cin);
     v_conv(n, p + ".conv1", cin, cout);
-    v_norm(n, p + ".norm2", cout);
+    w_norm(n, p + ".norm2", cout);
     v_conv(n, p + ".conv2", cout, cout);
-    if (cin != cout) { n.add(p + ".nin.w", cout, cin); n.add(p + ".nin.wt", cin, cout); n.add(p + ".nin.b", 1, cout); }
+    if (cin != cout) v_lin(n, p + ".nin", cin, cout);
     n.plan.push_back(VLayer{1, p, cin, cout});
 }
+void v_attn(VaeNet& n, const std::string& p, int c) {
+    w_norm(n, p + ".norm", c);
+    for (const char* nm : {".q", ".k", ".v", ".proj_out"}) v_lin(n, p + nm, c, c);
+    n.plan.push_back(VLayer{3, p, c, c});
+}
+
+// halfs of the largest activation a pass over the plan meets (H, W: the first layer's input)
+size_t max_act(const std::vector<VLayer>& plan, int B, int H, int W) {
+    size_t m = 0;
+    for (const VLayer& l : plan) {
+        if (l.kind == 5) { H *= 2; W *= 2; }
+        const size_t a = (size_t)B * H * W * (l.cin > l.cout ? l.cin : l.cout);
+        if (a > m) m = a;
+        if (l.kind == 2) { H = (H + 1 - 3) / 2 + 1; W = (W + 1 - 3) / 2 + 1; }
+    }
+    return m;
+}
+
+// Buffers a forward leaves behind for the input-gradient pass.  The encoder's forward records them per workspace (VLayout below): the
+// backward pass reads the addresses the forward wrote to, it does not derive them again.
+struct VSaved {
+    const half_t* x = nullptr;        // layer input
+    half_t* t2 = nullptr;             // ResnetBlock: conv1 output (input of norm2)
+    float* st1 = nullptr; float* st2 = nullptr;
+    half_t *q = nullptr, *k = nullptr, *v = nullptr, *p = nullptr;   // attention: projections and softmax probabilities [B][L,L]
+    half_t* out = nullptr;
+    int H = 0, W = 0;
+};
+
+// The mid block's single-head attention over the L positions of each image (AttnBlock, model.py:152-227): hn = GroupNorm(x) ->
+// x + proj_out(softmax(Q K^T / sqrt(C)) V), proj_out launched with `o` (the caller's record request) plus bias and residual.
+// keep (encoder): q, k, v, every image's probabilities and the output are allocated here and stay for the backward pass; without it
+// (decoder) one probability matrix serves every image and the result goes to `out`.
+void mid_attention(VaeNet& n, Run& r, const std::string& p, const half_t* hn, const half_t* x, int B, int L, int C, VSaved* keep, half_t* out,
+                   GemmOpt o) {
+    const int M = B * L;
+    half_t* qkv[3];
+    const char* nm[3] = {".q", ".k", ".v"};
+    for (int j = 0; j < 3; ++j) qkv[j] = r.mem.halfs((size_t)M * C);
+    for (int j = 0; j < 3; ++j) {
+        GemmOpt oj; oj.bias = n.w(p + nm[j] + ".b");
+        gemm(r, hn, M, C, n.w(p + nm[j] + ".w"), C, C, C, qkv[j], C, oj);
+    }
+    const size_t p_stride = keep ? (size_t)L * L : 0;
+    half_t* probs = r.mem.halfs((size_t)(keep ? B : 1) * L * L);
+    half_t* sc = r.mem.halfs((size_t)L * L);
+    half_t* vt = r.mem.halfs((size_t)C * L);
+    half_t* ao = r.mem.halfs((size_t)M * C);
+    for (int b = 0; b < B; ++b) {
+        const size_t ro = (size_t)b * L * C;
+        half_t* P = probs + b * p_stride;
+        gemm(r, qkv[0] + ro, L, C, qkv[1] + ro, L, C, C, sc, L);                               // S = Q K^T
+        LEAF(asd_softmax_f16(sc, L, L, L, 1.0f / sqrtf((float)C), P, L, r.stream));
+        LEAF(asd_transpose_f16(qkv[2] + ro, L, C, C, vt, L, r.stream));
+        gemm(r, P, L, L, vt, C, L, L, ao + ro, C);                                             // O = P V
+    }
+    if (keep) { keep->q = qkv[0]; keep->k = qkv[1]; keep->v = qkv[2]; keep->p = probs; out = keep->out = r.mem.halfs((size_t)M * C); }
+    o.bias = n.w(p + ".proj_out.b"); o.residual = x; o.ldr = C;
+    gemm(r, ao, M, C, n.w(p + ".proj_out.w"), C, C, C, out, C, o);
+}
+
+// ================================================================================================================================
+// VAE encoder: forward with the activations its input gradient needs kept in the workspace, and that backward pass
+// ================================================================================================================================
+// What the launching forward leaves for the backward pass, one per workspace; the handle's `sized` is the same record for the last
+// shape whose forward + backward layout was sized (no `saved`, no `given`).
+struct VLayout {
+    int batch = 0, H = 0, W = 0, tune = 0;
+    uint64_t gen = 0;               // plan generation (asd_gemm_plan_generation) the sizes below hold for; 0: the pass itself moved it (tuning)
+    size_t scratch = 0;             // split-K scratch in front of the activations
+    size_t fwd_end = 0;             // offset in the activation region at which the forward's allocations end and the backward's begin
+    int64_t need = 0, given = 0;    // bytes for forward + backward; bytes the forward was handed
+    std::vector<VSaved> saved;
+    bool same_shape(int b, int h, int w, int t) const { return batch == b && H == h && W == w && tune == t; }
+};
+
+struct Vae : VaeNet {
+    std::map<const void*, VLayout> layout_of;
+    VLayout sized;
+};
 
 void vae_build(Vae& n) {
     const asd_vae_desc& d = n.d;
+    n.grads = true;
     v_conv(n, "encoder.conv_in", d.in_channels, d.ch);
     n.plan.push_back(VLayer{0, "encoder.conv_in", d.in_channels, d.ch});
     int block_in = d.ch;
@@ -664,45 +715,16 @@ void vae_build(Vae& n) {
         }
     }
     v_res(n, "encoder.mid.block_1", block_in, block_in);
-    {
-        const std::string p = "encoder.mid.attn_1";
-        v_norm(n, p + ".norm", block_in);
-        for (const char* nm : {".q", ".k", ".v", ".proj_out"}) {
-            n.add(p + nm + ".w", block_in, block_in); n.add(p + nm + ".wt", block_in, block_in); n.add(p + nm + ".b", 1, block_in);
-        }
-        n.plan.push_back(VLayer{3, p, block_in, block_in});
-    }
+    v_attn(n, "encoder.mid.attn_1", block_in);
     v_res(n, "encoder.mid.block_2", block_in, block_in);
-    v_norm(n, "encoder.norm_out", block_in);
+    w_norm(n, "encoder.norm_out", block_in);
     v_conv(n, "encoder.conv_out_quant", block_in, 2 * d.embed_dim);   // quant_conv o conv_out composed at pack time (both linear)
     n.plan.push_back(VLayer{4, "encoder", block_in, 2 * d.embed_dim});
 }
 
-// Buffers a forward leaves behind for the input-gradient pass.  The backward pass re-derives the very same addresses by
-// replaying the allocation sequence (vae_forward with `launch == false`), so nothing but the workspace travels between the calls.
-struct VSaved {
-    const half_t* x = nullptr;        // layer input
-    half_t* t2 = nullptr;             // ResnetBlock: conv1 output (input of norm2)
-    float* st1 = nullptr; float* st2 = nullptr;
-    half_t *q = nullptr, *k = nullptr, *v = nullptr, *p = nullptr;   // attention: projections and softmax probabilities [B][L,L]
-    half_t* out = nullptr;
-    int H = 0, W = 0;
-};
-
-void vae_forward(Vae& n, Run& r, const half_t* x32, int B, int Hh, int Ww, float* moments, std::vector<VSaved>& saved, bool launch) {
-    const bool was_dry = r.dry;
-    if (!launch) r.dry = true;
-    // two scratch activations for GroupNorm outputs (consumed at once by the following convolution)
-    size_t max_act = 0;
-    {
-        int hh = Hh, ww = Ww;
-        for (const VLayer& l : n.plan) {
-            const size_t a = (size_t)B * hh * ww * (l.cin > l.cout ? l.cin : l.cout);
-            if (a > max_act) max_act = a;
-            if (l.kind == 2) { hh = (hh + 1 - 3) / 2 + 1; ww = (ww + 1 - 3) / 2 + 1; }
-        }
-    }
-    half_t* tmp = r.mem.halfs(max_act);
+void vae_forward(Vae& n, Run& r, const half_t* x32, int B, int Hh, int Ww, float* moments, std::vector<VSaved>& saved) {
+    // one scratch activation for GroupNorm outputs (consumed at once by the following convolution)
+    half_t* tmp = r.mem.halfs(max_act(n.plan, B, Hh, Ww));
     saved.assign(n.plan.size(), VSaved());
     Act h;
     h.p = x32;
@@ -746,29 +768,8 @@ void vae_forward(Vae& n, Run& r, const half_t* x32, int B, int Hh, int Ww, float
             const std::string& p = l.name;
             const int C = l.cin, L = hw;
             groupnorm(r, h.p, C, nullptr, 0, B, hw, n.w(p + ".norm.weight"), n.w(p + ".norm.bias"), 1e-6f, 0, tmp, &sv.st1, &h);
-            sv.q = r.mem.halfs((size_t)M * C); sv.k = r.mem.halfs((size_t)M * C); sv.v = r.mem.halfs((size_t)M * C);
-            half_t* dst[3] = {sv.q, sv.k, sv.v};
-            const char* nm[3] = {".q", ".k", ".v"};
-            for (int j = 0; j < 3; ++j) {
-                GemmOpt o; o.bias = n.w(p + nm[j] + ".b");
-                gemm(r, tmp, M, C, n.w(p + nm[j] + ".w"), C, C, C, dst[j], C, o);
-            }
-            sv.p = r.mem.halfs((size_t)B * L * L);
-            half_t* sc = r.mem.halfs((size_t)L * L);
-            half_t* vt = r.mem.halfs((size_t)C * L);
-            half_t* ao = r.mem.halfs((size_t)M * C);
-            for (int b = 0; b < B; ++b) {
-                const size_t ro = (size_t)b * L * C;
-                half_t* P = sv.p + (size_t)b * L * L;
-                gemm(r, sv.q + ro, L, C, sv.k + ro, L, C, C, sc, L);                                   // S = Q K^T
-                LEAF(asd_softmax_f16(sc, L, L, L, 1.0f / sqrtf((float)C), P, L, r.stream));
-                LEAF(asd_transpose_f16(sv.v + ro, L, C, C, vt, L, r.stream));
-                gemm(r, P, L, L, vt, C, L, L, ao + ro, C);                                             // O = P V
-            }
-            sv.out = r.mem.halfs((size_t)M * C);
-            GemmOpt o; o.bias = n.w(p + ".proj_out.b"); o.residual = h.p; o.ldr = C;                    // x + proj_out(attn)
-            o.gn_rows = hw; o.out = &produced;
-            gemm(r, ao, M, C, n.w(p + ".proj_out.w"), C, C, C, sv.out, C, o);
+            GemmOpt o; o.gn_rows = hw; o.out = &produced;
+            mid_attention(n, r, p, tmp, h.p, B, L, C, &sv, nullptr, o);
         } else {
             groupnorm(r, h.p, l.cin, nullptr, 0, B, hw, n.w(l.name + ".norm_out.weight"), n.w(l.name + ".norm_out.bias"), 1e-6f, 1, tmp, &sv.st1, &h);
             GemmOpt o; o.bias = n.w(l.name + ".conv_out_quant.bias"); o.out_f32 = 1;
@@ -777,37 +778,20 @@ void vae_forward(Vae& n, Run& r, const half_t* x32, int B, int Hh, int Ww, float
         }
         if (sv.out) { h = produced; h.p = sv.out; }
     }
-    r.dry = was_dry;
 }
 
-half_t* gn_bwd(Run& r, const half_t* x, const half_t* dy, int c, int B, int hw, const half_t* g, const half_t* b, int silu, const float* st,
-               const half_t* dx_add, half_t* dx, const Act* src = nullptr) {
+void gn_bwd(Run& r, const half_t* x, const half_t* dy, int c, int B, int hw, const half_t* g, const half_t* b, int silu, const float* st,
+            const half_t* dx_add, half_t* dx) {
     float* bst = r.mem.floats(ASD_GN_STATS_FLOATS(B) - 64 * B);
-    if (src && src->nrec > 0) {          // the conv / GEMM that produced dy left the two reductions behind: no pass over (x, dy) for them
-        LEAF(asd_groupnorm_bwd_apply_f16(x, dy, c, B, hw, g, b, 1e-6f, silu, st, src->rec, src->nrec, dx_add, dx, bst, r.stream));
-    } else
     LEAF(asd_groupnorm_bwd_f16(x, dy, c, B, hw, g, b, 1e-6f, silu, st, dx_add, dx, bst, r.stream));
-    return dx;
 }
 
-// options of a launch whose output is the gradient reaching GroupNorm(x) [+ SiLU]
-GemmOpt feeds_gn_bwd(Act* out, int hw, const half_t* x, const float* fstats, const half_t* gamma, const half_t* beta, int silu) {
-    GemmOpt o;
-    o.gn_rows = hw; o.out = out; o.gn_x = x; o.gn_fstats = fstats; o.gn_gamma = gamma; o.gn_beta = beta; o.gn_silu = silu;
-    o.gn_bwd_form = true;
-    return o;
-}
-
+// Allocates no GroupNorm records (launch_gemm): its activation layout depends on the shape only, its split-K scratch need on the plans.
 void vae_backward(Vae& n, Run& r, const std::vector<VSaved>& saved, const float* d_moments, int B, half_t* dx32) {
     // gradient buffers: four rotating activations of the largest size
-    size_t max_act = 0;
-    for (size_t i = 0; i < n.plan.size(); ++i) {
-        const VLayer& l = n.plan[i];
-        const size_t a = (size_t)B * saved[i].H * saved[i].W * (l.cin > l.cout ? l.cin : l.cout);
-        if (a > max_act) max_act = a;
-    }
+    const size_t largest = max_act(n.plan, B, saved[0].H, saved[0].W);
     half_t* buf[4];
-    for (int j = 0; j < 4; ++j) buf[j] = r.mem.halfs(max_act);
+    for (int j = 0; j < 4; ++j) buf[j] = r.mem.halfs(largest);
     int cur = 0;                                         // buf[cur] holds the gradient w.r.t. the current layer's OUTPUT
     auto other = [&](int k) { return buf[(cur + k) & 3]; };
     const half_t* dy = nullptr;
@@ -820,10 +804,8 @@ void vae_backward(Vae& n, Run& r, const std::vector<VSaved>& saved, const float*
             half_t* dm = other(1);
             LEAF(asd_pad_cast_f16(d_moments, M, l.cout, dm, cp, r.stream));
             half_t* dt = other(2);
-            Act at;
-            conv3x3(r, dm, B, hh, ww, cp, n.w(l.name + ".conv_out_quant.bwd"), l.cin, dt, hh, ww, 1, 1, 0,
-                    feeds_gn_bwd(&at, hw, sv.x, sv.st1, n.w(l.name + ".norm_out.weight"), n.w(l.name + ".norm_out.bias"), 1));
-            gn_bwd(r, sv.x, dt, l.cin, B, hw, n.w(l.name + ".norm_out.weight"), n.w(l.name + ".norm_out.bias"), 1, sv.st1, nullptr, buf[cur], &at);
+            conv3x3(r, dm, B, hh, ww, cp, n.w(l.name + ".conv_out_quant.bwd"), l.cin, dt, hh, ww, 1, 1, 0);
+            gn_bwd(r, sv.x, dt, l.cin, B, hw, n.w(l.name + ".norm_out.weight"), n.w(l.name + ".norm_out.bias"), 1, sv.st1, nullptr, buf[cur]);
             dy = buf[cur];
         } else if (l.kind == 3) {
             const std::string& p = l.name;
@@ -851,11 +833,9 @@ void vae_backward(Vae& n, Run& r, const std::vector<VSaved>& saved, const float*
             gemm(r, dq, M, C, n.w(p + ".q.wt"), C, C, C, d1, C);
             half_t* d2 = other(3);
             { GemmOpt o; o.residual = d1; o.ldr = C; gemm(r, dk, M, C, n.w(p + ".k.wt"), C, C, C, d2, C, o); }
-            Act a1;
-            { GemmOpt o = feeds_gn_bwd(&a1, hw, sv.x, sv.st1, n.w(p + ".norm.weight"), n.w(p + ".norm.bias"), 0);
-              o.residual = d2; o.ldr = C; gemm(r, dv, M, C, n.w(p + ".v.wt"), C, C, C, d1, C, o); }
+            { GemmOpt o; o.residual = d2; o.ldr = C; gemm(r, dv, M, C, n.w(p + ".v.wt"), C, C, C, d1, C, o); }
             half_t* dx = other(3);
-            gn_bwd(r, sv.x, d1, C, B, hw, n.w(p + ".norm.weight"), n.w(p + ".norm.bias"), 0, sv.st1, dy, dx, &a1);   // + the residual path
+            gn_bwd(r, sv.x, d1, C, B, hw, n.w(p + ".norm.weight"), n.w(p + ".norm.bias"), 0, sv.st1, dy, dx);   // + the residual path
             cur = (cur + 3) & 3;
             dy = buf[cur];
         } else if (l.kind == 2) {
@@ -867,24 +847,21 @@ void vae_backward(Vae& n, Run& r, const std::vector<VSaved>& saved, const float*
         } else if (l.kind == 1) {
             const std::string& p = l.name;
             half_t* d3 = other(1);
-            Act a3, a1;
-            conv3x3(r, dy, B, hh, ww, l.cout, n.w(p + ".conv2.bwd"), l.cout, d3, hh, ww, 1, 1, 0,
-                    feeds_gn_bwd(&a3, hw, sv.t2, sv.st2, n.w(p + ".norm2.weight"), n.w(p + ".norm2.bias"), 1));
+            conv3x3(r, dy, B, hh, ww, l.cout, n.w(p + ".conv2.bwd"), l.cout, d3, hh, ww, 1, 1, 0);
             half_t* d2 = other(2);
-            gn_bwd(r, sv.t2, d3, l.cout, B, hw, n.w(p + ".norm2.weight"), n.w(p + ".norm2.bias"), 1, sv.st2, nullptr, d2, &a3);
+            gn_bwd(r, sv.t2, d3, l.cout, B, hw, n.w(p + ".norm2.weight"), n.w(p + ".norm2.bias"), 1, sv.st2, nullptr, d2);
             half_t* d1 = other(1);
-            conv3x3(r, d2, B, hh, ww, l.cout, n.w(p + ".conv1.bwd"), l.cin, d1, hh, ww, 1, 1, 0,
-                    feeds_gn_bwd(&a1, hw, sv.x, sv.st1, n.w(p + ".norm1.weight"), n.w(p + ".norm1.bias"), 1));
+            conv3x3(r, d2, B, hh, ww, l.cout, n.w(p + ".conv1.bwd"), l.cin, d1, hh, ww, 1, 1, 0);
             if (n.has(p + ".nin.w")) {
                 half_t* dmain = other(2);
-                gn_bwd(r, sv.x, d1, l.cin, B, hw, n.w(p + ".norm1.weight"), n.w(p + ".norm1.bias"), 1, sv.st1, nullptr, dmain, &a1);
+                gn_bwd(r, sv.x, d1, l.cin, B, hw, n.w(p + ".norm1.weight"), n.w(p + ".norm1.bias"), 1, sv.st1, nullptr, dmain);
                 half_t* dx = other(3);
                 GemmOpt o; o.residual = dmain; o.ldr = l.cin;
                 gemm(r, dy, M, l.cout, n.w(p + ".nin.wt"), l.cin, l.cout, l.cout, dx, l.cin, o);
                 cur = (cur + 3) & 3;
             } else {
                 half_t* dx = other(2);
-                gn_bwd(r, sv.x, d1, l.cin, B, hw, n.w(p + ".norm1.weight"), n.w(p + ".norm1.bias"), 1, sv.st1, dy, dx, &a1);   // + shortcut
+                gn_bwd(r, sv.x, d1, l.cin, B, hw, n.w(p + ".norm1.weight"), n.w(p + ".norm1.bias"), 1, sv.st1, dy, dx);   // + shortcut
                 cur = (cur + 2) & 3;
             }
             dy = buf[cur];
@@ -897,21 +874,7 @@ void vae_backward(Vae& n, Run& r, const std::vector<VSaved>& saved, const float*
 // ================================================================================================================================
 // VAE decoder: forward only — nothing is kept for a backward pass, the activations rotate through four buffers of the largest size
 // ================================================================================================================================
-struct VaeDec : Net {
-    asd_vae_desc d;
-    std::vector<VLayer> plan;       // 0 conv_in, 1 res, 3 attn, 4 out (norm_out + conv_out), 5 nearest-2x + conv
-};
-
-void d_norm(VaeDec& n, const std::string& p, int c) { n.add(p + ".weight", 1, c); n.add(p + ".bias", 1, c); }
-void d_conv(VaeDec& n, const std::string& p, int cin, int cout) { n.add(p + ".fwd", cout, 9 * pad32(cin)); n.add(p + ".bias", 1, cout); }
-void d_res(VaeDec& n, const std::string& p, int cin, int cout) {
-    d_norm(n, p + ".norm1", cin);
-    d_conv(n, p + ".conv1", cin, cout);
-    d_norm(n, p + ".norm2", cout);
-    d_conv(n, p + ".conv2", cout, cout);
-    if (cin != cout) { n.add(p + ".nin.w", cout, cin); n.add(p + ".nin.b", 1, cout); }
-    n.plan.push_back(VLayer{1, p, cin, cout});
-}
+typedef VaeNet VaeDec;          // forward weights only (grads stays false)
 
 // GroupNorm(32)(+SiLU) of an activation into a buffer the schedule owns, with the ordered statistics pass: an image's result is the
 // same bits in every call and every batch.  (Not the encoder's groupnorm(): its statistics pass sums in arrival order on a grid sized
@@ -924,20 +887,15 @@ void d_groupnorm(Run& r, const Act& x, int c, int B, int hw, const half_t* gamma
 void vae_dec_build(VaeDec& n) {
     const asd_vae_desc& d = n.d;
     int block_in = d.ch * d.ch_mult[d.n_levels - 1];
-    d_conv(n, "decoder.conv_in", d.z_channels, block_in);
+    v_conv(n, "decoder.conv_in", d.z_channels, block_in);
     n.plan.push_back(VLayer{0, "decoder.conv_in", d.z_channels, block_in});
-    d_res(n, "decoder.mid.block_1", block_in, block_in);
-    {
-        const std::string p = "decoder.mid.attn_1";
-        d_norm(n, p + ".norm", block_in);
-        for (const char* nm : {".q", ".k", ".v", ".proj_out"}) { n.add(p + nm + ".w", block_in, block_in); n.add(p + nm + ".b", 1, block_in); }
-        n.plan.push_back(VLayer{3, p, block_in, block_in});
-    }
-    d_res(n, "decoder.mid.block_2", block_in, block_in);
+    v_res(n, "decoder.mid.block_1", block_in, block_in);
+    v_attn(n, "decoder.mid.attn_1", block_in);
+    v_res(n, "decoder.mid.block_2", block_in, block_in);
     for (int lvl = d.n_levels - 1; lvl >= 0; --lvl) {
         const int block_out = d.ch * d.ch_mult[lvl];
         for (int b = 0; b <= d.num_res_blocks; ++b) {
-            d_res(n, "decoder.up." + std::to_string(lvl) + ".block." + std::to_string(b), block_in, block_out);
+            v_res(n, "decoder.up." + std::to_string(lvl) + ".block." + std::to_string(b), block_in, block_out);
             block_in = block_out;
         }
         if (lvl != 0) {     // Upsample.conv in its parity form: [4 parities][cout][2 x 2 taps x cin] (weights._pack_upsample_conv3x3)
@@ -946,7 +904,7 @@ void vae_dec_build(VaeDec& n) {
             n.plan.push_back(VLayer{5, p, block_in, block_in});
         }
     }
-    d_norm(n, "decoder.norm_out", block_in);
+    w_norm(n, "decoder.norm_out", block_in);
     // the image channels padded to 32 output columns (zero rows, zero bias), as the encoder's conv_in input gradient pads its 3
     n.add("decoder.conv_out.fwd", pad32(d.in_channels), 9 * block_in); n.add("decoder.conv_out.bias", 1, pad32(d.in_channels));
     n.plan.push_back(VLayer{4, "decoder", block_in, pad32(d.in_channels)});
@@ -954,17 +912,9 @@ void vae_dec_build(VaeDec& n) {
 
 // Decoder.forward (model.py:619-655): z32 fp16 [B,hl,wl,32] (post_quant_conv already applied) -> x fp16 [B,H,W,pad32(in_channels)]
 void vae_dec_run(VaeDec& n, Run& r, const half_t* z32, int B, int hl, int wl, half_t* image32) {
-    size_t max_act = 0;
-    {
-        int hh = hl, ww = wl;
-        for (const VLayer& l : n.plan) {
-            if (l.kind == 5) { hh *= 2; ww *= 2; }
-            const size_t a = (size_t)B * hh * ww * (l.cin > l.cout ? l.cin : l.cout);
-            if (a > max_act) max_act = a;
-        }
-    }
+    const size_t largest = max_act(n.plan, B, hl, wl);
     half_t* buf[4];
-    for (int j = 0; j < 4; ++j) buf[j] = r.mem.halfs(max_act);
+    for (int j = 0; j < 4; ++j) buf[j] = r.mem.halfs(largest);
     float* stats = r.mem.floats(ASD_GN_STATS_FLOATS(B));      // one GroupNorm at a time reads them: no pass keeps its statistics
     // a buffer none of the live tensors occupies (the dry pass carries null pointers: slot numbers stand in for addresses)
     int slot_of_h = -1;
@@ -1007,32 +957,14 @@ void vae_dec_run(VaeDec& n, Run& r, const half_t* z32, int B, int hl, int wl, ha
             out_slot = pick(s_sc, s_tmp, s_sc == slot_of_h ? -1 : slot_of_h);     // conv1's output is dead once norm2 has read it
             GemmOpt o; o.bias = n.w(p + ".conv2.bias"); o.residual = sc; o.ldr = l.cout; o.out = &produced;   // x + h (model.py:141-148)
             conv3x3(r, tmp, B, hh, ww, l.cout, n.w(p + ".conv2.fwd"), l.cout, buf[out_slot], hh, ww, 1, 1, 0, o);
-        } else if (l.kind == 3) {          // single-head attention over the hw positions of each image, as the encoder's (vae_forward kind 3)
+        } else if (l.kind == 3) {          // single-head attention over the hw positions of each image
             const int C = l.cin, L = hw;
             const int s_tmp = pick(slot_of_h);
             half_t* tmp = buf[s_tmp];
             d_groupnorm(r, h, C, B, hw, n.w(p + ".norm.weight"), n.w(p + ".norm.bias"), 0, tmp, stats);
-            half_t* qkv[3];
-            const char* nm[3] = {".q", ".k", ".v"};
-            for (int j = 0; j < 3; ++j) {
-                qkv[j] = r.mem.halfs((size_t)M * C);
-                GemmOpt o; o.bias = n.w(p + nm[j] + ".b");
-                gemm(r, tmp, M, C, n.w(p + nm[j] + ".w"), C, C, C, qkv[j], C, o);
-            }
-            half_t* sc = r.mem.halfs((size_t)L * L);
-            half_t* P = r.mem.halfs((size_t)L * L);
-            half_t* vt = r.mem.halfs((size_t)C * L);
-            half_t* ao = r.mem.halfs((size_t)M * C);
-            for (int b = 0; b < B; ++b) {
-                const size_t ro = (size_t)b * L * C;
-                gemm(r, qkv[0] + ro, L, C, qkv[1] + ro, L, C, C, sc, L);                                // S = Q K^T
-                LEAF(asd_softmax_f16(sc, L, L, L, 1.0f / sqrtf((float)C), P, L, r.stream));
-                LEAF(asd_transpose_f16(qkv[2] + ro, L, C, C, vt, L, r.stream));
-                gemm(r, P, L, L, vt, C, L, L, ao + ro, C);                                               // O = P V
-            }
             out_slot = pick(slot_of_h, s_tmp);
-            GemmOpt o; o.bias = n.w(p + ".proj_out.b"); o.residual = h.p; o.ldr = C; o.out = &produced;   // x + proj_out(attn)
-            gemm(r, ao, M, C, n.w(p + ".proj_out.w"), C, C, C, buf[out_slot], C, o);
+            GemmOpt o; o.out = &produced;
+            mid_attention(n, r, p, tmp, h.p, B, L, C, nullptr, buf[out_slot], o);
         } else if (l.kind == 5) {          // nearest-2x is the convolution's own gather mode: the upsampled tensor never exists
             out_slot = pick(slot_of_h);
             GemmOpt o; o.bias = n.w(p + ".bias"); o.out = &produced;
@@ -1070,47 +1002,83 @@ int bind(Net& n, const void* const* ptrs, int count) {
     return ASD_OK;
 }
 
+// ---- what the three handles' create / destroy / num_weights / weight_info / bind_weights entries share (`who`: the entry, for the error text)
+#define NET_CHECK(cond, msg) do { if (!(cond)) { asd_set_error("%s: %s", who, msg); return ASD_ERR_ARG; } } while (0)
+template <class T, class D>
+int net_create(const D* desc, void (*build)(T&), void** out) {
+    T* n = new T();
+    n->d = *desc;
+    build(*n);
+    *out = static_cast<Net*>(n);        // every handle is the address of its Net
+    return ASD_OK;
+}
+template <class T, class H> T* net_of(H* h) { return static_cast<T*>((Net*)h); }
+void net_destroy(Net* n) {
+    if (!n) return;
+    if (n->zero_page) (void)hipFree(n->zero_page);
+    delete n;
+}
+int32_t net_num_weights(const Net* n) { return n ? (int32_t)n->specs.size() : 0; }
+int net_weight_info(const char* who, const Net* n, int32_t i, asd_weight_info* info) {
+    NET_CHECK(n && info && i >= 0 && i < (int)n->specs.size(), "bad argument");
+    info->name = n->specs[i].name.c_str(); info->rows = n->specs[i].rows; info->cols = n->specs[i].cols;
+    return ASD_OK;
+}
+int net_bind(const char* who, Net* n, const void* const* ptrs, int32_t count) {
+    NET_CHECK(n && ptrs, "null argument");
+    return bind(*n, ptrs, count);
+}
+
 const size_t TUNE_SCRATCH = (size_t)512 << 20;
 
 // workspace layout: [split-K scratch][activations]
+struct Sizes {
+    size_t scratch = 0, act = 0;
+    size_t bytes() const { return scratch + act + 256; }       // what the workspace_bytes queries answer
+};
 template <class F>
-size_t plan_bytes(F&& pass, bool tune) {
+Sizes size_pass(F&& pass, bool tune) {
     Run r;
     r.dry = true;
     r.tune = tune;        // sizing rule of the statistics records (upper bound while plans may still change)
     pass(r);
-    const size_t scratch = tune ? TUNE_SCRATCH : r.scratch_need;
-    return ((scratch + 255) & ~(size_t)255) + r.mem.off + 256;
+    return Sizes{((tune ? TUNE_SCRATCH : r.scratch_need) + 255) & ~(size_t)255, r.mem.off};
 }
-// *scratch_io: in = scratch size to use (when `given`), out = the size used — the VAE backward must lay the workspace out exactly
-// as its forward did, whatever happened to the plan table in between
-// checked: the caller has already run this very pass on this workspace size under the current plan table (asd_gemm_plan_generation) and
-// passes its scratch size — the sizing walk over the network is skipped (two of them took ~100 us of host time in front of the first
-// launch of every VAE pass, with the GPU idle: the host is not ahead right after the renderer's read-back)
+// size (or take the size the caller has sized this very pass with, and checked against workspace_bytes), check, run.  A given size skips
+// the sizing walk over the network: two of them took ~100 us of host time in front of the first launch of every VAE pass, with the GPU
+// idle (the host is not ahead right after the renderer's read-back).
 template <class F>
-int run_pass(F&& pass, void* workspace, size_t workspace_bytes, hipStream_t stream, bool tune, const void* zero_page,
-             size_t* scratch_io = nullptr, bool given = false, bool checked = false) {
-    size_t scratch = 0;
-    if (checked && given) scratch = *scratch_io;
-    else {
-        Run dry;
-        dry.dry = true;
-        dry.tune = tune;
-        pass(dry);
-        scratch = ((tune ? TUNE_SCRATCH : dry.scratch_need) + 255) & ~(size_t)255;
-        if (given) scratch = *scratch_io;
-        if (scratch_io) *scratch_io = scratch;
-        if (scratch + dry.mem.off > workspace_bytes) {
-            asd_set_error("workspace of %zu bytes is too small (need %zu)", workspace_bytes, scratch + dry.mem.off);
-            return ASD_ERR_ARG;
-        }
+int run_pass(F&& pass, void* workspace, size_t workspace_bytes, hipStream_t stream, bool tune, const void* zero_page, const Sizes* given = nullptr) {
+    const Sizes z = given ? *given : size_pass(pass, tune);
+    if (z.scratch + z.act > workspace_bytes) {
+        asd_set_error("workspace of %zu bytes is too small (need %zu)", workspace_bytes, z.scratch + z.act);
+        return ASD_ERR_ARG;
     }
     Run r;
     r.dry = false; r.tune = tune; r.stream = stream; r.zero_page = zero_page;
-    r.scratch = (float*)workspace; r.scratch_bytes = scratch;
-    r.mem.base = (char*)workspace + scratch;
+    r.scratch = (float*)workspace; r.scratch_bytes = z.scratch;
+    r.mem.base = (char*)workspace + z.scratch;
     pass(r);
     return r.status;
+}
+
+// sizes forward + backward of a shape under the current plans: [scratch of both][forward activations][backward temporaries]
+VLayout vae_size(Vae& n, int batch, int H, int W, int tune) {
+    VLayout z;
+    z.batch = batch; z.H = H; z.W = W; z.tune = tune; z.gen = asd_gemm_plan_generation();
+    std::vector<VSaved> saved;
+    const Sizes s = size_pass([&](Run& r) {
+        vae_forward(n, r, nullptr, batch, H, W, nullptr, saved);
+        z.fwd_end = r.mem.off;
+        vae_backward(n, r, saved, nullptr, batch, nullptr);
+    }, tune != 0);
+    z.scratch = s.scratch; z.need = (int64_t)s.bytes();
+    return z;
+}
+// the last sized shape while the plans are the same, else a walk over both passes (remembered)
+const VLayout& vae_sized(Vae& n, int batch, int H, int W, int tune) {
+    if (!(n.sized.gen == asd_gemm_plan_generation() && n.sized.same_shape(batch, H, W, tune))) n.sized = vae_size(n, batch, H, W, tune);
+    return n.sized;
 }
 
 }  // namespace
@@ -1122,35 +1090,18 @@ int asd_unet_create(const asd_unet_desc* desc, asd_unet** out) {
     ASD_CHECK_ARG(desc && out, "null argument");
     ASD_CHECK_ARG(desc->n_levels >= 1 && desc->n_levels <= 8 && desc->model_channels % 32 == 0 && desc->transformer_depth >= 1, "bad descriptor");
     ASD_CHECK_ARG(desc->num_head_channels == 64, "the attention kernel is built for head_dim 64");
-    UNet* n = new UNet();
-    n->d = *desc;
-    unet_build(*n);
-    *out = (asd_unet*)n;
-    return ASD_OK;
+    return net_create<UNet>(desc, unet_build, (void**)out);
 }
-void asd_unet_destroy(asd_unet* h) {
-    UNet* n = (UNet*)h;
-    if (!n) return;
-    if (n->zero_page) (void)hipFree(n->zero_page);
-    delete n;
-}
-int32_t asd_unet_num_weights(const asd_unet* h) { return h ? (int32_t)((const UNet*)h)->specs.size() : 0; }
-int asd_unet_weight_info(const asd_unet* h, int32_t i, asd_weight_info* info) {
-    const UNet* n = (const UNet*)h;
-    ASD_CHECK_ARG(n && info && i >= 0 && i < (int)n->specs.size(), "bad argument");
-    info->name = n->specs[i].name.c_str(); info->rows = n->specs[i].rows; info->cols = n->specs[i].cols;
-    return ASD_OK;
-}
-int asd_unet_bind_weights(asd_unet* h, const void* const* ptrs, int32_t count) {
-    ASD_CHECK_ARG(h && ptrs, "null argument");
-    return bind(*(UNet*)h, ptrs, count);
-}
+void asd_unet_destroy(asd_unet* h) { net_destroy((Net*)h); }
+int32_t asd_unet_num_weights(const asd_unet* h) { return net_num_weights((const Net*)h); }
+int asd_unet_weight_info(const asd_unet* h, int32_t i, asd_weight_info* info) { return net_weight_info(__func__, (const Net*)h, i, info); }
+int asd_unet_bind_weights(asd_unet* h, const void* const* ptrs, int32_t count) { return net_bind(__func__, (Net*)h, ptrs, count); }
 int64_t asd_unet_workspace_bytes_shared(asd_unet* h, int32_t batch, int32_t H, int32_t W, int32_t n_ctx, int32_t num_frames, int32_t tune,
                                         int32_t n_uniq) {
-    UNet* n = (UNet*)h;
+    UNet* n = net_of<UNet>(h);
     if (!n || batch < 1 || H < 1 || W < 1 || n_ctx < 1) return -1;
-    return (int64_t)plan_bytes([&](Run& r) { unet_run(*n, r, nullptr, nullptr, nullptr, nullptr, batch, H, W, n_ctx, num_frames, nullptr,
-                                                      nullptr, nullptr, n_uniq); }, tune != 0);
+    return (int64_t)size_pass([&](Run& r) { unet_run(*n, r, nullptr, nullptr, nullptr, nullptr, batch, H, W, n_ctx, num_frames, nullptr,
+                                                     nullptr, nullptr, n_uniq); }, tune != 0).bytes();
 }
 int64_t asd_unet_workspace_bytes(asd_unet* h, int32_t batch, int32_t H, int32_t W, int32_t n_ctx, int32_t num_frames, int32_t tune) {
     return asd_unet_workspace_bytes_shared(h, batch, H, W, n_ctx, num_frames, tune, 0);
@@ -1165,7 +1116,7 @@ int asd_unet_fwd(asd_unet* h, const void* x_nhwc, const float* t, const void* co
 int asd_unet_fwd_shared(asd_unet* h, const void* x_nhwc, const float* t, const void* context, const void* camera, int32_t batch, int32_t H,
                         int32_t W, int32_t n_ctx, int32_t num_frames, const int32_t* uniq_src_dev, const int32_t* expand_dev, int32_t n_uniq,
                         void* workspace, int64_t workspace_bytes, float* eps_nhwc, int32_t tune, void* stream) {
-    UNet* n = (UNet*)h;
+    UNet* n = net_of<UNet>(h);
     if (!uniq_src_dev || !expand_dev || n_uniq >= batch) n_uniq = 0;
     ASD_CHECK_ARG(n_uniq == 0 || (n_uniq > 0 && n_uniq % (num_frames > 0 ? num_frames : 1) == 0), "distinct inputs must come in whole groups of num_frames");
     ASD_CHECK_ARG(n && x_nhwc && t && context && workspace && eps_nhwc, "null argument");
@@ -1183,94 +1134,66 @@ int asd_unet_fwd_shared(asd_unet* h, const void* x_nhwc, const float* t, const v
 int asd_vae_enc_create(const asd_vae_desc* desc, asd_vae_enc** out) {
     ASD_CHECK_ARG(desc && out, "null argument");
     ASD_CHECK_ARG(desc->n_levels >= 1 && desc->n_levels <= 8 && desc->ch % 32 == 0 && (2 * desc->embed_dim) % 4 == 0, "bad descriptor");
-    Vae* n = new Vae();
-    n->d = *desc;
-    vae_build(*n);
-    *out = (asd_vae_enc*)n;
-    return ASD_OK;
+    return net_create<Vae>(desc, vae_build, (void**)out);
 }
-void asd_vae_enc_destroy(asd_vae_enc* h) {
-    Vae* n = (Vae*)h;
-    if (!n) return;
-    if (n->zero_page) (void)hipFree(n->zero_page);
-    delete n;
-}
-int32_t asd_vae_enc_num_weights(const asd_vae_enc* h) { return h ? (int32_t)((const Vae*)h)->specs.size() : 0; }
-int asd_vae_enc_weight_info(const asd_vae_enc* h, int32_t i, asd_weight_info* info) {
-    const Vae* n = (const Vae*)h;
-    ASD_CHECK_ARG(n && info && i >= 0 && i < (int)n->specs.size(), "bad argument");
-    info->name = n->specs[i].name.c_str(); info->rows = n->specs[i].rows; info->cols = n->specs[i].cols;
-    return ASD_OK;
-}
-int asd_vae_enc_bind_weights(asd_vae_enc* h, const void* const* ptrs, int32_t count) {
-    ASD_CHECK_ARG(h && ptrs, "null argument");
-    return bind(*(Vae*)h, ptrs, count);
-}
+void asd_vae_enc_destroy(asd_vae_enc* h) { net_destroy((Net*)h); }
+int32_t asd_vae_enc_num_weights(const asd_vae_enc* h) { return net_num_weights((const Net*)h); }
+int asd_vae_enc_weight_info(const asd_vae_enc* h, int32_t i, asd_weight_info* info) { return net_weight_info(__func__, (const Net*)h, i, info); }
+int asd_vae_enc_bind_weights(asd_vae_enc* h, const void* const* ptrs, int32_t count) { return net_bind(__func__, (Net*)h, ptrs, count); }
 // one workspace serves a forward and the backward that follows it: [scratch][forward activations][backward temporaries]
 int64_t asd_vae_enc_workspace_bytes(asd_vae_enc* h, int32_t batch, int32_t H, int32_t W, int32_t tune) {
-    Vae* n = (Vae*)h;
+    Vae* n = net_of<Vae>(h);
     if (!n || batch < 1 || H < 8 || W < 8) return -1;
-    {   // the answer of the last forward pass, while shape and plans are the same
-        const Vae::Sized& z = n->sized;
-        if (z.gen != 0 && z.gen == asd_gemm_plan_generation() && z.batch == batch && z.H == H && z.W == W && z.tune == tune) return z.need;
-    }
-    return (int64_t)plan_bytes([&](Run& r) {
-        std::vector<VSaved> saved;
-        vae_forward(*n, r, nullptr, batch, H, W, nullptr, saved, true);
-        vae_backward(*n, r, saved, nullptr, batch, nullptr);
-    }, tune != 0);
+    return vae_sized(*n, batch, H, W, tune).need;
 }
 int asd_vae_enc_fwd(asd_vae_enc* h, const void* x_nhwc32, int32_t batch, int32_t H, int32_t W, void* workspace, int64_t workspace_bytes,
                     float* moments_nhwc, int32_t tune, void* stream) {
-    Vae* n = (Vae*)h;
+    Vae* n = net_of<Vae>(h);
     ASD_CHECK_ARG(n && x_nhwc32 && workspace && moments_nhwc, "null argument");
     ASD_CHECK_ARG(n->bound, "weights are not bound (asd_vae_enc_bind_weights)");
     ASD_CHECK_ARG(H > 0 && W > 0 && H % (1 << (n->d.n_levels - 1)) == 0 && W % (1 << (n->d.n_levels - 1)) == 0,
                   "H and W must be multiples of 2^(levels - 1): every Downsample halves the image exactly (parity-form input gradient)");
-    // size check against the forward + backward plan, so that the backward can never overrun what the forward accepted
-    const uint64_t gen = asd_gemm_plan_generation();
-    Vae::Sized& z = n->sized;
-    const bool known = z.gen == gen && z.batch == batch && z.H == H && z.W == W && z.tune == tune && workspace_bytes >= z.need;
-    const int64_t need = known ? z.need : asd_vae_enc_workspace_bytes(h, batch, H, W, tune);
-    if (need < 0 || need > workspace_bytes) { asd_set_error("workspace of %lld bytes is too small (need %lld)", (long long)workspace_bytes, (long long)need); return ASD_ERR_ARG; }
-    // the scratch region is sized for both passes (the dry pass walks the backward as well) and remembered per workspace
-    size_t scratch = known ? z.scratch : 0;
-    std::vector<int> log;
+    ASD_CHECK_ARG(batch >= 1 && H >= 8 && W >= 8, "batch >= 1 and an image of at least 8 x 8");
+    // size check against the forward + backward layout, so that the backward can never overrun what the forward accepted; in the steady
+    // state (same shape, same plans) this is the handle's record of the last pass: no walk over the network in front of the first launch
+    VLayout rec = vae_sized(*n, batch, H, W, tune);
+    if (rec.need > workspace_bytes) { asd_set_error("workspace of %lld bytes is too small (need %lld)", (long long)workspace_bytes, (long long)rec.need); return ASD_ERR_ARG; }
+    rec.given = workspace_bytes;
+    const Sizes both{rec.scratch, (size_t)rec.need - rec.scratch - 256};
     const int st = run_pass([&](Run& r) {
-        std::vector<VSaved> saved;
-        if (!r.dry) r.rec_log = &log;
-        vae_forward(*n, r, (const half_t*)x_nhwc32, batch, H, W, moments_nhwc, saved, true);
-        if (r.dry) vae_backward(*n, r, saved, nullptr, batch, nullptr);
-    }, workspace, (size_t)workspace_bytes, (hipStream_t)stream, tune != 0, n->zero_page, &scratch, known, known);
-    if (st == ASD_OK) {
-        n->scratch_of[workspace] = scratch; n->recs_of[workspace] = log;
-        const uint64_t after = asd_gemm_plan_generation();          // tuning inside the pass changes the plans: nothing to remember then
-        n->gen_of[workspace] = after == gen ? gen : 0;
-        if (after == gen) { z.batch = batch; z.H = H; z.W = W; z.tune = tune; z.gen = gen; z.need = need; z.scratch = scratch; }
-        else z.gen = 0;
-    }
-    return st;
+        vae_forward(*n, r, (const half_t*)x_nhwc32, batch, H, W, moments_nhwc, rec.saved);
+        rec.fwd_end = r.mem.off;
+    }, workspace, (size_t)workspace_bytes, (hipStream_t)stream, tune != 0, n->zero_page, &both);
+    if (st != ASD_OK) return st;
+    if (asd_gemm_plan_generation() != rec.gen) rec.gen = 0;      // tuning inside the pass changed the plans: the backward sizes itself
+    n->layout_of[workspace] = std::move(rec);
+    return ASD_OK;
 }
 int asd_vae_enc_bwd(asd_vae_enc* h, const float* d_moments_nhwc, int32_t batch, int32_t H, int32_t W, void* workspace, int64_t workspace_bytes,
                     void* dx_nhwc32, int32_t tune, void* stream) {
-    Vae* n = (Vae*)h;
+    Vae* n = net_of<Vae>(h);
     ASD_CHECK_ARG(n && d_moments_nhwc && workspace && dx_nhwc32, "null argument");
     ASD_CHECK_ARG(n->bound, "weights are not bound (asd_vae_enc_bind_weights)");
-    auto it = n->scratch_of.find(workspace);
-    ASD_CHECK_ARG(it != n->scratch_of.end(), "no forward pass has run on this workspace");
-    size_t scratch = it->second;
-    const std::vector<int>& log = n->recs_of[workspace];
-    return run_pass([&](Run& r) {
-        std::vector<VSaved> saved;
-        r.rec_replay = &log;
-        r.rec_pos = 0;
-        vae_forward(*n, r, nullptr, batch, H, W, nullptr, saved, false);     // replays the forward's allocation sequence: same addresses
-        r.rec_replay = nullptr;                                              // the backward's own launches size their records from the plans
-        vae_backward(*n, r, saved, d_moments_nhwc, batch, (half_t*)dx_nhwc32);
-    }, workspace, (size_t)workspace_bytes, (hipStream_t)stream, tune != 0, n->zero_page, &scratch, true,
-       /* checked: the forward on this workspace sized both passes under the same plans and shape */
-       n->gen_of[workspace] != 0 && n->gen_of[workspace] == asd_gemm_plan_generation() && n->sized.gen == n->gen_of[workspace] &&
-           n->sized.batch == batch && n->sized.H == H && n->sized.W == W && n->sized.tune == tune && workspace_bytes >= n->sized.need);
+    auto it = n->layout_of.find(workspace);
+    ASD_CHECK_ARG(it != n->layout_of.end(), "no forward pass has run on this workspace");
+    const VLayout& rec = it->second;
+    if (!rec.same_shape(batch, H, W, tune) || workspace_bytes < rec.given) {
+        asd_set_error("asd_vae_enc_bwd: called with %d x %d x %d (tune %d, %lld bytes), the forward on this workspace ran %d x %d x %d (tune %d, %lld bytes)",
+                      batch, H, W, tune, (long long)workspace_bytes, rec.batch, rec.H, rec.W, rec.tune, (long long)rec.given);
+        return ASD_ERR_ARG;
+    }
+    // the backward continues the forward's layout: its temporaries begin where the forward's activations end, on the forward's scratch
+    auto pass = [&](Run& r) {
+        r.mem.off = rec.fwd_end;
+        vae_backward(*n, r, rec.saved, d_moments_nhwc, batch, (half_t*)dx_nhwc32);
+    };
+    Sizes both{rec.scratch, (size_t)rec.need - rec.scratch - 256};       // checked by the forward, while the plans are the ones it sized with
+    if (rec.gen == 0 || rec.gen != asd_gemm_plan_generation()) {
+        const Sizes now = size_pass(pass, tune != 0);                    // the backward's activations depend on the shape only, its scratch on the plans
+        if (now.scratch > rec.scratch) { asd_set_error("network workspace too small for a split-K GEMM"); return ASD_ERR_ARG; }
+        both.act = now.act;
+    }
+    return run_pass(pass, workspace, (size_t)workspace_bytes, (hipStream_t)stream, tune != 0, n->zero_page, &both);
 }
 
 // ---- VAE decoder -----------------------------------------------------------------------------------------------------------
@@ -1279,46 +1202,29 @@ int asd_vae_dec_create(const asd_vae_desc* desc, asd_vae_dec** out) {
     ASD_CHECK_ARG(desc->n_levels >= 1 && desc->n_levels <= 8 && desc->ch > 0 && desc->ch % 32 == 0 && desc->num_res_blocks >= 0 && desc->z_channels >= 1 &&
                   desc->z_channels <= 32 && desc->in_channels >= 1 && desc->in_channels <= 32, "bad descriptor");
     for (int i = 0; i < desc->n_levels; ++i) ASD_CHECK_ARG(desc->ch_mult[i] >= 1, "bad descriptor");
-    VaeDec* n = new VaeDec();
-    n->d = *desc;
-    vae_dec_build(*n);
-    *out = (asd_vae_dec*)n;
-    return ASD_OK;
+    return net_create<VaeDec>(desc, vae_dec_build, (void**)out);
 }
-void asd_vae_dec_destroy(asd_vae_dec* h) {
-    VaeDec* n = (VaeDec*)h;
-    if (!n) return;
-    if (n->zero_page) (void)hipFree(n->zero_page);
-    delete n;
-}
-int32_t asd_vae_dec_num_weights(const asd_vae_dec* h) { return h ? (int32_t)((const VaeDec*)h)->specs.size() : 0; }
-int asd_vae_dec_weight_info(const asd_vae_dec* h, int32_t i, asd_weight_info* info) {
-    const VaeDec* n = (const VaeDec*)h;
-    ASD_CHECK_ARG(n && info && i >= 0 && i < (int)n->specs.size(), "bad argument");
-    info->name = n->specs[i].name.c_str(); info->rows = n->specs[i].rows; info->cols = n->specs[i].cols;
-    return ASD_OK;
-}
-int asd_vae_dec_bind_weights(asd_vae_dec* h, const void* const* ptrs, int32_t count) {
-    ASD_CHECK_ARG(h && ptrs, "null argument");
-    return bind(*(VaeDec*)h, ptrs, count);
-}
+void asd_vae_dec_destroy(asd_vae_dec* h) { net_destroy((Net*)h); }
+int32_t asd_vae_dec_num_weights(const asd_vae_dec* h) { return net_num_weights((const Net*)h); }
+int asd_vae_dec_weight_info(const asd_vae_dec* h, int32_t i, asd_weight_info* info) { return net_weight_info(__func__, (const Net*)h, i, info); }
+int asd_vae_dec_bind_weights(asd_vae_dec* h, const void* const* ptrs, int32_t count) { return net_bind(__func__, (Net*)h, ptrs, count); }
 // hl, wl even and hl * wl a multiple of 8: the rows of the mid block's [hl*wl, hl*wl] score matrix are 16-byte aligned GEMM operands;
 // at most 16 images per call (asd_groupnorm_ordered_f16)
 static bool vae_dec_shape_ok(int32_t batch, int32_t hl, int32_t wl) {
     return batch >= 1 && batch <= 16 && hl >= 2 && wl >= 2 && hl % 2 == 0 && wl % 2 == 0 && ((int64_t)hl * wl) % 8 == 0 && (int64_t)hl * wl <= 16384;
 }
 int64_t asd_vae_dec_workspace_bytes(asd_vae_dec* h, int32_t batch, int32_t hl, int32_t wl, int32_t tune) {
-    VaeDec* n = (VaeDec*)h;
+    VaeDec* n = net_of<VaeDec>(h);
     if (!n || !vae_dec_shape_ok(batch, hl, wl)) {
         asd_set_error("VAE decoder: 1 <= batch <= 16 and an even latent grid of at most 16384 positions, hl * wl a multiple of 8 (got %d x %d x %d)", batch, hl, wl);
         return -(int64_t)ASD_ERR_ARG;
     }
     (void)tune;      // the decoder runs fixed tiles: nothing to tune, no tuning scratch
-    return (int64_t)plan_bytes([&](Run& r) { r.fixed = true; vae_dec_run(*n, r, nullptr, batch, hl, wl, nullptr); }, false);
+    return (int64_t)size_pass([&](Run& r) { r.fixed = true; vae_dec_run(*n, r, nullptr, batch, hl, wl, nullptr); }, false).bytes();
 }
 int asd_vae_dec_fwd(asd_vae_dec* h, const void* z_nhwc32, int32_t batch, int32_t hl, int32_t wl, void* workspace, int64_t workspace_bytes,
                     void* x_nhwc32, int32_t tune, void* stream) {
-    VaeDec* n = (VaeDec*)h;
+    VaeDec* n = net_of<VaeDec>(h);
     ASD_CHECK_ARG(n && z_nhwc32 && workspace && x_nhwc32, "null argument");
     ASD_CHECK_ARG(n->bound, "weights are not bound (asd_vae_dec_bind_weights)");
     ASD_CHECK_ARG(vae_dec_shape_ok(batch, hl, wl), "VAE decoder: 1 <= batch <= 16 and an even latent grid of at most 16384 positions, hl * wl a multiple of 8");

@@ -93,6 +93,69 @@ def test_network_weight_tables_match_the_packers():
     assert lib().asd_unet_create(C.byref(bad), C.byref(h)) != 0 and b"head_dim 64" in lib().asd_last_error()
 
 
+_SMALL_UNET = dict(model_channels=64, context_dim=96, channel_mult=(1, 2), attention_resolutions=(1,))
+# (UNetConfig arguments, (batch, hw, frames, tune, n_uniq)) -> asd_unet_workspace_bytes_shared, n_ctx 77
+_UNET_WS = [
+    ({}, (1, 8, 1, 0, 0), 29504512), ({}, (5, 64, 1, 0, 0), 3130461184), ({}, (5, 64, 1, 0, 1), 3033559552), ({}, (2, 16, 1, 0, 0), 102285568),
+    (dict(camera_dim=16), (4, 32, 4, 0, 0), 671877888), (dict(camera_dim=16), (8, 32, 4, 1, 0), 1792818432),
+    (dict(camera_dim=16), (2, 16, 1, 0, 0), 102295808),
+    (_SMALL_UNET, (1, 8, 1, 0, 0), 5608192), (_SMALL_UNET, (5, 64, 1, 0, 0), 447785984), (_SMALL_UNET, (5, 64, 1, 0, 1), 428580352),
+    (_SMALL_UNET, (2, 16, 1, 0, 0), 15465728),
+]
+# (batch, res, tune) -> asd_vae_enc_workspace_bytes for VAEConfig() / VAEConfig(ch=32)
+_VAE_ENC_WS = {(1, 8, 0): (6231040, 5882112), (1, 64, 0): (34339584, 12065024), (4, 256, 0): (1566771456, 418343168),
+               (1, 512, 0): (1707033344, 570565376), (1, 512, 1): (2250533888, 1097989376), (3, 40, 0): (39132672, 13039872)}
+# (batch, hl) -> asd_vae_dec_workspace_bytes(.., tune 0) for VAEConfig() / VAEConfig(ch=32); None: the shape is refused (negative)
+_VAE_DEC_WS = {(1, 4): (2311936, 677632), (1, 8): (8864512, 2327296), (4, 32): (559024384, 143001856), (16, 64): (8929812736, 2282889472),
+               (3, 6): (None, None)}
+
+
+def test_network_workspace_sizes_are_pinned():
+    """asd_unet_workspace_bytes_shared / asd_vae_enc_workspace_bytes / asd_vae_dec_workspace_bytes under the committed plan table (host
+    arithmetic only: no device needed).  The passes carve their workspace by the very walk that answers these queries, so a size that
+    moves is an allocation sequence, a record count or a split-K scratch need that moved."""
+    import ctypes as C
+
+    import pytest
+
+    if os.environ.get("ASD_GEMM_PLAN_FILE"):
+        pytest.skip("ASD_GEMM_PLAN_FILE is set: the recorded sizes are those of the committed gemm_plans.json")
+    from scaledreamer_amd._lib import check, i32, lib
+    from scaledreamer_amd.diffusion import hip_ops as H  # noqa: F401  (pushes the committed plans into the library)
+    from scaledreamer_amd.diffusion import weights as W
+    from scaledreamer_amd.diffusion.engine import unet_desc
+    from scaledreamer_amd.diffusion.vae_hip import vae_desc
+
+    l = lib()
+    assert l.asd_gemm_plan_count() >= 164
+
+    def handle(kind, desc):
+        h = C.c_void_p()
+        check(getattr(l, f"asd_{kind}_create")(C.byref(desc), C.byref(h)))
+        return h
+
+    unets = {}
+    for kw, (B, hw, frames, tune, n_uniq), want in _UNET_WS:
+        key = tuple(sorted(kw.items()))
+        if key not in unets:
+            unets[key] = handle("unet", unet_desc(W.UNetConfig(**kw)))
+        got = l.asd_unet_workspace_bytes_shared(unets[key], i32(B), i32(hw), i32(hw), i32(77), i32(frames), i32(tune), i32(n_uniq))
+        assert got == want, (kw, (B, hw, frames, tune, n_uniq), got, want)
+    for h in unets.values():
+        l.asd_unet_destroy(h)
+    for col, cfg in enumerate((W.VAEConfig(), W.VAEConfig(ch=32))):
+        enc, dec = handle("vae_enc", vae_desc(cfg)), handle("vae_dec", vae_desc(cfg))
+        for (B, res, tune), want in _VAE_ENC_WS.items():
+            for _ in range(2):      # the second query of a shape may be answered from the handle's record of the first
+                got = l.asd_vae_enc_workspace_bytes(enc, i32(B), i32(res), i32(res), i32(tune))
+                assert got == want[col], ("vae_enc", col, (B, res, tune), got, want[col])
+        for (B, hl), want in _VAE_DEC_WS.items():
+            got = l.asd_vae_dec_workspace_bytes(dec, i32(B), i32(hl), i32(hl), i32(0))
+            assert (got < 0) if want[col] is None else (got == want[col]), ("vae_dec", col, (B, hl), got, want[col])
+        l.asd_vae_enc_destroy(enc)
+        l.asd_vae_dec_destroy(dec)
+
+
 def test_gemm_plan_table_round_trip():
     import ctypes as C
 

@@ -120,3 +120,163 @@ def test_asd_vae_enc_fwd_bwd_through_ctypes_matches_the_reference_golden():
     torch.cuda.synchronize()
     l.asd_vae_enc_destroy(h)
     del keep
+
+
+class _VaeSmall:
+    """The diffusion_vae_small golden's encoder behind the C ABI, with its inputs on the device and one workspace per call of ws()."""
+
+    def __init__(self):
+        from scaledreamer_amd._lib import check, lib
+        from scaledreamer_amd.diffusion import weights as W
+        from scaledreamer_amd.diffusion.vae_hip import vae_desc
+
+        self.l = lib()
+        g = dict(np.load(os.path.join(GOLDEN_DIR, "diffusion_vae_small.npz")))
+        ch, nrb, zc = (int(v) for v in g["cfg"])
+        self.cfg = W.VAEConfig(ch=ch, num_res_blocks=nrb, z_channels=zc, ch_mult=tuple(int(v) for v in g["ch_mult"]))
+        seed, self.B, self.res = int(g["seed"]), int(g["batch"]), int(g["res"])
+        self.h = C.c_void_p()
+        check(self.l.asd_vae_enc_create(C.byref(vae_desc(self.cfg)), C.byref(self.h)))
+        self.keep = _bind(self.l, "vae_enc", self.h, W.pack_vae_encoder(W.gen_params(W.vae_encoder_layout(self.cfg)[0], seed), self.cfg))
+        img = torch.tanh(rnd("in.img", (self.B, 3, self.res, self.res), seed))
+        self.x = torch.zeros(self.B, self.res, self.res, 32, device="cuda", dtype=torch.float16)
+        self.x[..., :3] = img.permute(0, 2, 3, 1)
+        self.gm = rnd("in.gmoments", (self.B, 8, self.res // 8, self.res // 8), seed).permute(0, 2, 3, 1).contiguous().cuda()
+        self.moments, self.grad = torch.from_numpy(g["moments"]), torch.from_numpy(g["grad_x_sub"])
+        self.st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def ws(self, B, tune=0):
+        from scaledreamer_amd._lib import i32
+
+        nb = self.l.asd_vae_enc_workspace_bytes(self.h, i32(B), i32(self.res), i32(self.res), i32(tune))
+        assert nb > 0
+        return torch.empty(nb, dtype=torch.uint8, device="cuda")
+
+    def fwd(self, ws, B, tune=0):
+        from scaledreamer_amd._lib import i32
+
+        m = torch.empty(B, self.res // 8, self.res // 8, 8, device="cuda")
+        st = self.l.asd_vae_enc_fwd(self.h, C.c_void_p(self.x.data_ptr()), i32(B), i32(self.res), i32(self.res), C.c_void_p(ws.data_ptr()),
+                                    C.c_int64(ws.numel()), C.c_void_p(m.data_ptr()), i32(tune), self.st)
+        return st, m
+
+    def bwd(self, ws, B, tune=0, res=None, dx=None):
+        from scaledreamer_amd._lib import i32
+
+        res = self.res if res is None else res
+        if dx is None:
+            dx = torch.empty(B, res, res, 32, device="cuda", dtype=torch.float16)
+        st = self.l.asd_vae_enc_bwd(self.h, C.c_void_p(self.gm.data_ptr()), i32(B), i32(res), i32(res), C.c_void_p(ws.data_ptr()),
+                                    C.c_int64(ws.numel()), C.c_void_p(dx.data_ptr()), i32(tune), self.st)
+        return st, dx
+
+    def check(self, m, dx, B, tag):
+        """the bound of the golden test above, on the first B images (a batch item's moments and gradient do not depend on the others)"""
+        for got, ref, what in ((m.permute(0, 3, 1, 2), self.moments[:B], "moments"), (dx[..., :3].permute(0, 3, 1, 2), self.grad[:B], "grad")):
+            l2, mx = _rel(got, ref)
+            print(f"{tag} {what} B={B}: l2 {l2:.3e} max {mx:.3e}")
+            assert l2 < 1e-2 and mx < 1e-2, (tag, what, l2, mx)
+        assert float(dx[..., 3:].abs().max()) == 0.0                                          # gradient of the zero padding channels
+
+    def tuned(self):
+        """every GEMM shape of the golden's batch has a recorded plan (nothing is timed when an earlier test already did)"""
+        ws = self.ws(self.B, 1)
+        assert self.fwd(ws, self.B, 1)[0] == 0 and self.bwd(ws, self.B, 1)[0] == 0
+        torch.cuda.synchronize()
+
+    def close(self):
+        torch.cuda.synchronize()
+        self.l.asd_vae_enc_destroy(self.h)
+
+
+def test_asd_vae_enc_two_workspaces_interleaved():
+    """One handle, two workspaces with different layouts (the golden's batch, and its first image alone): fwd A, fwd B, bwd A, bwd B.
+    Each backward reads the layout ITS forward recorded for its workspace."""
+    v = _VaeSmall()
+    wa, wb = v.ws(v.B), v.ws(1)
+    sa, ma = v.fwd(wa, v.B)
+    sb, mb = v.fwd(wb, 1)
+    assert sa == 0 and sb == 0
+    sa, da = v.bwd(wa, v.B)
+    sb, db = v.bwd(wb, 1)
+    assert sa == 0 and sb == 0, v.l.asd_last_error()
+    v.check(ma, da, v.B, "A")
+    v.check(mb, db, 1, "B")
+    v.close()
+
+
+def test_asd_vae_enc_bwd_after_the_plan_table_changed():
+    """A plan of one of the forward's convolution shapes changes between forward and backward (another split-K: the record count a second
+    walk of the forward would allocate differs, and the plan generation moves).  The backward runs on the recorded layout."""
+    from scaledreamer_amd._lib import GemmArgs, check, i32
+
+    v = _VaeSmall()
+    v.tuned()
+    l, B, res = v.l, v.B, v.res
+    # forward-only shapes: the stride-2 Downsample convolutions (their input gradient is the parity-form launch, another plan key)
+    keys, c, hw = [], v.cfg.ch, res
+    for mult in v.cfg.ch_mult[:-1]:
+        c = v.cfg.ch * mult
+        keys.append((B * (hw // 2) ** 2, c, 9 * c, 1, hw, c, 2, 0, 0))
+        hw //= 2
+    plans, buf = {}, (C.c_int32 * 11)()
+    for i in range(l.asd_gemm_plan_count()):
+        check(l.asd_gemm_plan_entry(i32(i), buf))
+        plans[tuple(buf[:9])] = (buf[9], buf[10])
+
+    def records(key):
+        a = GemmArgs()
+        a.M, a.N, a.K, a.conv, a.Hin, a.Cin, a.stride, a.upsample, a.pad = key
+        a.Win, a.Hout, a.Wout, a.ldw, a.ldc = a.Hin, a.Hin // 2, a.Hin // 2, a.K, a.N
+        a.gn_rows, a.gn_cg = a.Hout * a.Wout, a.N // 32
+        return l.asd_gemm_gn_records(C.byref(a))
+
+    ws = v.ws(B)
+    st, m = v.fwd(ws, B)
+    assert st == 0
+    changed = None
+    for key in keys:
+        assert key in plans, ("the tuning pass recorded no plan for", key)
+        tile, split = plans[key]
+        before, gen = records(key), l.asd_gemm_plan_generation()
+        check(l.asd_gemm_plan_set(*[i32(k) for k in key], i32(tile), i32(2 if split == 1 else 1)))
+        if records(key) != before and l.asd_gemm_plan_generation() != gen:
+            changed = (key, tile, split)
+            break
+        check(l.asd_gemm_plan_set(*[i32(k) for k in key], i32(tile), i32(split)))
+    assert changed is not None, "no Downsample shape whose record count depends on its split-K"
+    try:
+        st, dx = v.bwd(ws, B)
+        assert st == 0, l.asd_last_error()
+        v.check(m, dx, B, "plan changed")
+    finally:
+        key, tile, split = changed
+        torch.cuda.synchronize()
+        check(l.asd_gemm_plan_set(*[i32(k) for k in key], i32(tile), i32(split)))
+    v.close()
+
+
+def test_asd_vae_enc_bwd_refuses_another_shape_than_its_forward():
+    v = _VaeSmall()
+    l, B, res = v.l, v.B, v.res
+    ws = v.ws(B)
+    fresh = v.ws(B)
+    st, m = v.fwd(ws, B)
+    assert st == 0
+    for bad_b, bad_res in ((B + 1, res), (B, res // 2)):
+        dx = torch.full((bad_b, bad_res, bad_res, 32), 7.0, device="cuda", dtype=torch.float16)
+        st = l.asd_vae_enc_bwd(v.h, C.c_void_p(v.gm.data_ptr()), C.c_int32(bad_b), C.c_int32(bad_res), C.c_int32(bad_res), C.c_void_p(ws.data_ptr()),
+                               C.c_int64(ws.numel()), C.c_void_p(dx.data_ptr()), C.c_int32(0), v.st)
+        err = l.asd_last_error()
+        assert st != 0
+        assert f"{bad_b} x {bad_res} x {bad_res}".encode() in err and f"{B} x {res} x {res}".encode() in err, err
+        torch.cuda.synchronize()
+        assert bool((dx == 7.0).all())                                                        # nothing was launched
+    assert v.bwd(fresh, B)[0] != 0 and b"no forward pass" in l.asd_last_error()               # a workspace no forward has run on
+    st, dx1 = v.bwd(ws, B)
+    assert st == 0, l.asd_last_error()
+    st, dx2 = v.bwd(ws, B)                                                                    # again, as under retain_graph
+    assert st == 0, l.asd_last_error()
+    v.check(m, dx1, B, "first")
+    v.check(m, dx2, B, "second")
+    v.close()
