@@ -38,7 +38,10 @@ typedef struct asd_grid_meta {
     uint32_t n_levels;            /* L */
     uint32_t n_features;          /* F, must be 2 */
     uint32_t n_params;            /* total floats = sum(size[l]) * F */
-    uint32_t reserved;
+    uint32_t n_masked_levels;     /* level limit (ProgressiveBandHashGrid, networks.py:129-167): the finest n_masked_levels levels encode
+                                   * to exactly +0.0f and receive no gradient; 0 = the plain grid, n_levels = nothing active.  Honoured by
+                                   * asd_hashgrid_*, asd_field_density / _fwd / _bwd (and the render pass through them); > n_levels is
+                                   * ASD_ERR_ARG; asd_field_analytic_* and asd_envmap_* return ASD_ERR_UNSUPPORTED for a non-zero limit */
     float    scale[ASD_MAX_LEVELS];       /* 2^(l*log2(per_level_scale)) * base_res - 1 */
     uint32_t resolution[ASD_MAX_LEVELS];  /* ceil(scale)+1 */
     uint32_t offset[ASD_MAX_LEVELS];      /* first entry (in F-tuples) of the level's table */

@@ -29,13 +29,23 @@ class GridMeta(C.Structure):
         ("n_levels", C.c_uint32),
         ("n_features", C.c_uint32),
         ("n_params", C.c_uint32),
-        ("reserved", C.c_uint32),
+        ("reserved", C.c_uint32),       # asd_grid_meta.n_masked_levels: read and written through the property below.  The field keeps the name
+                                        # the CPU oracle's struct has for this word (tests/test_abi_cpu.py compares the two field lists by name)
         ("scale", C.c_float * ASD_MAX_LEVELS),
         ("resolution", C.c_uint32 * ASD_MAX_LEVELS),
         ("offset", C.c_uint32 * ASD_MAX_LEVELS),
         ("size", C.c_uint32 * ASD_MAX_LEVELS),
         ("dense", C.c_uint32 * ASD_MAX_LEVELS),
     ]
+
+    @property
+    def n_masked_levels(self) -> int:
+        """the level limit (include/asd_hip.h): the finest n_masked_levels levels encode to +0.0f and receive no gradient; 0 = the plain grid"""
+        return int(self.reserved)
+
+    @n_masked_levels.setter
+    def n_masked_levels(self, v: int) -> None:
+        self.reserved = int(v)
 
 
 class FieldCfg(C.Structure):

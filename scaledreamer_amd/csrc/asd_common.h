@@ -245,28 +245,48 @@ __device__ __forceinline__ float asd_corner_weight(const asd_cell& q, int c) {
     return wt;
 }
 
-// Gather-interpolate all levels of one point. enc[2L] stays in VGPRs (L is a compile-time constant).
-template <int L>
+// Level limit (asd_grid_meta::n_masked_levels): levels l < asd_active_levels(m) are gathered and scattered, the finer ones encode to +0.0f
+// and receive no gradient.  The meta reaches every kernel by value, so the count is wave-uniform: the guards below are scalar compares.
+__host__ __device__ __forceinline__ int asd_active_levels(const asd_grid_meta& m) { return (int)m.n_levels - (int)m.n_masked_levels; }
+#define ASD_CHECK_LEVEL_LIMIT(meta) ASD_CHECK_ARG((meta)->n_masked_levels <= (meta)->n_levels, "n_masked_levels exceeds n_levels")
+
+// one level of one point (already inside the unit cube): the 8 gathers, then the trilinear sum in corner order
+__device__ __forceinline__ void asd_encode_level(const asd_grid_meta& m, const float* __restrict__ params, int l, float x, float y, float z,
+                                                 float& e0, float& e1) {
+    const asd_cell q = asd_cell_of(m, l, x, y, z);
+    const float2* __restrict__ tab = reinterpret_cast<const float2*>(params) + m.offset[l];
+    float2 v[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c)  // issue the 8 independent 8-byte gathers first
+        v[c] = tab[asd_corner_index(m, l, q, c)];
+    float f0 = 0.f, f1 = 0.f;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const float wt = asd_corner_weight(q, c);
+        f0 = fmaf(wt, v[c].x, f0);
+        f1 = fmaf(wt, v[c].y, f1);
+    }
+    e0 = f0;
+    e1 = f1;
+}
+
+// Gather-interpolate the active levels of one point, zeros for the masked ones. enc[2L] stays in VGPRs (L is a compile-time constant).
+// Every level sits behind its own scalar compare with the level limit; the enc[] indices stay compile-time constants.  LIMITED = false
+// is the plain grid without the compares, for the kernels whose entries refuse a level limit (analytic field, environment map) and
+// for asd_field_density on a plain grid (the compares cost that kernel a wave of occupancy: profiles/field_progressive_resources.txt).
+template <int L, bool LIMITED = true>
 __device__ __forceinline__ void asd_encode(const asd_grid_meta& m, const float* __restrict__ params, float x,
                                            float y, float z, float (&enc)[2 * L]) {
     x = asd_unit(x); y = asd_unit(y); z = asd_unit(z);
+    const int act = asd_active_levels(m);
 #pragma unroll
     for (int l = 0; l < L; ++l) {
-        const asd_cell q = asd_cell_of(m, l, x, y, z);
-        const float2* __restrict__ tab = reinterpret_cast<const float2*>(params) + m.offset[l];
-        float2 v[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c)  // issue the 8 independent 8-byte gathers first
-            v[c] = tab[asd_corner_index(m, l, q, c)];
-        float f0 = 0.f, f1 = 0.f;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const float wt = asd_corner_weight(q, c);
-            f0 = fmaf(wt, v[c].x, f0);
-            f1 = fmaf(wt, v[c].y, f1);
+        if (!LIMITED || l < act) {
+            asd_encode_level(m, params, l, x, y, z, enc[2 * l], enc[2 * l + 1]);
+        } else {
+            enc[2 * l] = 0.f;
+            enc[2 * l + 1] = 0.f;
         }
-        enc[2 * l] = f0;
-        enc[2 * l + 1] = f1;
         // keep at most 4 levels (32 gathers, 64 VGPRs) in flight: without this fence hipcc hoists all
         // 128 gathers of the 16 levels to the top and spills (256 VGPRs, occupancy 1)
         if ((l & 3) == 3) __builtin_amdgcn_sched_barrier(0);
@@ -306,8 +326,10 @@ __device__ __forceinline__ void asd_scatter_runs(const asd_grid_meta& m, float* 
         static_assert(ASD_PRIV_COPIES == 8, "one copy per XCD");
         priv += (size_t)copy * priv_stride;
     }
+    const int act = asd_active_levels(m);       // level limit: the masked levels' denc (W1^T . da, not zero) is dropped, not scattered
 #pragma unroll
     for (int l = 0; l < (NAGG < L ? NAGG : L); ++l) {
+        if (l >= act) continue;
         const float g0 = active ? denc[2 * l] : 0.f, g1 = active ? denc[2 * l + 1] : 0.f;
         const asd_cell q = asd_cell_of(m, l, x, y, z);
         float* __restrict__ tab = (l < NPRIV ? priv : dparams) + 2u * (size_t)m.offset[l];
@@ -349,7 +371,7 @@ __device__ __forceinline__ void asd_scatter_runs(const asd_grid_meta& m, float* 
             if (self_f1 && v[2 * c + 1] != 0.f) atomicAdd(tab + 2u * (size_t)idx + 1, v[2 * c + 1]);
         }
     }
-    if (NAGG >= L || !FINE) return;      // FINE = false: the levels >= NAGG go through the paged scatter (field_paged.hip)
+    if (NAGG >= L || !FINE || act <= NAGG) return;      // FINE = false: the levels >= NAGG go through the paged scatter (field_paged.hip)
     // ---- fine levels, transposed: lane = (source sample k = lane >> 2 of group q, x corner (lane >> 1) & 1, feature lane & 1)
     const int xb = (lane >> 1) & 1, ft = lane & 1;
 #pragma unroll 1
@@ -361,7 +383,7 @@ __device__ __forceinline__ void asd_scatter_runs(const asd_grid_meta& m, float* 
         for (int l = (NAGG < L ? NAGG : L); l < L; ++l) {
             const float ga = __shfl(denc[2 * l], src, 64), gb = __shfl(denc[2 * l + 1], src, 64);
             const float g = ft ? gb : ga;
-            if (!sact || g == 0.f) continue;
+            if (l >= act || !sact || g == 0.f) continue;
             // asd_cell_of's arithmetic with this lane's x corner added to cx.  Written out, not built on the helper: with it (three forms
             // tried) hipcc schedules every kernel that scatters differently (tools/asm_same.py) — keep the two in step
             const float s = m.scale[l];

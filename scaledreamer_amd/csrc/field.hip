@@ -8,6 +8,8 @@
 // Roofline: HBM/L2 gather bound — 16 levels x 8 corners x 8 B = 1024 B gathered per encode
 // (SURVEY.md §8d); the MLPs (2112 / 2240 MAC per point) run on the VALU with the weights read through
 // the scalar cache (uniform addresses -> s_load), so no LDS or VGPR is spent on weights.
+// Level limit (asd_grid_meta.n_masked_levels, ProgressiveBandHashGrid networks.py:129-167): 64 B x active levels per encode — the masked
+// levels' gathers, finite-difference re-encodes, atomics and paged items are skipped, their outputs are exact zeros.
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -31,6 +33,10 @@ __global__ __launch_bounds__(256) void hashgrid_fwd_kernel(const asd_grid_meta m
         int l;
         asd_point_level(t, L, i, l);
         if (i >= n) continue;
+        if (l >= asd_active_levels(m)) {       // level limit: a wave is on one level, so the compare is uniform
+            reinterpret_cast<float2*>(out)[i * L + l] = make_float2(0.f, 0.f);
+            continue;
+        }
         const float s = m.scale[l];
         const asd_cell q = asd_cell_at(s, asd_unit(x[3 * i]), asd_unit(x[3 * i + 1]), asd_unit(x[3 * i + 2]));
         const float2* __restrict__ tab = reinterpret_cast<const float2*>(params) + m.offset[l];
@@ -57,7 +63,7 @@ __global__ __launch_bounds__(256) void hashgrid_bwd_kernel(const asd_grid_meta m
         int64_t i;
         int l;
         asd_point_level(t, L, i, l);
-        if (i >= n) continue;
+        if (i >= n || l >= asd_active_levels(m)) continue;       // level limit: dout of a masked level is ignored
         const float2 g = reinterpret_cast<const float2*>(dout)[i * L + l];
         if (g.x == 0.f && g.y == 0.f) continue;
         const float s = m.scale[l];
@@ -112,7 +118,7 @@ __device__ __forceinline__ void vox_encode(const asd_grid_meta& m, const float* 
     }
 }
 
-template <int L, int H, int ENC = 0>
+template <int L, int H, int ENC = 0, bool LIMITED = true>
 __device__ __forceinline__ float field_raw(const asd_grid_meta& m, const asd_field_cfg& c,
                                            const float* __restrict__ grid, const float* __restrict__ w1d,
                                            const float* __restrict__ w2d, float px, float py, float pz,
@@ -121,14 +127,16 @@ __device__ __forceinline__ float field_raw(const asd_grid_meta& m, const asd_fie
     const float y = (py - c.bbox_min[1]) / (c.bbox_max[1] - c.bbox_min[1]);
     const float z = (pz - c.bbox_min[2]) / (c.bbox_max[2] - c.bbox_min[2]);
     if constexpr (ENC == 1) vox_encode<2 * L>(m, grid, x, y, z, enc);
-    else asd_encode<L>(m, grid, x, y, z, enc);
+    else asd_encode<L, LIMITED>(m, grid, x, y, z, enc);
     return mlp1<2 * L, H>(w1d, w2d, enc) + field_bias(c, px, py, pz);
 }
 
 // ---------------------------------------------------------------------------------------------------
 // sigma only (marcher sigma_fn, occupancy update)
 // ---------------------------------------------------------------------------------------------------
-template <int L, int H>
+// LIMITED: the meta carries a level limit.  Two instantiations, chosen by the host: on a plain grid the kernel is the one without the
+// per-level compares, which cost it registers (71 -> 78 VGPRs, 7 -> 6 waves per SIMD) and 2 % of its time on an MI355X
+template <int L, int H, bool LIMITED>
 __global__ __launch_bounds__(256, 4) void field_density_kernel(const asd_grid_meta m, const asd_field_cfg c,
                                                             const float* __restrict__ grid,
                                                             const float* __restrict__ w1d,
@@ -139,7 +147,7 @@ __global__ __launch_bounds__(256, 4) void field_density_kernel(const asd_grid_me
     const int nn = n_dev ? min(*n_dev, n) : n;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < nn; i += gridDim.x * 256) {
         float enc[2 * L];
-        const float raw = field_raw<L, H>(m, c, grid, w1d, w2d, points[3 * i], points[3 * i + 1], points[3 * i + 2], enc);
+        const float raw = field_raw<L, H, 0, LIMITED>(m, c, grid, w1d, w2d, points[3 * i], points[3 * i + 1], points[3 * i + 2], enc);
         sigma[i] = field_act(c, raw);
     }
 }
@@ -409,6 +417,13 @@ __global__ __launch_bounds__(256, ASD_FIELD_BWD_BLOCKS) void field_bwd_sample_ke
             }
         }
         }   // !PRE
+        if constexpr (ENC == 0) {
+            // level limit: denc of a masked level is W1^T . da, not zero — dropped here, so neither scatter nor the paged rows see it
+            const int act = asd_active_levels(m);
+#pragma unroll
+            for (int l = 0; l < L; ++l)
+                if (l >= act) { denc[2 * l] = 0.f; denc[2 * l + 1] = 0.f; }
+        }
         if constexpr (ENC == 1) {
             // the scatter into the feature volume is asd_voxel_sample_bwd's (run-aggregated, request-coalesced): leave it the rows
             if (active) {
@@ -577,7 +592,7 @@ __global__ __launch_bounds__(256) void envmap_fwd_kernel(const asd_grid_meta m, 
     constexpr int NIN = 2 * L;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
         float enc[NIN], h0[H], h1[H];
-        asd_encode<L>(m, grid, (dirs[3 * i] + 1.f) / 2.f, (dirs[3 * i + 1] + 1.f) / 2.f, (dirs[3 * i + 2] + 1.f) / 2.f, enc);
+        asd_encode<L, false>(m, grid, (dirs[3 * i] + 1.f) / 2.f, (dirs[3 * i + 1] + 1.f) / 2.f, (dirs[3 * i + 2] + 1.f) / 2.f, enc);
 #pragma unroll
         for (int h = 0; h < H; ++h) {
             float a = 0.f;
@@ -625,7 +640,7 @@ __global__ __launch_bounds__(256) void envmap_bwd_kernel(const asd_grid_meta m, 
     float x = 0.f, y = 0.f, z = 0.f;
     if (active) {
         x = (dirs[3 * i] + 1.f) / 2.f; y = (dirs[3 * i + 1] + 1.f) / 2.f; z = (dirs[3 * i + 2] + 1.f) / 2.f;
-        asd_encode<L>(m, grid, x, y, z, enc);
+        asd_encode<L, false>(m, grid, x, y, z, enc);
     } else {
 #pragma unroll
         for (int k = 0; k < NIN; ++k) enc[k] = 0.f;
@@ -782,6 +797,7 @@ int asd_hashgrid_fwd(const asd_grid_meta* meta, const float* params, const float
                      void* stream) {
     if (n == 0) return ASD_OK;
     ASD_CHECK_ARG(meta && params && x && out && n > 0, "null argument");
+    ASD_CHECK_LEVEL_LIMIT(meta);
     hipLaunchKernelGGL(hashgrid_fwd_kernel, dim3(asd_point_level_grid(n, (int)meta->n_levels)), dim3(256), 0, (hipStream_t)stream, *meta,
                        params, x, n, out);
     ASD_LAUNCH_CHECK();
@@ -792,6 +808,7 @@ int asd_hashgrid_bwd(const asd_grid_meta* meta, const float* x, const float* dou
                      void* stream) {
     if (n == 0) return ASD_OK;
     ASD_CHECK_ARG(meta && x && dout && dparams && n > 0, "null argument");
+    ASD_CHECK_LEVEL_LIMIT(meta);
     hipLaunchKernelGGL(hashgrid_bwd_kernel, dim3(asd_point_level_grid(n, (int)meta->n_levels)), dim3(256), 0, (hipStream_t)stream, *meta,
                        x, dout, n, dparams);
     ASD_LAUNCH_CHECK();
@@ -812,9 +829,14 @@ int asd_field_density(const asd_grid_meta* meta, const asd_field_cfg* cfg, const
                       const int32_t* n_dev, float* sigma, void* stream) {
     if (n == 0) return ASD_OK;
     ASD_CHECK_ARG(meta && cfg && grid_params && w1_density && w2_density && points && sigma && n > 0, "null argument");
+    ASD_CHECK_LEVEL_LIMIT(meta);
     if (!asd_field_supported(meta, cfg, "field")) return ASD_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((field_density_kernel<16, 64>), dim3(asd_grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
-                       *meta, *cfg, grid_params, w1_density, w2_density, points, n, n_dev, sigma);
+    if (meta->n_masked_levels == 0)
+        hipLaunchKernelGGL((field_density_kernel<16, 64, false>), dim3(asd_grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
+                           *meta, *cfg, grid_params, w1_density, w2_density, points, n, n_dev, sigma);
+    else
+        hipLaunchKernelGGL((field_density_kernel<16, 64, true>), dim3(asd_grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
+                           *meta, *cfg, grid_params, w1_density, w2_density, points, n, n_dev, sigma);
     ASD_LAUNCH_CHECK();
     return ASD_OK;
 }
@@ -825,6 +847,7 @@ int asd_field_fwd(const asd_grid_meta* meta, const asd_field_cfg* cfg, const flo
                   float* features, float* normal, float* fd_grad, float* enc_save, void* stream) {
     if (n == 0) return ASD_OK;
     ASD_CHECK_ARG(meta && cfg && grid_params && w1_density && w2_density && points && sigma && n > 0, "null argument");
+    ASD_CHECK_LEVEL_LIMIT(meta);
     if (!asd_field_supported(meta, cfg, "field")) return ASD_ERR_UNSUPPORTED;
     ASD_CHECK_ARG(cfg->n_feature_dims == 0 || !features || (w1_feature && w2_feature), "feature weights missing");
     hipLaunchKernelGGL((field_fwd_kernel<16, 64, 3>), dim3(asd_grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
@@ -910,6 +933,7 @@ int asd_field_bwd(const asd_grid_meta* meta, const asd_field_cfg* cfg, const flo
     ASD_CHECK_ARG(meta && cfg && grid_params && w1_density && w2_density && points && enc_save && sigma &&
                       d_grid_params && dw1_density && dw2_density && workspace && n > 0,
                   "null argument");
+    ASD_CHECK_LEVEL_LIMIT(meta);
     if (!asd_field_supported(meta, cfg, "field")) return ASD_ERR_UNSUPPORTED;
     ASD_CHECK_ARG(cfg->n_feature_dims == 3 || !d_features, "d_features given but no feature network");
     ASD_CHECK_ARG(cfg->n_feature_dims == 0 || (dw1_feature && dw2_feature && w1_feature && w2_feature), "feature gradients missing");
@@ -932,7 +956,8 @@ int asd_field_bwd(const asd_grid_meta* meta, const asd_field_cfg* cfg, const flo
     // the levels >= ASD_FIELD_NAGG (hashed: neighbouring samples share no entry) through the paged scatter — no global atomics
     static_assert(16 - ASD_FIELD_NAGG == ASD_PG_NF, "field_paged.h is sized for the levels >= ASD_FIELD_NAGG of the 16-level grid");
     asd_paged_plan plan;
-    const bool paged = field_paged_on() && asd_paged_plan_init(meta, ASD_FIELD_NAGG, &plan);
+    // (level limit: with no active level >= ASD_FIELD_NAGG there is nothing to page — no row writes, no fill, no accumulate)
+    const bool paged = field_paged_on() && asd_active_levels(*meta) > ASD_FIELD_NAGG && asd_paged_plan_init(meta, ASD_FIELD_NAGG, &plan);
     float *const pg_g = paged ? at(L.pg_g) : nullptr, *const pg_pos = paged ? at(L.pg_pos) : nullptr;
     const dim3 grid(asd_div_up(n, 256)), block(256);
     // slabs of the first-layer weight gradient: one per block of the launch that writes them, and slab_reduce_kernel sums that many
@@ -1049,6 +1074,10 @@ int asd_envmap_fwd(const asd_grid_meta* meta, const float* grid_params, const fl
         asd_set_error("envmap kernels are built for 4 levels and 16 hidden units (got %u, %d)", meta->n_levels, n_hidden);
         return ASD_ERR_UNSUPPORTED;
     }
+    if (meta->n_masked_levels != 0) {
+        asd_set_error("envmap kernels take no level limit (n_masked_levels = %u): the background grid is not progressive", meta->n_masked_levels);
+        return ASD_ERR_UNSUPPORTED;
+    }
     if (n == 0) return ASD_OK;
     hipLaunchKernelGGL((envmap_fwd_kernel<4, 16>), dim3(asd_grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, *meta,
                        grid_params, w0, w1, w2, dirs, n, color);
@@ -1064,6 +1093,10 @@ int asd_envmap_bwd(const asd_grid_meta* meta, const float* grid_params, const fl
                   "null argument");
     if (meta->n_levels != 4 || n_hidden != 16) {
         asd_set_error("envmap kernels are built for 4 levels and 16 hidden units (got %u, %d)", meta->n_levels, n_hidden);
+        return ASD_ERR_UNSUPPORTED;
+    }
+    if (meta->n_masked_levels != 0) {
+        asd_set_error("envmap kernels take no level limit (n_masked_levels = %u): the background grid is not progressive", meta->n_masked_levels);
         return ASD_ERR_UNSUPPORTED;
     }
     if (n == 0) return ASD_OK;

@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256, 4) void field_analytic_fwd_kernel(const asd_gr
         const float px = points[3 * (size_t)i], py = points[3 * (size_t)i + 1], pz = points[3 * (size_t)i + 2];
         const float ux = (px - c.bbox_min[0]) / bx, uy = (py - c.bbox_min[1]) / by, uz = (pz - c.bbox_min[2]) / bz;
         float enc[NIN], g[NIN];
-        asd_encode<L>(m, grid, ux, uy, uz, enc);
+        asd_encode<L, false>(m, grid, ux, uy, uz, enc);
         const float raw = an_mlp1_g<NIN, H>(w1d, w2d, enc, g) + field_bias(c, px, py, pz);
         sigma[i] = field_act(c, raw);
         if (enc_save) asd_row_store(enc_save + (size_t)i * NIN, enc);
@@ -434,6 +434,11 @@ int asd_field_analytic_fwd(const asd_grid_meta* meta, const asd_field_cfg* cfg, 
     if (n == 0) return ASD_OK;
     ASD_CHECK_ARG(meta && cfg && grid_params && w1_density && w2_density && points && sigma && normal && n > 0, "null argument");
     if (!asd_field_supported(meta, cfg, "analytic field")) return ASD_ERR_UNSUPPORTED;
+    if (meta->n_masked_levels != 0) {
+        asd_set_error("analytic field kernels take no level limit (n_masked_levels = %u): the position gradient of a progressive grid is not "
+                      "implemented, use finite-difference normals", meta->n_masked_levels);
+        return ASD_ERR_UNSUPPORTED;
+    }
     ASD_CHECK_ARG(cfg->n_feature_dims == 0 || !features || (w1_feature && w2_feature), "feature weights missing");
     hipLaunchKernelGGL((field_analytic_fwd_kernel<16, 64, 3>), dim3(asd_grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, *meta, *cfg,
                        grid_params, w1_density, w2_density, w1_feature, w2_feature, points, n, sigma,
@@ -458,6 +463,11 @@ int asd_field_analytic_bwd(const asd_grid_meta* meta, const asd_field_cfg* cfg, 
                       dw2_density && workspace && n > 0,
                   "null argument");
     if (!asd_field_supported(meta, cfg, "analytic field")) return ASD_ERR_UNSUPPORTED;
+    if (meta->n_masked_levels != 0) {
+        asd_set_error("analytic field kernels take no level limit (n_masked_levels = %u): the position gradient of a progressive grid is not "
+                      "implemented, use finite-difference normals", meta->n_masked_levels);
+        return ASD_ERR_UNSUPPORTED;
+    }
     ASD_CHECK_ARG(cfg->n_feature_dims == 3 || !d_features, "d_features given but no feature network");
     ASD_CHECK_ARG(cfg->n_feature_dims == 0 || (dw1_feature && dw2_feature && w1_feature && w2_feature), "feature gradients missing");
     hipStream_t s = (hipStream_t)stream;

@@ -45,6 +45,7 @@ __global__ __launch_bounds__(256) void pg_fill_kernel(const asd_grid_meta m, con
                                                       uint4* __restrict__ items, float* __restrict__ d_grid) {
     __shared__ uint32_t hist[ASD_PG_MAX_BINS];
     const int nn = n_dev ? min(*n_dev, n) : n;
+    const int act = asd_active_levels(m);       // level limit: no items for the masked levels
     const int64_t rr = row0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool live = pg_row_live(rr, rows, n, nn);
     if (__syncthreads_count(live) == 0) return;
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(256) void pg_fill_kernel(const asd_grid_meta m, con
         asd_row_load(g + rr * (2 * NFP), gv);
 #pragma unroll
         for (int f = 0; f < NF; ++f) {
-            if (gv[2 * f] == 0.f && gv[2 * f + 1] == 0.f) continue;
+            if (plan.first_level + f >= act || (gv[2 * f] == 0.f && gv[2 * f + 1] == 0.f)) continue;
             const pg_level r = pg_locate(m, plan.first_level + f, x, y, z);
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
@@ -82,8 +83,8 @@ __global__ __launch_bounds__(256) void pg_fill_kernel(const asd_grid_meta m, con
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
         const float g0 = gv[2 * f], g1 = gv[2 * f + 1];
-        if (g0 == 0.f && g1 == 0.f) continue;
         const int l = plan.first_level + f;
+        if (l >= act || (g0 == 0.f && g1 == 0.f)) continue;
         const pg_level r = pg_locate(m, l, x, y, z);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {

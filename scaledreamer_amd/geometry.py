@@ -235,6 +235,9 @@ class ImplicitVolume(BaseImplicitGeometry):
             self.normal_network = get_mlp(self.encoding.n_output_dims, 3, self.cfg.mlp_network_config)
         self._meta = self.encoding.encoding.encoding.meta
         self._fcfg = self._make_field_cfg()
+        if self.cfg.normal_type == "analytic" and self.cfg.pos_encoding_config.get("otype", "HashGrid") == "ProgressiveBandHashGrid":
+            raise NotImplementedError('normal_type "analytic" with a ProgressiveBandHashGrid: the analytic field kernels take no level limit '
+                                      "(asd_field_analytic_fwd returns ASD_ERR_UNSUPPORTED for a masked grid); use finite-difference normals")
         if self.cfg.normal_type == "analytic" and self._fcfg is None:
             raise NotImplementedError('normal_type "analytic" exists on the fused field kernels only (the composed route\'s encoding has no '
                                       "derivative with respect to the position); this configuration is kept off them by: "

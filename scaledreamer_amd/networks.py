@@ -16,6 +16,7 @@ import torch.nn.functional as F
 from . import _lib, ops
 from .base import Updateable
 from .config import config_to_primitive
+from .registry import debug
 
 
 def get_activation(name):
@@ -134,6 +135,49 @@ class TCNNEncoding(nn.Module):
         return self.encoding(x)
 
 
+class ProgressiveBandHashGrid(nn.Module, Updateable):
+    """networks.py:129-167: a hash grid whose coarsest `start_level` levels are on from `start_step`, one more every `update_steps`
+    steps (the Neuralangelo schedule).  `.encoding` is an `Encoding` built with otype Grid / Hash, so the state-dict key stays
+    `encoding.encoding.encoding.params` and a reference checkpoint loads.
+
+    The reference multiplies a full encode by a 0/1 mask.  Here there is no mask tensor and no multiply: `update_step` writes the number
+    of masked levels into the grid meta IN PLACE (`asd_grid_meta.n_masked_levels`; the geometries and the fused render pass hold the
+    same ctypes object), and the kernels skip the masked levels' gathers and scatters and write exact zeros.  The meta only changes
+    between steps, never between a forward and its backward.
+
+    Two quirks of the reference are kept: before the first `update_step` its mask is all zero, so EVERY level is masked (although
+    `current_level` already reads `start_level`); and its mask only ever grows (`mask[:current * F] = 1.0` never clears), so a step
+    counter that goes backwards lowers `current_level` but switches no level off again."""
+
+    def __init__(self, in_channels, config, dtype=torch.float32):
+        super().__init__()
+        self.n_input_dims = in_channels
+        encoding_config = dict(config)
+        encoding_config["otype"], encoding_config["type"] = "Grid", "Hash"
+        self.encoding = Encoding(in_channels, encoding_config, dtype=dtype)
+        self.n_output_dims = self.encoding.n_output_dims
+        self.n_level = int(config["n_levels"])
+        self.n_features_per_level = int(config["n_features_per_level"])
+        self.start_level, self.start_step, self.update_steps = config["start_level"], config["start_step"], config["update_steps"]
+        self.current_level = self.start_level
+        self.encoding.meta.n_masked_levels = self.n_level
+
+    @property
+    def n_active_levels(self) -> int:
+        """levels the kernels gather and scatter (the ones of the reference's mask)"""
+        return int(self.encoding.meta.n_levels - self.encoding.meta.n_masked_levels)
+
+    def forward(self, x):
+        return self.encoding(x)
+
+    def update_step(self, epoch, global_step, on_load_weights=False):
+        current_level = min(self.start_level + max(global_step - self.start_step, 0) // self.update_steps, self.n_level)
+        if current_level > self.current_level:
+            debug(f"Update current level to {current_level}")
+        self.current_level = current_level
+        self.encoding.meta.n_masked_levels = self.n_level - max(self.n_active_levels, min(max(int(current_level), 0), self.n_level))
+
+
 class CompositeEncoding(nn.Module, Updateable):
     def __init__(self, encoding, include_xyz=False, xyz_scale=2.0, xyz_offset=-1.0):
         super().__init__()
@@ -149,9 +193,12 @@ class CompositeEncoding(nn.Module, Updateable):
 
 def get_encoding(n_input_dims: int, config) -> nn.Module:
     otype = config.get("otype", "HashGrid")
-    if otype in ("ProgressiveBandFrequency", "ProgressiveBandHashGrid", "HashGridSpatialTime"):
+    if otype in ("ProgressiveBandFrequency", "HashGridSpatialTime"):
         raise NotImplementedError(f"{otype} is not used by any shipped ScaleDreamer config (out of scope)")
-    enc = TCNNEncoding(n_input_dims, config_to_primitive(config))
+    if otype == "ProgressiveBandHashGrid":
+        enc = ProgressiveBandHashGrid(n_input_dims, config_to_primitive(config))
+    else:
+        enc = TCNNEncoding(n_input_dims, config_to_primitive(config))
     return CompositeEncoding(enc, include_xyz=config.get("include_xyz", False), xyz_scale=2.0, xyz_offset=-1.0)
 
 
@@ -189,5 +236,5 @@ def tcnn_grid_param_count(config: dict) -> int:
     return int(m.n_params)
 
 
-__all__ = ["Encoding", "TCNNEncoding", "CompositeEncoding", "get_encoding", "VanillaMLP", "get_mlp", "get_activation",
+__all__ = ["Encoding", "TCNNEncoding", "ProgressiveBandHashGrid", "CompositeEncoding", "get_encoding", "VanillaMLP", "get_mlp", "get_activation",
            "tcnn_grid_param_count", "math"]

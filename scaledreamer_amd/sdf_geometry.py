@@ -5,8 +5,12 @@ reference checkpoint loads).  Two routes, as `implicit-volume` (geometry.py):
   fused      asd_field_fwd / asd_field_bwd / asd_field_density in ASD_FIELD_SDF mode (hash grid -> two 32 -> 64 -> 1 | 3 heads -> const or
              sphere bias -> forward-difference sdf_grad and normal in one kernel each way) — the same entries the hypernetwork geometry calls
   composed   tensor ops over the HIP hash-grid encoding: ellipsoid bias, finite_difference_laplacian, pred, a deformation network
-Not carried, each raising NotImplementedError with its reason: finite_difference_normal_eps "progressive" (no ProgressiveBandHashGrid),
-shape_init "mesh:..." (needs trimesh and pysdf), normal_type "analytic" (the derivative of the hash grid w.r.t. the position exists for
+Coarse-to-fine (Neuralangelo, implicit_sdf.py:380-413): with pos_encoding_config.otype "ProgressiveBandHashGrid" the encoding switches its
+levels on by schedule (networks.ProgressiveBandHashGrid writes the level limit into the grid meta both routes read, the kernels skip the
+masked levels), and finite_difference_normal_eps "progressive" shrinks the finite-difference step with the finest active level: update_step
+writes it into the field cfg, so the route stays fused.
+Not carried, each raising NotImplementedError with its reason: finite_difference_normal_eps "progressive" on any other encoding (the
+reference asserts ProgressiveBandHashGrid there), shape_init "mesh:..." (needs trimesh and pysdf), normal_type "analytic" (the derivative of the hash grid w.r.t. the position exists for
 `implicit-volume` only: asd_field_analytic_fwd / _bwd take ASD_FIELD_SDF cfgs, but this geometry is not wired to them).
 """
 from __future__ import annotations
@@ -59,8 +63,9 @@ class ImplicitSDF(BaseImplicitGeometry):
     def configure(self) -> None:
         super().configure()
         c = self.cfg
-        if c.finite_difference_normal_eps == "progressive":
-            raise NotImplementedError('finite_difference_normal_eps "progressive" needs ProgressiveBandHashGrid, which this port does not have')
+        if c.finite_difference_normal_eps == "progressive" and c.pos_encoding_config.get("otype", "HashGrid") != "ProgressiveBandHashGrid":
+            raise NotImplementedError('finite_difference_normal_eps "progressive" only works with pos_encoding_config.otype '
+                                      '"ProgressiveBandHashGrid" (the reference asserts it)')
         if isinstance(c.shape_init, str) and c.shape_init.startswith("mesh:"):
             raise NotImplementedError('shape_init "mesh:..." needs trimesh and pysdf, which this port does not use')
         if c.normal_type == "analytic":
@@ -93,7 +98,8 @@ class ImplicitSDF(BaseImplicitGeometry):
             self._meta.n_levels == 16 and self.encoding.n_output_dims == 32 and not self.encoding.include_xyz
             and isinstance(self.sdf_network, VanillaMLP) and mlp.get("n_neurons") == 64 and mlp.get("n_hidden_layers") == 1
             and mlp.get("output_activation", "none") in (None, "none") and c.n_feature_dims in (0, 3)
-            and c.normal_type in (None, "finite_difference") and c.n_input_dims == 3 and isinstance(c.finite_difference_normal_eps, float)
+            and c.normal_type in (None, "finite_difference") and c.n_input_dims == 3
+            and (isinstance(c.finite_difference_normal_eps, float) or c.finite_difference_normal_eps == "progressive")
         )
         if not ok:
             return None
@@ -102,7 +108,10 @@ class ImplicitSDF(BaseImplicitGeometry):
             f.bbox_min[d], f.bbox_max[d] = -c.radius, c.radius
         f.radius, f.bias_mode, f.bias_value = c.radius, bias, value
         f.blob_scale, f.blob_std, f.activation = 0.0, 1.0, _lib.ASD_ACT_NONE
-        f.fd_eps, f.n_hidden, f.n_feature_dims, f.field_mode = float(c.finite_difference_normal_eps), 64, c.n_feature_dims, _lib.ASD_FIELD_SDF
+        # "progressive": update_step writes the step of the finest active level before anything asks for a normal (0.01, the config's
+        # default, stands in until then)
+        eps = float(c.finite_difference_normal_eps) if isinstance(c.finite_difference_normal_eps, float) else 0.01
+        f.fd_eps, f.n_hidden, f.n_feature_dims, f.field_mode = eps, 64, c.n_feature_dims, _lib.ASD_FIELD_SDF
         return f
 
     @property
@@ -279,5 +288,15 @@ class ImplicitSDF(BaseImplicitGeometry):
                 if self.finite_difference_normal_eps != self.cfg.finite_difference_normal_eps:
                     info(f"finite_difference_normal_eps = {self.cfg.finite_difference_normal_eps}")
                 self.finite_difference_normal_eps = self.cfg.finite_difference_normal_eps
+            elif self.cfg.finite_difference_normal_eps == "progressive":
+                # progressive finite-difference eps from Neuralangelo (https://arxiv.org/abs/2306.03092): the cell of the finest active level
+                hg = self.cfg.pos_encoding_config
+                current_level = min(hg["start_level"] + max(global_step - hg["start_step"], 0) // hg["update_steps"], hg["n_levels"])
+                grid_size = 2 * self.cfg.radius / (hg["base_resolution"] * hg["per_level_scale"] ** (current_level - 1))
+                if grid_size != self.finite_difference_normal_eps:
+                    info(f"Update finite_difference_normal_eps to {grid_size}")
+                self.finite_difference_normal_eps = grid_size
+                if self._fcfg is not None:
+                    self._fcfg.fd_eps = grid_size
             else:
                 raise ValueError(f"Unknown finite_difference_normal_eps={self.cfg.finite_difference_normal_eps}")
