@@ -8,7 +8,8 @@ the one those kernels are built for, otherwise in the composed path (HIP hash gr
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Any, Dict, Optional, Union
+from functools import partial
+from typing import Any, Dict, Optional, Tuple, Union
 
 import torch
 import torch.nn.functional as F
@@ -142,18 +143,64 @@ class BaseImplicitGeometry(BaseModule):
             return self._isosurface(self.bbox)
 
 
+def make_field_cfg(radius: float, bias_mode: int, bias_value: float, fd_eps: float, n_feature_dims: int, field_mode: int,
+                   activation: int = _lib.ASD_ACT_NONE, blob_scale: float = 0.0, blob_std: float = 1.0) -> _lib.FieldCfg:
+    """The ONE place an asd_field_cfg is filled, for every geometry on the field kernels (a field added to the struct is set here or is
+    zero everywhere).  activation / blob_scale / blob_std are the density case's; an SDF cfg leaves them at their neutral values."""
+    f = _lib.FieldCfg()
+    for d in range(3):
+        f.bbox_min[d], f.bbox_max[d] = -radius, radius
+    f.radius, f.bias_mode, f.bias_value = radius, bias_mode, bias_value
+    f.blob_scale, f.blob_std, f.activation = blob_scale, blob_std, activation
+    f.fd_eps, f.n_hidden, f.n_feature_dims, f.field_mode = fd_eps, 64, n_feature_dims, field_mode
+    return f
+
+
+def sdf_bias_mode(cfg) -> Optional[Tuple[int, float]]:
+    """(bias mode, bias value) of sdf_bias / sdf_bias_params as the field kernels apply it; None for a bias they do not (ellipsoid)"""
+    if cfg.sdf_bias == "sphere" and isinstance(cfg.sdf_bias_params, float):
+        return _lib.ASD_BIAS_SPHERE, float(cfg.sdf_bias_params)
+    if isinstance(cfg.sdf_bias, float):
+        return _lib.ASD_BIAS_CONST, float(cfg.sdf_bias)
+    return None
+
+
+def shifted_sdf(cfg, points, sdf):
+    """get_shifted_sdf of the four SDF geometries (implicit_sdf.py:224, and its copies hyper_iNGP.py:206, stylegan_3dconv_net.py:201,
+    triplane_transformer.py:104); the ellipsoid parameters may be any sequence of three"""
+    if cfg.sdf_bias == "ellipsoid":
+        assert hasattr(cfg.sdf_bias_params, "__len__") and len(cfg.sdf_bias_params) == 3
+        size = torch.as_tensor(list(cfg.sdf_bias_params)).to(points)
+        bias = ((points / size) ** 2).sum(dim=-1, keepdim=True).sqrt() - 1.0
+    elif cfg.sdf_bias == "sphere":
+        assert isinstance(cfg.sdf_bias_params, float)
+        bias = (points ** 2).sum(dim=-1, keepdim=True).sqrt() - cfg.sdf_bias_params
+    elif isinstance(cfg.sdf_bias, float):
+        bias = cfg.sdf_bias
+    else:
+        raise ValueError(f"Unknown sdf bias {cfg.sdf_bias}")
+    return sdf + bias
+
+
+def _contiguous(t):
+    return None if t is None else t.contiguous()
+
+
 class _FieldFn(torch.autograd.Function):
-    """sigma, features, normal = field(points); backward scatters into the table and reduces MLP grads."""
+    """sigma, features, normal = field(points) around the ops pair it is handed: (ops.field_fwd, ops.field_bwd) with their want_normal /
+    n_dev bound — backward scatters into the table and reduces MLP grads — or (ops.field_analytic_fwd, ops.field_analytic_bwd), where
+    normal = -grad sigma / |grad sigma| from the field's own position derivative (normal_type "analytic") and backward is the double
+    backward of the reference's autograd.grad(..., create_graph=True)."""
 
     @staticmethod
-    def forward(ctx, points, grid, w1d, w2d, w1f, w2f, geom, want_normal, n_dev=None):
-        sigma, feats, normal, enc = ops.field_fwd(geom._meta, geom._fcfg, grid, w1d, w2d, w1f, w2f, points, want_normal, n_dev=n_dev)
+    def forward(ctx, points, grid, w1d, w2d, w1f, w2f, geom, fwd, bwd):
+        sigma, feats, normal, enc = fwd(geom._meta, geom._fcfg, grid, w1d, w2d, w1f, w2f, points)
         ctx.save_for_backward(points, grid, w1d, w2d, w1f, w2f, enc, sigma)
-        ctx.geom, ctx.n_dev = geom, n_dev
+        ctx.geom, ctx.bwd = geom, bwd
         ctx.set_materialize_grads(False)
         if normal is None:
             normal = sigma.new_zeros(0)
-        ctx.mark_non_differentiable(*([normal] if not want_normal else []))
+            ctx.mark_non_differentiable(normal)
         return sigma, feats, normal
 
     @staticmethod
@@ -163,37 +210,38 @@ class _FieldFn(torch.autograd.Function):
         d_grid = torch.zeros_like(grid)
         if d_sigma is None and d_feats is None and d_normal is None:
             return None, d_grid, torch.zeros_like(w1d), torch.zeros_like(w2d), torch.zeros_like(w1f), torch.zeros_like(w2f), None, None, None
-        dw = ops.field_bwd(g._meta, g._fcfg, grid, w1d, w2d, w1f, w2f, points, enc, sigma,
-                           None if d_sigma is None else d_sigma.contiguous(),
-                           None if d_feats is None else d_feats.contiguous(),
-                           None if d_normal is None else d_normal.contiguous(), d_grid, n_dev=ctx.n_dev)
+        dw = ctx.bwd(g._meta, g._fcfg, grid, w1d, w2d, w1f, w2f, points, enc, sigma, _contiguous(d_sigma), _contiguous(d_feats),
+                     _contiguous(d_normal), d_grid)
         return None, d_grid, dw[0], dw[1], dw[2], dw[3], None, None, None
 
 
-class _AnalyticFieldFn(torch.autograd.Function):
-    """sigma, features, normal = field(points) with normal = -grad sigma / |grad sigma| from the field's own position derivative
-    (normal_type "analytic"); backward is the double backward of the reference's autograd.grad(..., create_graph=True)."""
+class _SdfFieldFn(torch.autograd.Function):
+    """(sdf, features, normal, sdf_grad) of ONE field evaluation in ASD_FIELD_SDF mode (fused HIP kernels): `implicit-sdf` with its own heads,
+    `Hyper-iNGP` with one prompt's hypernetwork weights."""
 
     @staticmethod
-    def forward(ctx, points, grid, w1d, w2d, w1f, w2f, geom):
-        sigma, feats, normal, enc = ops.field_analytic_fwd(geom._meta, geom._fcfg, grid, w1d, w2d, w1f, w2f, points)
-        ctx.save_for_backward(points, grid, w1d, w2d, w1f, w2f, enc, sigma)
-        ctx.geom = geom
+    def forward(ctx, points, grid, w1d, w2d, w1f, w2f, meta, fcfg, want_normal):
+        if want_normal:
+            sdf, feats, normal, fdg, enc = ops.field_fwd(meta, fcfg, grid, w1d, w2d, w1f, w2f, points, True, want_fd_grad=True)
+        else:
+            sdf, feats, normal, enc = ops.field_fwd(meta, fcfg, grid, w1d, w2d, w1f, w2f, points, False)
+            normal, fdg = sdf.new_zeros(0), sdf.new_zeros(0)
+            ctx.mark_non_differentiable(normal, fdg)
+        ctx.save_for_backward(points, grid, w1d, w2d, w1f, w2f, enc, sdf)
+        ctx.meta, ctx.fcfg, ctx.want_normal = meta, fcfg, want_normal
         ctx.set_materialize_grads(False)
-        return sigma, feats, normal
+        return sdf, feats, normal, fdg
 
     @staticmethod
-    def backward(ctx, d_sigma, d_feats, d_normal):
-        points, grid, w1d, w2d, w1f, w2f, enc, sigma = ctx.saved_tensors
-        g = ctx.geom
+    def backward(ctx, d_sdf, d_feats, d_normal, d_fdg):
+        points, grid, w1d, w2d, w1f, w2f, enc, sdf = ctx.saved_tensors
         d_grid = torch.zeros_like(grid)
-        if d_sigma is None and d_feats is None and d_normal is None:
-            return None, d_grid, torch.zeros_like(w1d), torch.zeros_like(w2d), torch.zeros_like(w1f), torch.zeros_like(w2f), None
-        dw = ops.field_analytic_bwd(g._meta, g._fcfg, grid, w1d, w2d, w1f, w2f, points, enc, sigma,
-                                    None if d_sigma is None else d_sigma.contiguous(),
-                                    None if d_feats is None else d_feats.contiguous(),
-                                    None if d_normal is None else d_normal.contiguous(), d_grid)
-        return None, d_grid, dw[0], dw[1], dw[2], dw[3], None
+        if d_sdf is None and d_feats is None and d_normal is None and d_fdg is None:
+            return (None, d_grid, *(torch.zeros_like(w) for w in (w1d, w2d, w1f, w2f)), None, None, None)
+        c = _contiguous
+        dw = ops.field_bwd(ctx.meta, ctx.fcfg, grid, w1d, w2d, w1f, w2f, points, enc, sdf, c(d_sdf), c(d_feats),
+                           c(d_normal) if ctx.want_normal else None, d_grid, d_fd_grad=c(d_fdg) if ctx.want_normal else None)
+        return None, d_grid, dw[0], dw[1], dw[2], dw[3], None, None, None
 
 
 @register("implicit-volume")
@@ -271,13 +319,8 @@ class ImplicitVolume(BaseImplicitGeometry):
         self._fused_blockers = blockers
         if blockers:
             return None
-        f = _lib.FieldCfg()
-        for d in range(3):
-            f.bbox_min[d], f.bbox_max[d] = -c.radius, c.radius
-        f.radius, f.bias_mode, f.bias_value = c.radius, bias, bias_value
-        f.blob_scale, f.blob_std, f.activation = c.density_blob_scale, c.density_blob_std, act
-        f.fd_eps, f.n_hidden, f.n_feature_dims = c.finite_difference_normal_eps, 64, c.n_feature_dims
-        return f
+        return make_field_cfg(c.radius, bias, bias_value, c.finite_difference_normal_eps, c.n_feature_dims, _lib.ASD_FIELD_DENSITY,
+                              activation=act, blob_scale=c.density_blob_scale, blob_std=c.density_blob_std)
 
     @property
     def fused(self) -> bool:
@@ -323,12 +366,13 @@ class ImplicitVolume(BaseImplicitGeometry):
             if n_dev is not None:
                 raise ValueError('normal_type "analytic" takes no n_dev: the renderer path with a device-side sample count never asks for normals')
             if torch.is_grad_enabled() and grid.requires_grad:
-                sigma, feats, normal = _AnalyticFieldFn.apply(flat, grid, w1d, w2d, w1f, w2f, self)
+                sigma, feats, normal = _FieldFn.apply(flat, grid, w1d, w2d, w1f, w2f, self, ops.field_analytic_fwd, ops.field_analytic_bwd)
             else:       # detached, as the reference detaches the normal when grad was disabled (implicit_volume.py:189-190)
                 sigma, feats, normal, _ = ops.field_analytic_fwd(self._meta, self._fcfg, grid.detach(), w1d.detach(), w2d.detach(),
                                                                  w1f.detach(), w2f.detach(), flat)
         elif torch.is_grad_enabled() and grid.requires_grad:
-            sigma, feats, normal = _FieldFn.apply(flat, grid, w1d, w2d, w1f, w2f, self, bool(output_normal), n_dev)
+            fwd, bwd = partial(ops.field_fwd, want_normal=bool(output_normal), n_dev=n_dev), partial(ops.field_bwd, n_dev=n_dev)
+            sigma, feats, normal = _FieldFn.apply(flat, grid, w1d, w2d, w1f, w2f, self, fwd, bwd)
         else:
             sigma, feats, normal, _ = ops.field_fwd(self._meta, self._fcfg, grid.detach(), w1d.detach(), w2d.detach(),
                                                     w1f.detach(), w2f.detach(), flat, bool(output_normal), n_dev=n_dev)

@@ -21,7 +21,7 @@ import torch.nn.functional as F
 
 from . import _lib, ops
 from .background import BaseBackground
-from .geometry import BaseImplicitGeometry, contract_to_unisphere
+from .geometry import BaseImplicitGeometry, _SdfFieldFn, make_field_cfg, sdf_bias_mode, shifted_sdf
 from .networks import get_activation, get_encoding
 from .registry import register
 
@@ -82,34 +82,6 @@ def hypernet_forward(enc: torch.Tensor, params, activation=torch.relu, output_ac
     return enc
 
 
-class _SdfFieldFn(torch.autograd.Function):
-    """(sdf, features, normal, sdf_grad) of ONE prompt from its points and hypernetwork weights (fused HIP kernels)."""
-
-    @staticmethod
-    def forward(ctx, points, grid, w1d, w2d, w1f, w2f, meta, fcfg, want_normal):
-        if want_normal:
-            sdf, feats, normal, fdg, enc = ops.field_fwd(meta, fcfg, grid, w1d, w2d, w1f, w2f, points, True, want_fd_grad=True)
-        else:
-            sdf, feats, normal, enc = ops.field_fwd(meta, fcfg, grid, w1d, w2d, w1f, w2f, points, False)
-            normal, fdg = sdf.new_zeros(0), sdf.new_zeros(0)
-            ctx.mark_non_differentiable(normal, fdg)
-        ctx.save_for_backward(points, grid, w1d, w2d, w1f, w2f, enc, sdf)
-        ctx.meta, ctx.fcfg, ctx.want_normal = meta, fcfg, want_normal
-        ctx.set_materialize_grads(False)
-        return sdf, feats, normal, fdg
-
-    @staticmethod
-    def backward(ctx, d_sdf, d_feats, d_normal, d_fdg):
-        points, grid, w1d, w2d, w1f, w2f, enc, sdf = ctx.saved_tensors
-        d_grid = torch.zeros_like(grid)
-        if d_sdf is None and d_feats is None and d_normal is None and d_fdg is None:
-            return (None, d_grid, *(torch.zeros_like(w) for w in (w1d, w2d, w1f, w2f)), None, None, None)
-        c = lambda t: None if t is None else t.contiguous()
-        dw = ops.field_bwd(ctx.meta, ctx.fcfg, grid, w1d, w2d, w1f, w2f, points, enc, sdf, c(d_sdf), c(d_feats),
-                           c(d_normal) if ctx.want_normal else None, d_grid, d_fd_grad=c(d_fdg) if ctx.want_normal else None)
-        return None, d_grid, dw[0], dw[1], dw[2], dw[3], None, None, None
-
-
 @register("Hyper-iNGP")
 class Hypernet_Sdf(BaseImplicitGeometry):
     @dataclass
@@ -159,24 +131,15 @@ class Hypernet_Sdf(BaseImplicitGeometry):
     def _field_cfg(self) -> Optional[_lib.FieldCfg]:
         c = self.cfg
         od = self.hypernet.out_dims
-        if c.sdf_bias == "sphere" and isinstance(c.sdf_bias_params, float):
-            bias, value = _lib.ASD_BIAS_SPHERE, float(c.sdf_bias_params)
-        elif isinstance(c.sdf_bias, float):
-            bias, value = _lib.ASD_BIAS_CONST, float(c.sdf_bias)
-        else:
+        bias = sdf_bias_mode(c)
+        if bias is None:
             return None
         ok = (self._meta.n_levels == 16 and self.encoding.n_output_dims == 32 and not self.encoding.include_xyz
               and od.get("sdf_weights") == [32, 64, 1] and od.get("feature_weights") == [32, 64, 3] and c.n_feature_dims == 3
               and c.normal_type == "finite_difference" and self.finite_difference_normal_eps is not None and c.n_input_dims == 3)
         if not ok:
             return None
-        f = _lib.FieldCfg()
-        for d in range(3):
-            f.bbox_min[d], f.bbox_max[d] = -c.radius, c.radius
-        f.radius, f.bias_mode, f.bias_value = c.radius, bias, value
-        f.blob_scale, f.blob_std, f.activation = 0.0, 1.0, _lib.ASD_ACT_NONE
-        f.fd_eps, f.n_hidden, f.n_feature_dims, f.field_mode = float(self.finite_difference_normal_eps), 64, 3, _lib.ASD_FIELD_SDF
-        return f
+        return make_field_cfg(c.radius, *bias, float(self.finite_difference_normal_eps), 3, _lib.ASD_FIELD_SDF)
 
     def update_step(self, epoch: int, global_step: int, on_load_weights: bool = False):
         if self.cfg.normal_type == "finite_difference":
@@ -188,19 +151,7 @@ class Hypernet_Sdf(BaseImplicitGeometry):
 
     # ---- reference surface ---------------------------------------------------------------------------------------------
     def get_shifted_sdf(self, points, sdf):
-        c = self.cfg
-        if c.sdf_bias == "ellipsoid":
-            assert len(c.sdf_bias_params) == 3
-            size = torch.as_tensor(c.sdf_bias_params).to(points)
-            bias = ((points / size) ** 2).sum(dim=-1, keepdim=True).sqrt() - 1.0
-        elif c.sdf_bias == "sphere":
-            assert isinstance(c.sdf_bias_params, float)
-            bias = (points ** 2).sum(dim=-1, keepdim=True).sqrt() - c.sdf_bias_params
-        elif isinstance(c.sdf_bias, float):
-            bias = c.sdf_bias
-        else:
-            raise ValueError(f"Unknown sdf bias {c.sdf_bias}")
-        return sdf + bias
+        return shifted_sdf(self.cfg, points, sdf)
 
     def generate_space_cache(self, styles, text_embed: Optional[torch.Tensor] = None) -> Any:
         return self.hypernet(text_embed)  # the noise `styles` is not used by the hypernetwork

@@ -5,15 +5,16 @@
                              transformer, 3 bilinear lookups concatenated)
 Both: contract to [-1,1] -> sample features -> VanillaMLP sdf / feature heads -> sdf + sphere bias -> finite-difference
 sdf_grad / normal from 3 offset lookups.  Shipped configurations run lookup + heads + bias + finite differences as ONE fused HIP kernel each
-way (asd_voxfield_* / asd_trifield_*, `_VoxFieldFn` / `_TriFieldFn` below); the composed form (HIP samplers of samplers.py + torch MLP heads) is
-the fallback for head shapes the fused kernels are not instantiated for and the A/B partner (ASD_VOXFIELD=0 / ASD_TRIFIELD=0).  The generators
-live in generators.py (Generator3D on csrc/conv3d.hip, TriplaneTransformer on csrc/transformer.hip).
+way (asd_voxfield_* / asd_trifield_*: `_SampledFieldFn` below around the `_VOXFIELD` / `_TRIFIELD` adapter, driven per batch entry by
+`_SampledSdfGeometry._field_entries`); the composed form (HIP samplers of samplers.py + torch MLP heads) is the fallback for head shapes
+the fused kernels are not instantiated for and the A/B partner (ASD_VOXFIELD=0 / ASD_TRIFIELD=0).  The generators live in generators.py
+(Generator3D on csrc/conv3d.hip, TriplaneTransformer on csrc/transformer.hip).
 """
 from __future__ import annotations
 
 import os
 from dataclasses import dataclass, field
-from typing import Any, Dict, Optional, Union
+from typing import Any, Callable, Dict, NamedTuple, Optional, Union
 
 import torch
 import torch.nn.functional as F
@@ -21,7 +22,7 @@ import torch.nn.functional as F
 from . import _lib, ops
 from .config import C
 from .generators import Generator3D, TriplaneTransformer
-from .geometry import BaseImplicitGeometry
+from .geometry import BaseImplicitGeometry, make_field_cfg, sdf_bias_mode, shifted_sdf
 from .networks import get_activation, get_mlp
 from .registry import register
 from .samplers import channels_last, contract_to_unisphere_custom, get_trilinear_feature, planes_channels_last, sample_from_planes
@@ -49,19 +50,7 @@ class _SampledSdfGeometry(BaseImplicitGeometry):
         raise NotImplementedError
 
     def get_shifted_sdf(self, points, sdf):
-        c = self.cfg
-        if c.sdf_bias == "ellipsoid":
-            assert len(c.sdf_bias_params) == 3
-            size = torch.as_tensor(c.sdf_bias_params).to(points)
-            bias = ((points / size) ** 2).sum(dim=-1, keepdim=True).sqrt() - 1.0
-        elif c.sdf_bias == "sphere":
-            assert isinstance(c.sdf_bias_params, float)
-            bias = (points ** 2).sum(dim=-1, keepdim=True).sqrt() - c.sdf_bias_params
-        elif isinstance(c.sdf_bias, float):
-            bias = c.sdf_bias
-        else:
-            raise ValueError(f"Unknown sdf bias {c.sdf_bias}")
-        return sdf + bias
+        return shifted_sdf(self.cfg, points, sdf)
 
     # COMPOSED path only (the fused kernels keep nothing per evaluation but the points, so they never chunk): above this many points per
     # call the torch MLP heads run chunk by chunk under activation checkpointing — they keep ~1.2 KB of autograd state per point and SDF
@@ -70,8 +59,38 @@ class _SampledSdfGeometry(BaseImplicitGeometry):
     CHECKPOINT_ABOVE = 8 * 1024 * 1024
     CHECKPOINT_CHUNK = 2 * 1024 * 1024
 
+    # ---- fused path: a subclass names its predicate, its adapter (_field), its relayout (_channels_last) and its switch (_use_fused) -----
+    def _fused_eligible(self) -> bool:
+        raise NotImplementedError
+
+    def _field_cfg(self) -> Optional[_lib.FieldCfg]:
+        bias = sdf_bias_mode(self.cfg)
+        if bias is None or not self._fused_eligible():
+            return None
+        return make_field_cfg(self.cfg.radius, *bias, float(self.finite_difference_normal_eps), 3, _lib.ASD_FIELD_SDF)
+
     def _use_fused(self, points) -> bool:
         return False
+
+    def _field_entries(self, points: torch.Tensor, space_cache: Any, want_normal: bool, want_features: bool):
+        """The fused field of points [B, n, 3], entry by entry -> (sdf [B, n], features, normal, sdf_grad [B, n, 3]), None for what was not
+        asked for.  Through the autograd node when a gradient is wanted (it always computes the features), the bare forward entry under
+        no_grad otherwise, with the weights prepared once per call."""
+        cache_cl, w = self._channels_last(space_cache), self._heads_weights()
+        need_grad = torch.is_grad_enabled() and (cache_cl.requires_grad or w[0].requires_grad)
+        if not need_grad:
+            with torch.no_grad():
+                w = self._field.prepare(w)
+        outs = []
+        for b in range(points.shape[0]):
+            pts = points[b].contiguous().float()
+            if need_grad:
+                outs.append(_SampledFieldFn.apply(pts, *self._gate(space_cache, cache_cl, b), self._field, self._fcfg, want_normal, *w))
+            else:
+                with torch.no_grad():
+                    outs.append(self._field.fwd(cache_cl[b], self._fcfg, w, pts, want_normal, want_features, False))
+        wanted = (True, want_features, want_normal, want_normal)
+        return tuple(torch.stack([o[i] for o in outs], 0) if use else None for i, use in enumerate(wanted))
 
     def forward(self, points: torch.Tensor, space_cache: Any, output_normal: bool = False) -> Dict[str, torch.Tensor]:
         batch_size, n_points, _ = points.shape
@@ -89,6 +108,12 @@ class _SampledSdfGeometry(BaseImplicitGeometry):
         them batch-major (triplane_transformer.py:153-200, stylegan_3dconv_net.py forward).  With a normal the centre and its three
         +eps probes go through the feature sampler and the SDF head as ONE stencil of 4 points per sample — one sampler launch and one
         head pass over 4 N points instead of one over N plus one over 3 N; per point the arithmetic is that of forward_sdf."""
+        if self._use_fused(points):
+            sdf, feats, normal, sdf_grad = self._field_entries(points, space_cache, bool(output_normal), True)
+            out = {"sdf": sdf[..., None], "features": feats}
+            if output_normal:
+                out.update(normal=normal, shading_normal=normal, sdf_grad=sdf_grad)
+            return out
         if output_normal and self.cfg.normal_type != "finite_difference":
             raise NotImplementedError(f"normal_type {self.cfg.normal_type!r}: only the finite-difference normal of the shipped configs is implemented")
         batch, n = points.shape[:2]
@@ -125,6 +150,8 @@ class _SampledSdfGeometry(BaseImplicitGeometry):
 
     def forward_sdf(self, points: torch.Tensor, space_cache: Any) -> torch.Tensor:
         batch_size = points.shape[0]
+        if self._use_fused(points):
+            return self._field_entries(points.reshape(batch_size, -1, 3), space_cache, False, False)[0].reshape(*points.shape[:-1], 1)
         pts = contract_to_unisphere_custom(points, self.bbox, self.unbounded)
         enc = self.interpolate_encodings(pts.reshape(batch_size, -1, 3), space_cache).reshape(*pts.shape[:-1], -1)
         return self.get_shifted_sdf(points, self.sdf_network(enc).reshape(*pts.shape[:-1], 1))
@@ -151,6 +178,7 @@ class _SampledSdfGeometry(BaseImplicitGeometry):
             raise NotImplementedError(f"normal_type == {self.cfg.normal_type} is not implemented yet.")
         if isinstance(self.cfg.finite_difference_normal_eps, float):
             self.finite_difference_normal_eps = self.cfg.finite_difference_normal_eps
+        self._fcfg = self._field_cfg()
 
 
 class _GradSlot:
@@ -208,32 +236,69 @@ def _gate_of(owner: torch.Tensor, cache_cl: torch.Tensor):
     return st[0], st[1]
 
 
-class _VoxFieldFn(torch.autograd.Function):
-    """(sdf, features, normal, sdf_grad) of ONE batch entry from its points, its channel-last feature volume and the two MLP heads: trilinear
-    lookup, heads, bias and finite differences in one kernel each way (include/asd_hip.h: asd_voxfield_fwd / _bwd)"""
+class _FieldKind(NamedTuple):
+    """What differs between the two fused sampled fields, and nothing else: how the heads' weights are handed to the kernels (prepare), and
+    the entry pair around them.  fwd -> (sdf, features, normal, fd_grad, kept), `kept` being what the backward entry wants back besides the
+    points and the sdf; bwd -> one gradient per head weight, in the parameter's own layout."""
+    prepare: Callable
+    fwd: Callable
+    bwd: Callable
+
+
+def _vox_fwd(vol_b, fcfg, w, points, want_normal, want_features, keep):
+    return ops.voxfield_fwd(vol_b, fcfg, *w, points, want_normal, want_features=want_features, save_enc=keep)
+
+
+def _vox_bwd(vol_b, fcfg, w, points, enc, sdf, d_sdf, d_feats, d_normal, d_fdg, d_vol_b):
+    return ops.voxfield_bwd(vol_b, fcfg, *w, points, enc, sdf, d_sdf, d_feats, d_normal, d_fdg, d_vol_b)
+
+
+def _tri_weights(w):
+    """(W1^T [96, 64], W2, W3) of the sdf head, then of the feature head, contiguous (ops.trifield_fwd)"""
+    return (w[0].t().contiguous(), w[1].contiguous(), w[2].contiguous(), w[3].t().contiguous(), w[4].contiguous(), w[5].contiguous())
+
+
+def _tri_fwd(planes_b, fcfg, w6, points, want_normal, want_features, keep):
+    return (*ops.trifield_fwd(planes_b, fcfg, w6, points, want_normal, want_features=want_features), None)
+
+
+def _tri_bwd(planes_b, fcfg, w6, points, kept, sdf, d_sdf, d_feats, d_normal, d_fdg, d_planes_b):
+    return ops.trifield_bwd(planes_b, fcfg, w6, points, sdf, d_sdf, d_feats, d_normal, d_fdg, d_planes_b)
+
+
+# asd_voxfield_*: the four weights as they are, and the sampled encoding [n, 32] is kept for the backward pass
+_VOXFIELD = _FieldKind(prepare=lambda w: w, fwd=_vox_fwd, bwd=_vox_bwd)
+# asd_trifield_*: nothing but the points and the sdf is kept; the first layers' gradients come back in the native [64, 96] layout
+_TRIFIELD = _FieldKind(prepare=_tri_weights, fwd=_tri_fwd, bwd=_tri_bwd)
+
+
+class _SampledFieldFn(torch.autograd.Function):
+    """(sdf, features, normal, sdf_grad) of ONE batch entry from its points, its channel-last cache entry and the two MLP heads: lookup,
+    heads, bias and finite differences in one kernel each way (include/asd_hip.h: asd_voxfield_fwd / _bwd, asd_trifield_fwd / _bwd)"""
 
     @staticmethod
-    def forward(ctx, points, vol_cl, b, slot, w1s, w2s, w1f, w2f, fcfg, want_normal):
-        """vol_cl: the WHOLE channel-last cache [B, D, H, W, C] (contiguous), b: the entry these points sample"""
-        sdf, feats, normal, fdg, enc = ops.voxfield_fwd(vol_cl[b], fcfg, w1s, w2s, w1f, w2f, points, want_normal)
+    def forward(ctx, points, cache_cl, b, slot, kind, fcfg, want_normal, *weights):
+        """cache_cl: the WHOLE channel-last cache [B, D, H, W, C] | [B, 3, H, W, C] (contiguous), b: the entry these points sample"""
+        w = kind.prepare(weights)
+        sdf, feats, normal, fdg, kept = kind.fwd(cache_cl[b], fcfg, w, points, want_normal, True, True)
         if not want_normal:
             normal, fdg = sdf.new_zeros(0), sdf.new_zeros(0)
             ctx.mark_non_differentiable(normal, fdg)
-        ctx.save_for_backward(points, vol_cl, w1s, w2s, w1f, w2f, enc, sdf)
-        ctx.fcfg, ctx.want_normal, ctx.slot, ctx.b = fcfg, want_normal, slot, b
+        ctx.save_for_backward(points, cache_cl, sdf, kept, *w)
+        ctx.kind, ctx.fcfg, ctx.want_normal, ctx.slot, ctx.b = kind, fcfg, want_normal, slot, b
         ctx.set_materialize_grads(False)
         return sdf, feats, normal, fdg
 
     @staticmethod
     def backward(ctx, d_sdf, d_feats, d_normal, d_fdg):
-        points, vol_cl, w1s, w2s, w1f, w2f, enc, sdf = ctx.saved_tensors
+        points, cache_cl, sdf, kept, *w = ctx.saved_tensors
         if d_sdf is None and d_feats is None and d_normal is None and d_fdg is None:
-            return (None,) * 10
-        d_vol, first = (ctx.slot or _GradSlot()).acquire(vol_cl)
+            return (None,) * (7 + len(w))
+        d_cache, first = (ctx.slot or _GradSlot()).acquire(cache_cl)
         c = lambda t: None if t is None else t.contiguous()
-        dw = ops.voxfield_bwd(vol_cl[ctx.b], ctx.fcfg, w1s, w2s, w1f, w2f, points, enc, sdf, c(d_sdf), c(d_feats),
-                              c(d_normal) if ctx.want_normal else None, c(d_fdg) if ctx.want_normal else None, d_vol[ctx.b])
-        return None, (d_vol if first else None), None, None, dw[0], dw[1], dw[2], dw[3], None, None
+        dws = ctx.kind.bwd(cache_cl[ctx.b], ctx.fcfg, w, points, kept, sdf, c(d_sdf), c(d_feats), c(d_normal) if ctx.want_normal else None,
+                           c(d_fdg) if ctx.want_normal else None, d_cache[ctx.b])
+        return (None, (d_cache if first else None), None, None, None, None, None, *dws)
 
 
 @register("3DConv-net")
@@ -290,31 +355,17 @@ class Voxel_3d_Sdf(_SampledSdfGeometry):
     def update_step(self, epoch: int, global_step: int, on_load_weights: bool = False):
         super().update_step(epoch, global_step, on_load_weights)
         self.truncation_psi = C(self.cfg.truncation_psi, epoch, global_step)
-        self._fcfg = self._field_cfg()
 
     # ---- fused path: lookup + heads + bias + finite differences as one kernel (the shipped configuration) -------------------------------
-    def _field_cfg(self) -> Optional[_lib.FieldCfg]:
-        c = self.cfg
-        if c.sdf_bias == "sphere" and isinstance(c.sdf_bias_params, float):
-            bias, value = _lib.ASD_BIAS_SPHERE, float(c.sdf_bias_params)
-        elif isinstance(c.sdf_bias, float):
-            bias, value = _lib.ASD_BIAS_CONST, float(c.sdf_bias)
-        else:
-            return None
-        m = c.mlp_network_config
-        ok = (c.space_generator_config["img_channels"] == 32 and c.n_feature_dims == 3 and m.get("otype") == "VanillaMLP"
-              and m.get("n_neurons") == 64 and m.get("n_hidden_layers") == 1 and m.get("activation") == "ReLU"
-              and m.get("output_activation", "none") in (None, "none") and c.normal_type == "finite_difference"
-              and self.finite_difference_normal_eps is not None and not self.unbounded and not c.isosurface_deformable_grid)
-        if not ok:
-            return None
-        f = _lib.FieldCfg()
-        for d in range(3):
-            f.bbox_min[d], f.bbox_max[d] = -c.radius, c.radius
-        f.radius, f.bias_mode, f.bias_value = c.radius, bias, value
-        f.blob_scale, f.blob_std, f.activation = 0.0, 1.0, _lib.ASD_ACT_NONE
-        f.fd_eps, f.n_hidden, f.n_feature_dims, f.field_mode = float(self.finite_difference_normal_eps), 64, 3, _lib.ASD_FIELD_SDF
-        return f
+    _field = _VOXFIELD
+    _channels_last = staticmethod(channels_last)                          # [B, D, H, W, 32] (the HIP generator's own layout: a view)
+
+    def _fused_eligible(self) -> bool:
+        c, m = self.cfg, self.cfg.mlp_network_config
+        return (c.space_generator_config["img_channels"] == 32 and c.n_feature_dims == 3 and m.get("otype") == "VanillaMLP"
+                and m.get("n_neurons") == 64 and m.get("n_hidden_layers") == 1 and m.get("activation") == "ReLU"
+                and m.get("output_activation", "none") in (None, "none") and c.normal_type == "finite_difference"
+                and self.finite_difference_normal_eps is not None and not self.unbounded and not c.isosurface_deformable_grid)
 
     def _heads_weights(self):
         return (self.sdf_network.layers[0].weight, self.sdf_network.layers[2].weight,
@@ -322,73 +373,6 @@ class Voxel_3d_Sdf(_SampledSdfGeometry):
 
     def _use_fused(self, points) -> bool:
         return getattr(self, "_fcfg", None) is not None and points.is_cuda and os.environ.get("ASD_VOXFIELD", "1") != "0"
-
-    def _forward_points(self, points, space_cache, output_normal):
-        if not self._use_fused(points):
-            return super()._forward_points(points, space_cache, output_normal)
-        vol = channels_last(space_cache)                                  # [B, D, H, W, 32] (the HIP generator's own layout: a view)
-        w = self._heads_weights()
-        need_grad = torch.is_grad_enabled() and (vol.requires_grad or w[0].requires_grad)
-        outs = []
-        for b in range(points.shape[0]):
-            pts = points[b].reshape(-1, 3).contiguous().float()
-            if need_grad:
-                outs.append(_VoxFieldFn.apply(pts, *self._gate(space_cache, vol, b), *w, self._fcfg, bool(output_normal)))
-            else:
-                with torch.no_grad():
-                    outs.append(ops.voxfield_fwd(vol[b], self._fcfg, *w, pts, bool(output_normal), save_enc=False)[:4])
-        st = lambda i: torch.stack([o[i] for o in outs], 0)
-        out = {"sdf": st(0)[..., None], "features": st(1)}
-        if output_normal:
-            normal, sdf_grad = st(2), st(3)
-            out.update(normal=normal, shading_normal=normal, sdf_grad=sdf_grad)
-        return out
-
-    def forward_sdf(self, points, space_cache):
-        if not self._use_fused(points):
-            return super().forward_sdf(points, space_cache)
-        vol, w = channels_last(space_cache), self._heads_weights()
-        B = points.shape[0]
-        with torch.set_grad_enabled(torch.is_grad_enabled()):
-            pts = points.reshape(B, -1, 3)
-            need_grad = torch.is_grad_enabled() and (vol.requires_grad or w[0].requires_grad)
-            outs = []
-            for b in range(B):
-                p = pts[b].contiguous().float()
-                if need_grad:
-                    outs.append(_VoxFieldFn.apply(p, *self._gate(space_cache, vol, b), *w, self._fcfg, False)[0])
-                else:
-                    outs.append(ops.voxfield_fwd(vol[b], self._fcfg, *w, p, False, want_features=False, save_enc=False)[0])
-        return torch.stack(outs, 0).reshape(*points.shape[:-1], 1)
-
-
-class _TriFieldFn(torch.autograd.Function):
-    """(sdf, features, normal, sdf_grad) of ONE batch entry from its points, its channel-last planes [3, H, W, 32] and the two 96 -> 64 -> 64 -> 1 | 3
-    heads (include/asd_hip.h: asd_trifield_fwd / _bwd); nothing but the points and the sdf is kept for the backward pass"""
-
-    @staticmethod
-    def forward(ctx, points, planes_cl, b, slot, s1, s2, s3, f1, f2, f3, fcfg, want_normal):
-        """planes_cl: the WHOLE channel-last cache [B, 3, H, W, 32] (contiguous), b: the entry these points sample"""
-        w6 = (s1.t().contiguous(), s2.contiguous(), s3.contiguous(), f1.t().contiguous(), f2.contiguous(), f3.contiguous())
-        sdf, feats, normal, fdg = ops.trifield_fwd(planes_cl[b], fcfg, w6, points, want_normal)
-        if not want_normal:
-            normal, fdg = sdf.new_zeros(0), sdf.new_zeros(0)
-            ctx.mark_non_differentiable(normal, fdg)
-        ctx.save_for_backward(points, planes_cl, sdf, *w6)
-        ctx.fcfg, ctx.want_normal, ctx.slot, ctx.b = fcfg, want_normal, slot, b
-        ctx.set_materialize_grads(False)
-        return sdf, feats, normal, fdg
-
-    @staticmethod
-    def backward(ctx, d_sdf, d_feats, d_normal, d_fdg):
-        points, planes_cl, sdf, *w6 = ctx.saved_tensors
-        if d_sdf is None and d_feats is None and d_normal is None and d_fdg is None:
-            return (None,) * 12
-        d_pl, first = (ctx.slot or _GradSlot()).acquire(planes_cl)
-        c = lambda t: None if t is None else t.contiguous()
-        dws = ops.trifield_bwd(planes_cl[ctx.b], ctx.fcfg, w6, points, sdf, c(d_sdf), c(d_feats), c(d_normal) if ctx.want_normal else None,
-                               c(d_fdg) if ctx.want_normal else None, d_pl[ctx.b])
-        return (None, (d_pl if first else None), None, None, *dws, None, None)
 
 
 @register("Triplane-transformer-sdf")
@@ -426,33 +410,16 @@ class TriplaneTransformerSDF(_SampledSdfGeometry):
     def interpolate_encodings(self, points, space_cache):
         return sample_from_planes(plane_features=space_cache, coordinates=points).view(*points.shape[:-1], -1)
 
-    def update_step(self, epoch: int, global_step: int, on_load_weights: bool = False):
-        super().update_step(epoch, global_step, on_load_weights)
-        self._fcfg = self._field_cfg()
-
     # ---- fused path: three lookups + both heads + bias + finite differences as one kernel each way (the shipped configuration) -----------
-    def _field_cfg(self) -> Optional[_lib.FieldCfg]:
-        c = self.cfg
-        if c.sdf_bias == "sphere" and isinstance(c.sdf_bias_params, float):
-            bias, value = _lib.ASD_BIAS_SPHERE, float(c.sdf_bias_params)
-        elif isinstance(c.sdf_bias, float):
-            bias, value = _lib.ASD_BIAS_CONST, float(c.sdf_bias)
-        else:
-            return None
-        m = c.mlp_network_config
-        ok = (c.space_generator_config["triplane_dim"] == 32 and c.n_feature_dims == 3 and m.get("otype") == "VanillaMLP"
-              and m.get("n_neurons") == 64 and m.get("n_hidden_layers") == 2 and m.get("activation") == "ReLU"
-              and m.get("output_activation", "none") in (None, "none") and c.normal_type == "finite_difference"
-              and self.finite_difference_normal_eps is not None and not self.unbounded and not c.isosurface_deformable_grid)
-        if not ok:
-            return None
-        f = _lib.FieldCfg()
-        for d in range(3):
-            f.bbox_min[d], f.bbox_max[d] = -c.radius, c.radius
-        f.radius, f.bias_mode, f.bias_value = c.radius, bias, value
-        f.blob_scale, f.blob_std, f.activation = 0.0, 1.0, _lib.ASD_ACT_NONE
-        f.fd_eps, f.n_hidden, f.n_feature_dims, f.field_mode = float(self.finite_difference_normal_eps), 64, 3, _lib.ASD_FIELD_SDF
-        return f
+    _field = _TRIFIELD
+    _channels_last = staticmethod(planes_channels_last)                   # [B, 3, H, W, 32]
+
+    def _fused_eligible(self) -> bool:
+        c, m = self.cfg, self.cfg.mlp_network_config
+        return (c.space_generator_config["triplane_dim"] == 32 and c.n_feature_dims == 3 and m.get("otype") == "VanillaMLP"
+                and m.get("n_neurons") == 64 and m.get("n_hidden_layers") == 2 and m.get("activation") == "ReLU"
+                and m.get("output_activation", "none") in (None, "none") and c.normal_type == "finite_difference"
+                and self.finite_difference_normal_eps is not None and not self.unbounded and not c.isosurface_deformable_grid)
 
     def _heads_weights(self):
         s, f = self.sdf_network.layers, self.feature_network.layers
@@ -460,42 +427,3 @@ class TriplaneTransformerSDF(_SampledSdfGeometry):
 
     def _use_fused(self, points) -> bool:
         return getattr(self, "_fcfg", None) is not None and points.is_cuda and os.environ.get("ASD_TRIFIELD", "1") != "0"
-
-    def _forward_points(self, points, space_cache, output_normal):
-        if not self._use_fused(points):
-            return super()._forward_points(points, space_cache, output_normal)
-        planes = planes_channels_last(space_cache)                        # [B, 3, H, W, 32]
-        w = self._heads_weights()
-        need_grad = torch.is_grad_enabled() and (planes.requires_grad or w[0].requires_grad)
-        outs = []
-        for b in range(points.shape[0]):
-            pts = points[b].reshape(-1, 3).contiguous().float()
-            if need_grad:
-                outs.append(_TriFieldFn.apply(pts, *self._gate(space_cache, planes, b), *w, self._fcfg, bool(output_normal)))
-            else:
-                with torch.no_grad():
-                    w6 = (w[0].t().contiguous(), w[1], w[2], w[3].t().contiguous(), w[4], w[5])
-                    outs.append(ops.trifield_fwd(planes[b], self._fcfg, w6, pts, bool(output_normal)))
-        st = lambda i: torch.stack([o[i] for o in outs], 0)
-        out = {"sdf": st(0)[..., None], "features": st(1)}
-        if output_normal:
-            normal, sdf_grad = st(2), st(3)
-            out.update(normal=normal, shading_normal=normal, sdf_grad=sdf_grad)
-        return out
-
-    def forward_sdf(self, points, space_cache):
-        if not self._use_fused(points):
-            return super().forward_sdf(points, space_cache)
-        planes, w = planes_channels_last(space_cache), self._heads_weights()
-        B = points.shape[0]
-        pts = points.reshape(B, -1, 3)
-        need_grad = torch.is_grad_enabled() and (planes.requires_grad or w[0].requires_grad)
-        outs = []
-        for b in range(B):
-            p = pts[b].contiguous().float()
-            if need_grad:
-                outs.append(_TriFieldFn.apply(p, *self._gate(space_cache, planes, b), *w, self._fcfg, False)[0])
-            else:
-                w6 = (w[0].t().contiguous(), w[1], w[2], w[3].t().contiguous(), w[4], w[5])
-                outs.append(ops.trifield_fwd(planes[b], self._fcfg, w6, p, False, want_features=False)[0])
-        return torch.stack(outs, 0).reshape(*points.shape[:-1], 1)

@@ -22,8 +22,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, dist, ops
-from .geometry import BaseImplicitGeometry, contract_to_unisphere
-from .hyper import _SdfFieldFn
+from .geometry import BaseImplicitGeometry, _SdfFieldFn, contract_to_unisphere, make_field_cfg, sdf_bias_mode, shifted_sdf
 from .networks import VanillaMLP, get_encoding, get_mlp
 from .registry import info, register, warn
 
@@ -87,11 +86,8 @@ class ImplicitSDF(BaseImplicitGeometry):
     # ---- fused-kernel eligibility (the conditions of ImplicitVolume._make_field_cfg) ----------------------------------------------
     def _make_field_cfg(self) -> Optional[_lib.FieldCfg]:
         c = self.cfg
-        if c.sdf_bias == "sphere" and isinstance(c.sdf_bias_params, float):
-            bias, value = _lib.ASD_BIAS_SPHERE, float(c.sdf_bias_params)
-        elif isinstance(c.sdf_bias, float):
-            bias, value = _lib.ASD_BIAS_CONST, float(c.sdf_bias)
-        else:
+        bias = sdf_bias_mode(c)
+        if bias is None:
             return None
         mlp = c.mlp_network_config
         ok = (
@@ -103,16 +99,10 @@ class ImplicitSDF(BaseImplicitGeometry):
         )
         if not ok:
             return None
-        f = _lib.FieldCfg()
-        for d in range(3):
-            f.bbox_min[d], f.bbox_max[d] = -c.radius, c.radius
-        f.radius, f.bias_mode, f.bias_value = c.radius, bias, value
-        f.blob_scale, f.blob_std, f.activation = 0.0, 1.0, _lib.ASD_ACT_NONE
         # "progressive": update_step writes the step of the finest active level before anything asks for a normal (0.01, the config's
         # default, stands in until then)
         eps = float(c.finite_difference_normal_eps) if isinstance(c.finite_difference_normal_eps, float) else 0.01
-        f.fd_eps, f.n_hidden, f.n_feature_dims, f.field_mode = eps, 64, c.n_feature_dims, _lib.ASD_FIELD_SDF
-        return f
+        return make_field_cfg(c.radius, *bias, eps, c.n_feature_dims, _lib.ASD_FIELD_SDF)
 
     @property
     def fused(self) -> bool:
@@ -165,19 +155,7 @@ class ImplicitSDF(BaseImplicitGeometry):
             dist.broadcast_parameters(self, src=0)
 
     def get_shifted_sdf(self, points, sdf):
-        c = self.cfg
-        if c.sdf_bias == "ellipsoid":
-            assert hasattr(c.sdf_bias_params, "__len__") and len(c.sdf_bias_params) == 3
-            size = torch.as_tensor(list(c.sdf_bias_params)).to(points)
-            bias = ((points / size) ** 2).sum(dim=-1, keepdim=True).sqrt() - 1.0
-        elif c.sdf_bias == "sphere":
-            assert isinstance(c.sdf_bias_params, float)
-            bias = (points ** 2).sum(dim=-1, keepdim=True).sqrt() - c.sdf_bias_params
-        elif isinstance(c.sdf_bias, float):
-            bias = c.sdf_bias
-        else:
-            raise ValueError(f"Unknown sdf bias {c.sdf_bias}")
-        return sdf + bias
+        return shifted_sdf(self.cfg, points, sdf)
 
     # ---- forward ----------------------------------------------------------------------------------------------------------------------
     def forward(self, points: torch.Tensor, output_normal: bool = False) -> Dict[str, torch.Tensor]:
