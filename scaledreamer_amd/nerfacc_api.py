@@ -3,6 +3,7 @@
   OccGridEstimator(roi_aabb, resolution=32, levels=1)     nerf_volume_renderer.py:60-65
       .occs / .binaries / .aabbs / .resolution             (buffers: they travel in checkpoints)
       .sampling(...) -> (ray_indices, t_starts, t_ends)    nerf_volume_renderer.py:139-180
+      .sample_packed(...)                                  the one sampler under .sampling and the renderers' _sample (not in nerfacc)
       .update_every_n_steps(step=, occ_eval_fn=)           nerf_volume_renderer.py:442-444
   render_weight_from_density / render_weight_from_alpha / accumulate_along_rays
                                                            nerf_volume_renderer.py:313-349
@@ -153,31 +154,56 @@ class OccGridEstimator(nn.Module):
         if alpha_fn is not None and sigma_fn is not None:
             raise ValueError("Only one of sigma_fn and alpha_fn can be specified.")
         rays_o, rays_d = rays_o.contiguous().float(), rays_d.contiguous().float()
-        n_rays = rays_o.shape[0]
         if stratified and jitter is None:
-            jitter = torch.rand(n_rays, device=rays_o.device)
+            jitter = torch.rand(rays_o.shape[0], device=rays_o.device)
+        values_fn = sigma_fn if sigma_fn is not None else alpha_fn
+        prune_fn = None
+        if values_fn is not None and (early_stop_eps > 0 or alpha_thre > 0):
+            def prune_fn(pts, t0, t1, ray_idx, offset, count, n_dev):
+                n_cand = ray_idx.shape[0]
+                if n_cand > 0:
+                    vals = values_fn(t0, t1, ray_idx.long()).reshape(-1).contiguous().float()
+                    assert vals.shape[0] == n_cand, f"{'sigmas' if sigma_fn is not None else 'alphas'} must have shape of (N,)! Got {vals.shape}"
+                else:
+                    vals = t0.new_zeros(0)
+                if sigma_fn is None:
+                    # neus_volume_renderer.py:183-194: the same pruning pass on opacities; asd_prune_count takes densities, and
+                    # 1 - exp(-sigma dt) with sigma = -log(1 - alpha) / dt is alpha again (alpha >= 1: sigma = inf, T = 0 behind it)
+                    vals = (-torch.log1p(-vals.clamp(max=1.0)) / (t1 - t0)).contiguous()
+                return ops.prune(vals, t0, t1, offset, count, early_stop_eps, self.alpha_threshold(alpha_thre))
+        return self.sample_packed(rays_o, rays_d, near_plane, far_plane, render_step_size, jitter, prune_fn=prune_fn, points=False)[:3]
+
+    def alpha_threshold(self, alpha_thre: float) -> float:
+        """nerfacc: alpha_thre = min(alpha_thre, occs.mean()) — the host mirror of the mean, as of the last `_bits()`"""
+        return min(alpha_thre, self._occ_mean)
+
+    @torch.no_grad()
+    def sample_packed(self, rays_o, rays_d, near_plane, far_plane, render_step_size, jitter=None, capacity: Optional[int] = None,
+                      prune_fn: Optional[Callable] = None, count_on_device: bool = False, points: bool = True):
+        """The occupancy-grid sampler, the one march -> values -> prune -> scan -> compact sequence of the package:
+        (ray_indices int64, t_starts, t_ends, points, dirs, offset int32, count int32, total) of the kept samples.
+
+        `prune_fn(pts, t0, t1, ray_idx, offset, count, n_dev) -> (keep, kept)` is the visibility pass over the candidates (their mid-points,
+        interval ends, int32 ray index, packed layout and count as an int32 device scalar); without one every candidate is kept (and
+        with `points=False` handed back as it is: no compact launch, no points or dirs).  `capacity` sizes the candidate buffers (default:
+        exactly, which costs one read of the candidate count).  `total` is None and the sample tensors have exactly the kept length — or,
+        with `count_on_device`, capacity-sized buffers and a pruning pass, `total` is the kept count as an int32 device tensor [1] and the
+        sample tensors keep the candidates' capacity: only their first `total` rows are written (ray_indices reads 0 behind them), and
+        no device->host read happens in here at all."""
         cfg = self.march_cfg(near_plane, far_plane, render_step_size)
-        bits = self._bits()
-        count, offset, total, ray_idx, t0, t1, pts = ops.march(cfg, rays_o, rays_d, bits, jitter)
-        prune_fn = sigma_fn if sigma_fn is not None else alpha_fn
-        if prune_fn is not None and (early_stop_eps > 0 or alpha_thre > 0):
-            alpha_thre = min(alpha_thre, self._occ_mean)
-            n_cand = ray_idx.shape[0]
-            if n_cand > 0:
-                vals = prune_fn(t0, t1, ray_idx.long()).reshape(-1).contiguous().float()
-                assert vals.shape[0] == n_cand, f"{'sigmas' if sigma_fn is not None else 'alphas'} must have shape of (N,)! Got {vals.shape}"
+        count, offset, total, ray_idx, t0, t1, pts = ops.march(cfg, rays_o, rays_d, self._bits(), jitter, n_max=capacity)
+        if prune_fn is None and not points:
+            return ray_idx.long(), t0, t1, None, None, offset, count, None
+        keep, kept, kept_offset, n_out, n_dev = None, count, offset, ray_idx.shape[0], None
+        if prune_fn is not None:
+            keep, kept = prune_fn(pts, t0, t1, ray_idx, offset, count, total)
+            kept_offset, kept_total = ops.scan_i32(kept)
+            if count_on_device and capacity is not None and n_out > 0:
+                n_dev = kept_total.reshape(1)
             else:
-                vals = t0.new_zeros(0)
-            if sigma_fn is None:
-                # neus_volume_renderer.py:183-194: the same pruning pass on opacities; asd_prune_count takes densities, and
-                # 1 - exp(-sigma dt) with sigma = -log(1 - alpha) / dt is alpha again (alpha >= 1: sigma = inf, T = 0 behind it)
-                vals = (-torch.log1p(-vals.clamp(max=1.0)) / (t1 - t0)).contiguous()
-            keep, kept = ops.prune(vals, t0, t1, offset, count, early_stop_eps, alpha_thre)
-            koff, ktot = ops.scan_i32(kept)
-            n_out = int(ktot.item())
-            ri, k0, k1, _, _ = ops.compact(rays_o, rays_d, offset, count, keep, t0, t1, koff, n_out)
-            return ri, k0, k1
-        return ray_idx.long(), t0, t1
+                n_out = int(kept_total.item())
+        ri, k0, k1, kp, kd = ops.compact(rays_o, rays_d, offset, count, keep, t0, t1, kept_offset, n_out, zero_ray_idx=n_dev is not None)
+        return ri, k0, k1, kp, kd, kept_offset, kept, n_dev
 
     # -- maintenance -----------------------------------------------------------------------------
     @torch.no_grad()

@@ -8,7 +8,9 @@ csrc/render.hip; what is specific to NeuS — the opacity model of the learned v
     update_step  cos_anneal_ratio, and the occupancy update with asd_neus_step_alpha as occ_eval_fn
 Two routes (ASD_NEUS, read at every call; "0" = composed, kept as fallback and A/B partner): the composed route forms alpha with tensor ops
 (get_alpha / step_alpha of sdf_opacity.py), prunes with asd_prune_count fed -log(1 - alpha) / dt and composites with asd_composite_* mode 1.
-This first version reads the kept count once per pass; the sync-free, capacity-sized form of the NeRF renderer is not carried over.
+This renderer reads the kept count once per pass; the sync-free, capacity-sized form of the NeRF renderer is not carried over.  The sampler
+is shared (renderer.OccGridVolumeRenderer), so adopting it takes `count_on_device` in `_sample` and a forward that hands `n_dev` to the field and
+defers the per-sample entries (renderer.defer_per_sample); asd_neus_composite_* is per ray already.
 """
 from __future__ import annotations
 
@@ -21,7 +23,7 @@ import torch.nn.functional as F
 
 from . import nerfacc_api, ops
 from .registry import register
-from .renderer import VolumeRenderer, chunk_batch, validate_empty_rays
+from .renderer import OccGridVolumeRenderer, VolumeRenderer, background_colour, chunk_batch, image_outputs, per_sample_entries
 from .sdf_opacity import LearnedVariance, get_alpha, kernel_color_act, step_alpha
 
 
@@ -55,7 +57,7 @@ class _NeuSCompositeFn(torch.autograd.Function):
 
 
 @register("neus-volume-renderer")
-class NeuSVolumeRenderer(VolumeRenderer):
+class NeuSVolumeRenderer(OccGridVolumeRenderer):
     @dataclass
     class Config(VolumeRenderer.Config):
         num_samples_per_ray: int = 512
@@ -72,25 +74,18 @@ class NeuSVolumeRenderer(VolumeRenderer):
         num_samples_per_ray_importance: int = 64
 
     cfg: Config
-    MAX_CANDIDATE_CAPACITY = 48 << 20       # as NeRFVolumeRenderer: upper bound of the capacity-sized candidate buffers
 
     def configure(self, geometry, material, background) -> None:
-        super().configure(geometry, material, background)
         self.variance = LearnedVariance(self.cfg.learned_variance_init)
-        if self.cfg.estimator == "occgrid":
-            self.estimator = nerfacc_api.OccGridEstimator(roi_aabb=self.bbox.view(-1), resolution=32, levels=1)
-            if not self.cfg.grid_prune:
-                self.estimator.occs.fill_(True)
-                self.estimator.binaries.fill_(True)
-            self.render_step_size = 1.732 * 2 * self.cfg.radius / self.cfg.num_samples_per_ray
-            self.randomized = self.cfg.randomized
-        elif self.cfg.estimator == "importance":
-            raise NotImplementedError("estimator 'importance': importance-sampled VolSDF rendering is the amortized renderer "
-                                      "(generative-space-volsdf-volume-renderer); the single-prompt NeuS renderer here uses 'occgrid'")
-        else:
-            raise NotImplementedError("unknown estimator, should be in ['occgrid', 'importance']")
         self.cos_anneal_ratio = 1.0
-        self.jitter_fn = lambda n, device: torch.rand(n, device=device)  # injectable, as on the NeRF renderer
+        super().configure(geometry, material, background)
+
+    @staticmethod
+    def _refused_estimator(name: str) -> str:
+        if name == "importance":
+            return ("estimator 'importance': importance-sampled VolSDF rendering is the amortized renderer "
+                    "(generative-space-volsdf-volume-renderer); the single-prompt NeuS renderer here uses 'occgrid'")
+        return "unknown estimator, should be in ['occgrid', 'importance']"
 
     # ---- routes -----------------------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -104,76 +99,42 @@ class NeuSVolumeRenderer(VolumeRenderer):
         return get_alpha(sdf, normal, dirs, dists, self.variance(sdf), self.cos_anneal_ratio, self.cfg.use_volsdf)
 
     # ---- sampling ---------------------------------------------------------------------------------------------------------------------
-    def _candidate_sdf(self, pts: torch.Tensor, n_dev: Optional[torch.Tensor]) -> torch.Tensor:
-        if n_dev is not None:
-            return self.geometry.forward_sdf(pts, n_dev=n_dev)[..., 0]
-        if self.training:
-            return self.geometry.forward_sdf(pts)[..., 0]
-        return chunk_batch(self.geometry.forward_sdf, self.cfg.eval_chunk_size, pts)[..., 0]
-
     def _sample(self, rays_o_flatten, rays_d_flatten):
         """(ray_indices int64, t_starts, t_ends, points, dirs, offset int32, count int32) of the kept samples: the three branches of the
-        reference (:168-194) — no grid pruning, pruning by the grid alone, pruning by the grid and alpha_fn"""
-        n_rays = rays_o_flatten.shape[0]
-        est = self.estimator
-        jitter = self.jitter_fn(n_rays, rays_o_flatten.device) if self.randomized else None
-        cfg = est.march_cfg(self.cfg.near_plane, self.cfg.far_plane, self.render_step_size)
-        bits = est._bits()
-        prune = self.cfg.grid_prune and self.cfg.prune_alpha_threshold
-        # candidates at their upper bound with the count left on the device when the sdf kernel takes it there: one host read per pass
-        # (the kept count below), not two — on either route (the composed one forms its alphas over the whole buffer; the pruning pass
-        # only ever looks at [offset, offset + count) of each ray)
-        fused_sdf = prune and rays_o_flatten.is_cuda and self.training and getattr(self.geometry, "fused", False)
-        n_cap = n_rays * int(cfg.max_steps) if fused_sdf else None
-        if n_cap is not None and n_cap > self.MAX_CANDIDATE_CAPACITY:
-            n_cap = None
-        count, offset, total, ray_idx, t0, t1, pts = ops.march(cfg, rays_o_flatten, rays_d_flatten, bits, jitter, n_max=n_cap)
-        if prune:
-            early_stop_eps, alpha_thre = 1e-4, min(0.01, est._occ_mean)       # nerfacc: alpha_thre = min(alpha_thre, occs.mean())
-            p = self.variance._inv_std.detach()
-            if ray_idx.shape[0] > 0:
-                sdf = self._candidate_sdf(pts, total if n_cap is not None else None).contiguous().float()
-            else:
-                sdf = t0.new_zeros(0)
-            if self._fused_route(rays_o_flatten):
-                keep, kept = ops.neus_prune(sdf, offset, count, p, self.render_step_size, self.cfg.use_volsdf, early_stop_eps, alpha_thre)
-            else:
+        reference (:168-194) — no grid pruning, pruning by the grid alone, pruning by the grid and alpha_fn.  One host read per pass (the kept
+        count), not two, where the sdf kernel takes the candidate count on the device — on either route (the composed one forms its alphas
+        over the whole buffer; the pruning pass only ever looks at [offset, offset + count) of each ray)."""
+        _, capacity = self._candidates(rays_o_flatten)
+        prune_fn = None
+        if self.cfg.grid_prune and self.cfg.prune_alpha_threshold:
+            def prune_fn(pts, t0, t1, ray_idx, offset, count, n_dev):
+                early_stop_eps, alpha_thre = 1e-4, self.estimator.alpha_threshold(0.01)
+                sdf = self._candidate_values(self.geometry.forward_sdf, pts, n_dev if capacity is not None else None)
+                if self._fused_route(rays_o_flatten):
+                    return ops.neus_prune(sdf, offset, count, self.variance._inv_std.detach(), self.render_step_size, self.cfg.use_volsdf,
+                                          early_stop_eps, alpha_thre)
                 alpha = step_alpha(sdf, self.variance(sdf), self.render_step_size, self.cfg.use_volsdf)
                 # (a VolSDF alpha above 1 has no density: it ends the ray here, while the running product of the fused kernel — nerfacc's —
                 # changes sign behind it; step * inv_std <= 1 keeps the two routes on the same samples)
                 sigma = -torch.log1p(-alpha.clamp(max=1.0)) / (t1 - t0)
-                keep, kept = ops.prune(sigma.contiguous(), t0, t1, offset, count, early_stop_eps, alpha_thre)
-            koff, ktot = ops.scan_i32(kept)
-            n_out = int(ktot.item())
-            ri, k0, k1, kp, kd = ops.compact(rays_o_flatten, rays_d_flatten, offset, count, keep, t0, t1, koff, n_out)
-            return ri, k0, k1, kp, kd, koff, kept
-        n_out = ray_idx.shape[0]
-        ri, k0, k1, kp, kd = ops.compact(rays_o_flatten, rays_d_flatten, offset, count, None, t0, t1, offset, n_out)
-        return ri, k0, k1, kp, kd, offset, count
+                return ops.prune(sigma.contiguous(), t0, t1, offset, count, early_stop_eps, alpha_thre)
+        return self._sample_packed(rays_o_flatten, rays_d_flatten, capacity, prune_fn)[:7]
 
     # ---- forward ----------------------------------------------------------------------------------------------------------------------
     def forward(self, rays_o: torch.Tensor, rays_d: torch.Tensor, light_positions: torch.Tensor, bg_color: Optional[torch.Tensor] = None,
                 **kwargs) -> Dict[str, torch.Tensor]:
-        batch_size, height, width = rays_o.shape[:3]
+        bhw = batch_size, height, width = rays_o.shape[:3]
         rays_o_flatten = rays_o.reshape(-1, 3).contiguous().float()
         rays_d_flatten = rays_d.reshape(-1, 3).contiguous().float()
         light_positions_flatten = light_positions.reshape(-1, 1, 1, 3).expand(-1, height, width, -1).reshape(-1, 3)
         n_rays = rays_o_flatten.shape[0]
         with torch.no_grad():
             ray_indices, t_starts_, t_ends_, positions, t_dirs, offset, count = self._sample(rays_o_flatten, rays_d_flatten)
-        if ray_indices.nelement() == 0:          # the reference's one dummy sample (validate_empty_rays): ray 0, t = 0
-            ray_indices, t_starts_, t_ends_ = validate_empty_rays(ray_indices, t_starts_, t_ends_)
-            positions = rays_o_flatten[ray_indices] + rays_d_flatten[ray_indices] * 0.0
-            t_dirs = rays_d_flatten[ray_indices]
-            count = torch.zeros(n_rays, dtype=torch.int32, device=rays_o.device)
-            count[0] = 1
-            offset = torch.ones(n_rays, dtype=torch.int32, device=rays_o.device)
-            offset[0] = 0
+        if ray_indices.nelement() == 0:
+            ray_indices, t_starts_, t_ends_, positions, t_dirs, offset, count = self._dummy_sample(
+                ray_indices, t_starts_, t_ends_, rays_o_flatten, rays_d_flatten)
         self._last_n = int(ray_indices.shape[0])
-        t_starts, t_ends = t_starts_[..., None], t_ends_[..., None]
         t_light_positions = light_positions_flatten[ray_indices]
-        t_positions = (t_starts + t_ends) / 2.0
-        t_intervals = t_ends - t_starts
 
         fused = self._fused_route(rays_o_flatten)
         color_act = self._color_act() if fused else None
@@ -189,11 +150,7 @@ class NeuSVolumeRenderer(VolumeRenderer):
                 rgb_fg_all = chunk_batch(self.material, self.cfg.eval_chunk_size, viewdirs=t_dirs, positions=positions,
                                          light_positions=t_light_positions, **geo_out)
             comp_rgb_bg = chunk_batch(self.background, self.cfg.eval_chunk_size, dirs=rays_d)
-
-        if bg_color is None:
-            bg_color = comp_rgb_bg
-        if bg_color.shape[:-1] == (batch_size, height, width):
-            bg_color = bg_color.reshape(batch_size * height * width, -1)
+        bg_color = background_colour(bg_color, comp_rgb_bg, *bhw, per_view=False)
 
         want_cn = not self.training and "normal" in geo_out
         if fused:
@@ -202,7 +159,7 @@ class NeuSVolumeRenderer(VolumeRenderer):
                 geo_out["sdf"], geo_out["normal"], colours, bg_color.float(), self.variance._inv_std, t_dirs, t_starts_, t_ends_, offset, count,
                 act, float(self.cos_anneal_ratio), bool(self.cfg.use_volsdf), want_cn)
         else:
-            alpha = self.get_alpha(geo_out["sdf"], geo_out["normal"], t_dirs, t_intervals)
+            alpha = self.get_alpha(geo_out["sdf"], geo_out["normal"], t_dirs, (t_ends_ - t_starts_)[..., None])
             weights_, opacity_, depth_, comp_rgb_fg, _, comp_rgb = nerfacc_api.composite(
                 alpha[..., 0], rgb_fg_all, bg_color.float(), t_starts_, t_ends_, offset, count, 1)
             comp_normal = None
@@ -210,43 +167,21 @@ class NeuSVolumeRenderer(VolumeRenderer):
                 cn = nerfacc_api.accumulate_along_rays(weights_, values=geo_out["normal"], ray_indices=ray_indices, n_rays=n_rays)
                 comp_normal = (F.normalize(cn, dim=-1) + 1.0) / 2.0 * opacity_[..., None]
 
-        out = {
-            "comp_rgb": comp_rgb.view(batch_size, height, width, -1),
-            "comp_rgb_fg": comp_rgb_fg.view(batch_size, height, width, -1),
-            "comp_rgb_bg": comp_rgb_bg.view(batch_size, height, width, -1),
-            "opacity": opacity_.view(batch_size, height, width, 1),
-            "depth": depth_.view(batch_size, height, width, 1),
-        }
+        out = image_outputs(bhw, comp_rgb, comp_rgb_fg, comp_rgb_bg, opacity_, depth_)
         if self.training:
-            out.update({"weights": weights_[..., None], "t_points": t_positions, "t_intervals": t_intervals, "t_dirs": t_dirs,
-                        "ray_indices": ray_indices, "points": positions, **geo_out})
+            out.update(per_sample_entries(None, t_starts_, t_ends_, weights_, t_dirs, ray_indices, positions, geo_out))
         elif want_cn:
             out["comp_normal"] = comp_normal.view(batch_size, height, width, 3)
         out["inv_std"] = self.variance.inv_std
         return out
 
-    @property
-    def last_n_samples(self) -> int:
-        return int(getattr(self, "_last_n", 0))
-
     # ---- maintenance ------------------------------------------------------------------------------------------------------------------
+    def _occ_eval_fn(self, x):
+        sdf = self.geometry.forward_sdf(x)
+        if self._fused_route(sdf):
+            return ops.neus_step_alpha(sdf, self.variance._inv_std.detach(), self.render_step_size, self.cfg.use_volsdf)
+        return step_alpha(sdf, self.variance(sdf), self.render_step_size, self.cfg.use_volsdf)
+
     def update_step(self, epoch: int, global_step: int, on_load_weights: bool = False) -> None:
         self.cos_anneal_ratio = 1.0 if self.cfg.cos_anneal_end_steps == 0 else min(1.0, global_step / self.cfg.cos_anneal_end_steps)
-        if self.cfg.estimator == "occgrid" and self.cfg.grid_prune:
-
-            def occ_eval_fn(x):
-                sdf = self.geometry.forward_sdf(x)
-                if self._fused_route(sdf):
-                    return ops.neus_step_alpha(sdf, self.variance._inv_std.detach(), self.render_step_size, self.cfg.use_volsdf)
-                return step_alpha(sdf, self.variance(sdf), self.render_step_size, self.cfg.use_volsdf)
-
-            if self.training and not on_load_weights:
-                self.estimator.update_every_n_steps(step=global_step, occ_eval_fn=occ_eval_fn)
-
-    def train(self, mode=True):
-        self.randomized = mode and self.cfg.randomized
-        return super().train(mode=mode)
-
-    def eval(self):
-        self.randomized = False
-        return super().eval()
+        super().update_step(epoch, global_step, on_load_weights)

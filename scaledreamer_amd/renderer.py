@@ -270,8 +270,164 @@ def validate_empty_rays(ray_indices, t_start, t_end):
     return ray_indices, t_start, t_end
 
 
+# ---- what every route of the three volume renderers builds the same way -------------------------------------------------------------
+def background_colour(bg_color, comp_rgb_bg, batch_size: int, height: int, width: int, per_view: bool = True):
+    """the colour compositing blends behind each ray: the background's own image unless the caller names a colour — one per view [B, C]
+    (expanded over the image; `per_view=False` hands it on as it came, as the reference's neus_volume_renderer.py does), an image
+    [B, H, W, C] or rows [n_rays, C].  Images leave as rows."""
+    if bg_color is None:
+        bg_color = comp_rgb_bg
+    elif per_view and bg_color.shape[:-1] == (batch_size,):
+        bg_color = bg_color.unsqueeze(1).unsqueeze(1).expand(-1, height, width, -1)
+    if bg_color.shape[:-1] == (batch_size, height, width):
+        bg_color = bg_color.reshape(batch_size * height * width, -1)
+    return bg_color
+
+
+def image_outputs(bhw, comp_rgb, comp_rgb_fg, comp_rgb_bg, opacity, depth, z_variance=None) -> Dict[str, torch.Tensor]:
+    """the per-ray entries of an output dictionary as images [B, H, W, C], in the reference's order"""
+    out = {"comp_rgb": comp_rgb.reshape(*bhw, -1), "comp_rgb_fg": comp_rgb_fg.reshape(*bhw, -1), "comp_rgb_bg": comp_rgb_bg.reshape(*bhw, -1),
+           "opacity": opacity.reshape(*bhw, 1), "depth": depth.reshape(*bhw, 1)}
+    if z_variance is not None:
+        out["z_variance"] = z_variance.reshape(*bhw, 1)
+    return out
+
+
+SAMPLE_KEYS = ("weights", "t_points", "t_intervals", "t_dirs", "ray_indices", "points")
+
+
+def per_sample_entries(n: Optional[int], t0, t1, weights, dirs, ray_indices, points, geo_out) -> Dict[str, torch.Tensor]:
+    """the per-sample entries of a training pass's output dictionary (SAMPLE_KEYS, then the geometry's own) from the packed sample tensors:
+    all of their rows, or the first n of capacity-sized ones"""
+    cut = (lambda t: t) if n is None else (lambda t: t[:n])
+    t0, t1 = cut(t0)[..., None], cut(t1)[..., None]
+    out = {"weights": cut(weights)[..., None], "t_points": (t0 + t1) / 2.0, "t_intervals": t1 - t0, "t_dirs": cut(dirs),
+           "ray_indices": cut(ray_indices), "points": cut(points)}
+    out.update({k: cut(v) for k, v in geo_out.items()})
+    return out
+
+
+def kept_points(n_dev, points, rays_o) -> torch.Tensor:
+    """`points(n)`, the n written rows of a capacity-sized buffer, with ONE read of the device count — or, of an empty batch, the position
+    of the reference's dummy sample (validate_empty_rays): the origin of ray 0"""
+    n = int(n_dev.item())
+    return points(n) if n > 0 else rays_o[:1].detach()
+
+
+def defer_per_sample(out: LazyOutputs, n_dev, geometry, rays_o, rays_d, geo_keys, rows) -> None:
+    """the per-sample entries of a pass that left the kept count on the device: made with ONE read of the count when somebody first asks for
+    one.  `rows(n)` -> (t0, t1, weights, dirs, ray_indices, points, geo_out) holding at least n rows.  An empty batch gives the one dummy
+    sample: ray 0, t = 0, no weight, the field's entries at its position zeroed."""
+    def per_sample():
+        n = int(n_dev.item())
+        if n > 0:
+            return per_sample_entries(n, *rows(n))
+        point = rays_o[:1].detach()
+        z = point.new_zeros(1)
+        geo_out = {k: v * 0.0 for k, v in geometry(point, output_normal=False).items()}
+        return per_sample_entries(None, z, z, z, rays_d[:1], torch.zeros(1, dtype=torch.long, device=z.device), point, geo_out)
+
+    out.defer(SAMPLE_KEYS + tuple(geo_keys), per_sample)
+
+
+def defer_normals(out: LazyOutputs, geometry, points) -> None:
+    """`normal` / `shading_normal` of a material that asks for normals nothing in the call reads: the geometry is evaluated with them at
+    `points()` only if somebody indexes one (LazyOutputs)"""
+    def lazy_normal():
+        g = geometry(points(), output_normal=True)
+        return {"normal": g["normal"], "shading_normal": g["shading_normal"]}
+
+    out.defer(("normal", "shading_normal"), lazy_normal)
+
+
+class OccGridVolumeRenderer(VolumeRenderer):
+    """What the two occupancy-grid renderers (nerf-volume-renderer, neus-volume-renderer) share: the estimator and its step size, the
+    candidate-capacity rule and the call of the one sampler (nerfacc_api.OccGridEstimator.sample_packed), the dummy sample of an all-miss
+    batch, and the occupancy update.  A class says what it prunes with (`_sample`) and what the grid holds (`_occ_eval_fn`)."""
+
+    # upper bound of the capacity-sized candidate buffers (~28 B per candidate across ray_idx / t0 / t1 / points / sigma / keep: 1.3 GB);
+    # also keeps every 3-component index of those buffers far below 2^31
+    MAX_CANDIDATE_CAPACITY = 48 << 20
+
+    def configure(self, geometry, material, background) -> None:
+        super().configure(geometry, material, background)
+        if self.cfg.estimator != "occgrid":
+            raise NotImplementedError(self._refused_estimator(self.cfg.estimator))
+        self.estimator = nerfacc_api.OccGridEstimator(roi_aabb=self.bbox.view(-1), resolution=32, levels=1)
+        if not self.cfg.grid_prune:
+            self.estimator.occs.fill_(True)
+            self.estimator.binaries.fill_(True)
+        self.render_step_size = 1.732 * 2 * self.cfg.radius / self.cfg.num_samples_per_ray
+        self.randomized = self.cfg.randomized
+        self.jitter_fn = lambda n, device: torch.rand(n, device=device)  # injectable (SURVEY.md Appendix C #2)
+
+    def _march_cfg(self) -> "_lib.MarchCfg":
+        return self.estimator.march_cfg(self.cfg.near_plane, self.cfg.far_plane, self.render_step_size)
+
+    def _capacity(self, n_rays: int) -> Optional[int]:
+        """every ray at most max_steps lattice points; None for large batches (256^2 x 4 views: 1.3e8 lattice points)"""
+        n_cap = n_rays * int(self._march_cfg().max_steps)
+        return n_cap if n_cap <= self.MAX_CANDIDATE_CAPACITY else None
+
+    def _candidates(self, rays_o):
+        """(device_count, capacity).  With a pruning pass on the fused field kernels in training, the candidate buffers stand at their
+        upper bound and the candidate count stays on the device: the pruning pass only ever looks at [offset, offset + count) of each ray,
+        and the field kernel takes the total as a device scalar — no device->host read of it.  Above MAX_CANDIDATE_CAPACITY: exact-size
+        buffers after one count read-back."""
+        device_count = bool(self.training and self.cfg.grid_prune and self.cfg.prune_alpha_threshold
+                            and getattr(self.geometry, "fused", False) and rays_o.is_cuda)
+        return device_count, (self._capacity(rays_o.shape[0]) if device_count else None)
+
+    def _candidate_values(self, field_fn, pts, n_dev=None) -> torch.Tensor:
+        """field_fn (forward_density / forward_sdf) at the candidate mid-points the marcher produced, [n]: over the first n_dev rows where
+        the count stays on the device, in chunks of eval_chunk_size outside training"""
+        if pts.shape[0] == 0:
+            return pts.new_zeros(0)
+        if n_dev is not None:
+            vals = field_fn(pts, n_dev=n_dev)
+        elif self.training:
+            vals = field_fn(pts)
+        else:
+            vals = chunk_batch(field_fn, self.cfg.eval_chunk_size, pts)
+        return vals[..., 0].contiguous().float()
+
+    def _sample_packed(self, rays_o, rays_d, capacity, prune_fn, count_on_device: bool = False):
+        jitter = self.jitter_fn(rays_o.shape[0], rays_o.device) if self.randomized else None
+        return self.estimator.sample_packed(rays_o, rays_d, self.cfg.near_plane, self.cfg.far_plane, self.render_step_size, jitter,
+                                            capacity, prune_fn, count_on_device)
+
+    @staticmethod
+    def _dummy_sample(ray_indices, t_starts, t_ends, rays_o, rays_d):
+        """the reference's one dummy sample of a batch that kept nothing (validate_empty_rays): ray 0, t = 0, with its packed layout"""
+        ray_indices, t_starts, t_ends = validate_empty_rays(ray_indices, t_starts, t_ends)
+        positions = rays_o[ray_indices] + rays_d[ray_indices] * 0.0
+        count = torch.zeros(rays_o.shape[0], dtype=torch.int32, device=rays_o.device)
+        count[0] = 1
+        offset = torch.ones(rays_o.shape[0], dtype=torch.int32, device=rays_o.device)
+        offset[0] = 0
+        return ray_indices, t_starts, t_ends, positions, rays_d[ray_indices], offset, count
+
+    @property
+    def last_n_samples(self) -> int:
+        """kept samples of the last forward pass (reads the device count of a sync-free pass when asked)"""
+        n = getattr(self, "_last_n", 0)
+        return int(n.item()) if torch.is_tensor(n) else int(n)
+
+    def update_step(self, epoch: int, global_step: int, on_load_weights: bool = False) -> None:
+        if self.cfg.grid_prune and self.training and not on_load_weights:
+            self.estimator.update_every_n_steps(step=global_step, occ_eval_fn=self._occ_eval_fn)
+
+    def train(self, mode=True):
+        self.randomized = mode and self.cfg.randomized
+        return super().train(mode=mode)
+
+    def eval(self):
+        self.randomized = False
+        return super().eval()
+
+
 @register("nerf-volume-renderer")
-class NeRFVolumeRenderer(VolumeRenderer):
+class NeRFVolumeRenderer(OccGridVolumeRenderer):
     @dataclass
     class Config(VolumeRenderer.Config):
         num_samples_per_ray: int = 512
@@ -291,28 +447,13 @@ class NeRFVolumeRenderer(VolumeRenderer):
         num_samples_per_ray_importance: int = 64
 
     cfg: Config
-    # upper bound of the sync-free candidate buffers (~28 B per candidate across ray_idx / t0 / t1 / points / sigma / keep: 1.3 GB);
-    # also keeps every 3-component index of those buffers far below 2^31
-    MAX_CANDIDATE_CAPACITY = 48 << 20
 
-    def configure(self, geometry, material, background) -> None:
-        super().configure(geometry, material, background)
-        if self.cfg.estimator == "occgrid":
-            self.estimator = nerfacc_api.OccGridEstimator(roi_aabb=self.bbox.view(-1), resolution=32, levels=1)
-            if not self.cfg.grid_prune:
-                self.estimator.occs.fill_(True)
-                self.estimator.binaries.fill_(True)
-            self.render_step_size = 1.732 * 2 * self.cfg.radius / self.cfg.num_samples_per_ray
-            self.randomized = self.cfg.randomized
-        elif self.cfg.estimator in ("importance", "proposal"):
-            raise NotImplementedError(
-                f"estimator {self.cfg.estimator!r}: the single-prompt ASD configs use 'occgrid' "
-                "(importance sampling belongs to the amortized renderer; proposal is unused — SURVEY.md §2.2 N9/N10)"
-            )
-        else:
-            raise NotImplementedError("Unknown estimator, should be one of ['occgrid', 'proposal', 'importance'].")
-        self.vars_in_forward: Dict[str, Any] = {}
-        self.jitter_fn = lambda n, device: torch.rand(n, device=device)  # injectable
+    @staticmethod
+    def _refused_estimator(name: str) -> str:
+        if name in ("importance", "proposal"):
+            return (f"estimator {name!r}: the single-prompt ASD configs use 'occgrid' "
+                    "(importance sampling belongs to the amortized renderer; proposal is unused — SURVEY.md §2.2 N9/N10)")
+        return "Unknown estimator, should be one of ['occgrid', 'proposal', 'importance']."
 
     # ------------------------------------------------------------------------------------------
     def _sample(self, rays_o_flatten, rays_d_flatten, sync_free: bool = False):
@@ -320,55 +461,18 @@ class NeRFVolumeRenderer(VolumeRenderer):
         and the sample tensors have exactly the kept length — or, with sync_free (and the fused candidate path), `total` is the kept
         count as an int32 DEVICE scalar and the sample tensors have the candidates' capacity: only their first `total` rows are
         written (ray_indices reads 0 behind them), and no device->host read happens in here at all."""
-        n_rays = rays_o_flatten.shape[0]
-        est = self.estimator
-        jitter = self.jitter_fn(n_rays, rays_o_flatten.device) if self.randomized else None
-        cfg = est.march_cfg(self.cfg.near_plane, self.cfg.far_plane, self.render_step_size)
-        bits = est._bits()
-        # Candidate buffers at their upper bound (every ray at most max_steps lattice points) with the count left on the device:
-        # the pruning pass below only ever looks at [offset, offset + count) of each ray, and the density kernel takes the total
-        # as a device scalar — no device->host read of the candidate count (one of the two syncs of this method; the kept count
-        # below stays, it sizes every tensor of the output dictionary).
-        prune = self.cfg.grid_prune and self.cfg.prune_alpha_threshold
-        fused_density = self.training and prune and getattr(self.geometry, "fused", False) and rays_o_flatten.is_cuda
-        n_cap = n_rays * int(cfg.max_steps) if fused_density else None
-        if n_cap is not None and n_cap > self.MAX_CANDIDATE_CAPACITY:
-            n_cap = None     # large batches (256^2 x 4 views: 1.3e8 lattice points): exact-size buffers after one count read-back
-        count, offset, total, ray_idx, t0, t1, pts = ops.march(cfg, rays_o_flatten, rays_d_flatten, bits, jitter, n_max=n_cap)
-        if self.cfg.grid_prune:
-            early_stop_eps, alpha_thre = 1e-4, (0.01 if self.cfg.prune_alpha_threshold else 0.0)
-        else:
-            early_stop_eps, alpha_thre = 0.0, 0.0
-        if prune and (early_stop_eps > 0 or alpha_thre > 0):
-            alpha_thre = min(alpha_thre, est._occ_mean)
-            if ray_idx.shape[0] > 0:
-                # sigma at the candidate mid-points (the reference's sigma_fn, nerf_volume_renderer.py:153-167);
-                # the marcher already produced the positions o + d*(t0+t1)/2
-                if fused_density:
-                    sigma = self.geometry.forward_density(pts, n_dev=total)[..., 0]
-                elif self.training:
-                    sigma = self.geometry.forward_density(pts)[..., 0]
-                else:
-                    sigma = chunk_batch(self.geometry.forward_density, self.cfg.eval_chunk_size, pts)[..., 0]
-                sigma = sigma.contiguous().float()
-            else:
-                sigma = t0.new_zeros(0)
-            keep, kept = ops.prune(sigma, t0, t1, offset, count, early_stop_eps, alpha_thre)
-            koff, ktot = ops.scan_i32(kept)
-            if sync_free and fused_density and n_cap is not None and ray_idx.shape[0] > 0:
-                ri, k0, k1, kp, kd = ops.compact(rays_o_flatten, rays_d_flatten, offset, count, keep, t0, t1, koff, ray_idx.shape[0],
-                                                 zero_ray_idx=True)
-                return ri, k0, k1, kp, kd, koff, kept, ktot.reshape(1)
-            n_out = int(ktot.item())
-            ri, k0, k1, kp, kd = ops.compact(rays_o_flatten, rays_d_flatten, offset, count, keep, t0, t1, koff, n_out)
-            return ri, k0, k1, kp, kd, koff, kept, None
-        n_out = ray_idx.shape[0]
-        ri, k0, k1, kp, kd = ops.compact(rays_o_flatten, rays_d_flatten, offset, count, None, t0, t1, offset, n_out)
-        return ri, k0, k1, kp, kd, offset, count, None
+        device_count, capacity = self._candidates(rays_o_flatten)
+        prune_fn = None
+        if self.cfg.grid_prune and self.cfg.prune_alpha_threshold:      # (grid_prune alone: the grid prunes, no visibility pass)
+            def prune_fn(pts, t0, t1, ray_idx, offset, count, n_dev):
+                # sigma at the candidate mid-points (the reference's sigma_fn, nerf_volume_renderer.py:153-167)
+                sigma = self._candidate_values(self.geometry.forward_density, pts, n_dev if device_count else None)
+                return ops.prune(sigma, t0, t1, offset, count, 1e-4, self.estimator.alpha_threshold(0.01))
+        return self._sample_packed(rays_o_flatten, rays_d_flatten, capacity, prune_fn, sync_free)
 
     def forward(self, rays_o: torch.Tensor, rays_d: torch.Tensor, light_positions: torch.Tensor,
                 bg_color: Optional[torch.Tensor] = None, **kwargs) -> Dict[str, torch.Tensor]:
-        batch_size, height, width = rays_o.shape[:3]
+        bhw = batch_size, height, width = rays_o.shape[:3]
         rays_o_flatten = rays_o.reshape(-1, 3).contiguous().float()
         rays_d_flatten = rays_d.reshape(-1, 3).contiguous().float()
         light_positions_flatten = light_positions.reshape(-1, 1, 1, 3).expand(-1, height, width, -1).reshape(-1, 3)
@@ -384,37 +488,26 @@ class NeRFVolumeRenderer(VolumeRenderer):
                      and not self.cfg.return_normal_perturb
                      and not (self.material.requires_normal and getattr(self.material, "reads_normal", True)))
         if sync_free and self._fused_pass_ok(n_rays):
-            return self._forward_fused_pass(batch_size, height, width, rays_o_flatten, rays_d_flatten, rays_d, bg_color, kwargs)
+            return self._forward_fused_pass(bhw, rays_o_flatten, rays_d_flatten, rays_d, bg_color, kwargs)
         with torch.no_grad():
             ray_indices, t_starts_, t_ends_, positions, t_dirs, offset, count, n_dev = self._sample(rays_o_flatten, rays_d_flatten, sync_free)
         if n_dev is not None:
-            return self._forward_sync_free(batch_size, height, width, rays_d, bg_color, ray_indices, t_starts_, t_ends_, positions, t_dirs,
-                                           offset, count, n_dev, kwargs)
+            return self._forward_sync_free(bhw, rays_o_flatten, rays_d_flatten, rays_d, bg_color, ray_indices, t_starts_, t_ends_, positions,
+                                           t_dirs, offset, count, n_dev, kwargs)
         if ray_indices.nelement() == 0:
-            ray_indices, t_starts_, t_ends_ = validate_empty_rays(ray_indices, t_starts_, t_ends_)
-            positions = rays_o_flatten[ray_indices] + rays_d_flatten[ray_indices] * 0.0
-            t_dirs = rays_d_flatten[ray_indices]
-            count = torch.zeros(n_rays, dtype=torch.int32, device=rays_o.device)
-            count[0] = 1
-            offset = torch.ones(n_rays, dtype=torch.int32, device=rays_o.device)
-            offset[0] = 0
+            ray_indices, t_starts_, t_ends_, positions, t_dirs, offset, count = self._dummy_sample(
+                ray_indices, t_starts_, t_ends_, rays_o_flatten, rays_d_flatten)
         self._last_n = int(ray_indices.shape[0])
-        t_starts, t_ends = t_starts_[..., None], t_ends_[..., None]
         t_light_positions = light_positions_flatten[ray_indices]
-        t_positions = (t_starts + t_ends) / 2.0
-        t_intervals = t_ends - t_starts
 
-        lazy_normal = None
+        want_lazy_normal = False
         if self.training:
             # the normal is evaluated with the field only if something inside this call reads it (a shading material, comp_normal,
             # normal_perturb); otherwise it becomes a deferred entry of the output dictionary (LazyOutputs)
             want_normal = bool(self.material.requires_normal)
             now = want_normal and (getattr(self.material, "reads_normal", True) or self.cfg.return_comp_normal or self.cfg.return_normal_perturb)
+            want_lazy_normal = want_normal and not now
             geo_out = self.geometry(positions, output_normal=now)
-            if want_normal and not now:
-                def lazy_normal(geometry=self.geometry, pts=positions):
-                    g = geometry(pts, output_normal=True)
-                    return {"normal": g["normal"], "shading_normal": g["shading_normal"]}
             rgb_fg_all = self.material(viewdirs=t_dirs, positions=positions, light_positions=t_light_positions,
                                        **geo_out, **kwargs)
             comp_rgb_bg = self.background(dirs=rays_d)
@@ -425,40 +518,21 @@ class NeRFVolumeRenderer(VolumeRenderer):
                                      light_positions=t_light_positions, **geo_out)
             comp_rgb_bg = chunk_batch(self.background, self.cfg.eval_chunk_size, dirs=rays_d)
 
-        if bg_color is None:
-            bg_color = comp_rgb_bg
-        else:
-            if bg_color.shape[:-1] == (batch_size,):
-                bg_color = bg_color.unsqueeze(1).unsqueeze(1).expand(-1, height, width, -1)
-        if bg_color.shape[:-1] == (batch_size, height, width):
-            bg_color = bg_color.reshape(batch_size * height * width, -1)
-
         # T / alpha / weights + all per-ray accumulations (reference :312-364) in one fused pass
         weights_, opacity_, depth_, comp_rgb_fg, z_variance_, comp_rgb = nerfacc_api.composite(
-            geo_out["density"][..., 0], rgb_fg_all, bg_color.float(), t_starts_, t_ends_, offset, count, 0
+            geo_out["density"][..., 0], rgb_fg_all, background_colour(bg_color, comp_rgb_bg, *bhw).float(), t_starts_, t_ends_, offset, count, 0
         )
-        weights = weights_[..., None]
-        opacity, depth, z_variance = opacity_[..., None], depth_[..., None], z_variance_[..., None]
-
-        out = LazyOutputs({
-            "comp_rgb": comp_rgb.view(batch_size, height, width, -1),
-            "comp_rgb_fg": comp_rgb_fg.view(batch_size, height, width, -1),
-            "comp_rgb_bg": comp_rgb_bg.view(batch_size, height, width, -1),
-            "opacity": opacity.view(batch_size, height, width, 1),
-            "depth": depth.view(batch_size, height, width, 1),
-            "z_variance": z_variance.view(batch_size, height, width, 1),
-        })
+        out = LazyOutputs(image_outputs(bhw, comp_rgb, comp_rgb_fg, comp_rgb_bg, opacity_, depth_, z_variance_))
 
         def comp_normal_of(normal):
-            cn = nerfacc_api.accumulate_along_rays(weights[..., 0], values=normal, ray_indices=ray_indices, n_rays=n_rays)
+            cn = nerfacc_api.accumulate_along_rays(weights_, values=normal, ray_indices=ray_indices, n_rays=n_rays)
             cn = F.normalize(cn, dim=-1)
-            return ((cn + 1.0) / 2.0 * opacity).view(batch_size, height, width, 3)
+            return ((cn + 1.0) / 2.0 * opacity_[..., None]).view(batch_size, height, width, 3)
 
         if self.training:
-            out.update({"weights": weights, "t_points": t_positions, "t_intervals": t_intervals, "t_dirs": t_dirs,
-                        "ray_indices": ray_indices, "points": positions, **geo_out})
-            if lazy_normal is not None:
-                out.defer(("normal", "shading_normal"), lazy_normal)
+            out.update(per_sample_entries(None, t_starts_, t_ends_, weights_, t_dirs, ray_indices, positions, geo_out))
+            if want_lazy_normal:
+                defer_normals(out, self.geometry, lambda: positions)
             if "normal" in geo_out:
                 if self.cfg.return_comp_normal:
                     out["comp_normal"] = comp_normal_of(geo_out["normal"])
@@ -480,149 +554,60 @@ class NeRFVolumeRenderer(VolumeRenderer):
         return (fc is not None and hasattr(geo, "_weights") and hasattr(geo, "_meta")
                 and getattr(geo.cfg, "n_feature_dims", 0) == 3 and fc.field_mode == _lib.ASD_FIELD_DENSITY
                 and getattr(mat.cfg, "color_activation", "?") in self._COLOR_ACTS and torch.is_grad_enabled()
-                and geo.encoding.encoding.encoding.params.requires_grad
-                and n_rays * int(self.estimator.march_cfg(self.cfg.near_plane, self.cfg.far_plane, self.render_step_size).max_steps) <= self.MAX_CANDIDATE_CAPACITY)
+                and geo.encoding.encoding.encoding.params.requires_grad and self._capacity(n_rays) is not None)
 
-    def _forward_fused_pass(self, batch_size, height, width, rays_o_flatten, rays_d_flatten, rays_d, bg_color, kwargs):
+    def _forward_fused_pass(self, bhw, rays_o_flatten, rays_d_flatten, rays_d, bg_color, kwargs):
         n_rays = rays_o_flatten.shape[0]
-        est, geo = self.estimator, self.geometry
+        est, geo, material = self.estimator, self.geometry, self.material
         jitter = self.jitter_fn(n_rays, rays_o_flatten.device) if self.randomized else None
         if jitter is not None:
             jitter = jitter.contiguous().float()
-        mcfg = est.march_cfg(self.cfg.near_plane, self.cfg.far_plane, self.render_step_size)
+        mcfg = self._march_cfg()
         bits = est._bits()                       # (also refreshes the host mirror of the mean occupancy read below)
         prune = self.cfg.grid_prune and self.cfg.prune_alpha_threshold
-        early_stop_eps, alpha_thre = (1e-4, min(0.01, est._occ_mean)) if prune else (0.0, 0.0)
+        early_stop_eps, alpha_thre = (1e-4, est.alpha_threshold(0.01)) if prune else (0.0, 0.0)
         st = _RenderPass(mcfg, geo._meta, geo._fcfg, rays_o_flatten, rays_d_flatten, bits, jitter, early_stop_eps, alpha_thre, prune,
-                         self._COLOR_ACTS[self.material.cfg.color_activation], n_rays * int(mcfg.max_steps))
+                         self._COLOR_ACTS[material.cfg.color_activation], n_rays * int(mcfg.max_steps))
         comp_rgb_bg = self.background(dirs=rays_d)
-        if bg_color is None:
-            bg_color = comp_rgb_bg
-        elif bg_color.shape[:-1] == (batch_size,):
-            bg_color = bg_color.unsqueeze(1).unsqueeze(1).expand(-1, height, width, -1)
-        if bg_color.shape[:-1] == (batch_size, height, width):
-            bg_color = bg_color.reshape(n_rays, -1)
+        bg_flat = background_colour(bg_color, comp_rgb_bg, *bhw)
         grid = geo.encoding.encoding.encoding.params
-        comp_rgb, comp_rgb_fg, opacity, depth, z_var = _RenderFn.apply(grid, *geo._weights(), bg_color.float().contiguous(), st)
+        comp_rgb, comp_rgb_fg, opacity, depth, z_var = _RenderFn.apply(grid, *geo._weights(), bg_flat.float().contiguous(), st)
         n_dev = st.view("n_kept")
         self._last_n = n_dev
-        out = LazyOutputs({
-            "comp_rgb": comp_rgb.view(batch_size, height, width, -1),
-            "comp_rgb_fg": comp_rgb_fg.view(batch_size, height, width, -1),
-            "comp_rgb_bg": comp_rgb_bg.view(batch_size, height, width, -1),
-            "opacity": opacity.view(batch_size, height, width, 1),
-            "depth": depth.view(batch_size, height, width, 1),
-            "z_variance": z_var.view(batch_size, height, width, 1),
-        })
-        material, bg_flat = self.material, bg_color
+        out = LazyOutputs(image_outputs(bhw, comp_rgb, comp_rgb_fg, comp_rgb_bg, opacity, depth, z_var))
 
-        def per_sample():
-            """the per-sample entries, when somebody reads them: ONE read of the kept count, then the composed (differentiable) evaluation of
-            the same samples — field, material, compositing weights — so that a loss on them reaches the parameters as in the reference"""
-            n = int(n_dev.item())
-            if n == 0:                          # the reference's dummy sample of an empty batch (validate_empty_rays)
-                z = rays_o_flatten.new_zeros(1)
-                pts0 = rays_o_flatten[:1].detach()
-                g = geo(pts0, output_normal=False)
-                o = {"weights": z[..., None], "t_points": z[..., None], "t_intervals": z[..., None], "t_dirs": rays_d_flatten[:1],
-                     "ray_indices": torch.zeros(1, dtype=torch.long, device=z.device), "points": pts0}
-                o.update({k: v * 0.0 for k, v in g.items()})
-                return o
-            t0, t1, pts = st.view("t0", rows=n), st.view("t1", rows=n), st.view("pts", 3, rows=n)
+        def rows(n):
+            """the composed (differentiable) evaluation of the same samples — field, material, compositing weights — so that a loss on the
+            per-sample entries reaches the parameters as in the reference"""
+            t0, t1, pts, dirs = st.view("t0", rows=n), st.view("t1", rows=n), st.view("pts", 3, rows=n), st.view("dirs", 3, rows=n)
             g = geo(pts, output_normal=False)
-            rgb = material(viewdirs=st.view("dirs", 3, rows=n), positions=pts, light_positions=None, **g, **kwargs)
+            rgb = material(viewdirs=dirs, positions=pts, light_positions=None, **g, **kwargs)
             w = nerfacc_api.composite(g["density"][..., 0], rgb, bg_flat.float().detach(), t0, t1, st.view("koff"), st.view("kept"), 0)[0]
-            o = {"weights": w[..., None], "t_points": ((t0 + t1) / 2.0)[..., None], "t_intervals": (t1 - t0)[..., None],
-                 "t_dirs": st.view("dirs", 3, rows=n), "ray_indices": st.view("ray_idx", rows=n), "points": pts}
-            o.update(g)
-            return o
+            return t0, t1, w, dirs, st.view("ray_idx", rows=n), pts, g
 
-        geo_keys = ("density", "features")
-        out.defer(("weights", "t_points", "t_intervals", "t_dirs", "ray_indices", "points") + geo_keys, per_sample)
-        if self.material.requires_normal:
-            def lazy_normal():
-                n = int(n_dev.item())
-                pts = st.view("pts", 3, rows=n) if n > 0 else rays_o_flatten[:1].detach()
-                g = geo(pts, output_normal=True)
-                return {"normal": g["normal"], "shading_normal": g["shading_normal"]}
-            out.defer(("normal", "shading_normal"), lazy_normal)
+        defer_per_sample(out, n_dev, geo, rays_o_flatten, rays_d_flatten, ("density", "features"), rows)
+        if material.requires_normal:
+            defer_normals(out, geo, lambda: kept_points(n_dev, lambda n: st.view("pts", 3, rows=n), rays_o_flatten))
         return out
 
-    @property
-    def last_n_samples(self) -> int:
-        """kept samples of the last forward pass (reads the device count of a sync-free pass when asked)"""
-        n = getattr(self, "_last_n", 0)
-        return int(n.item()) if torch.is_tensor(n) else int(n)
-
-    def _forward_sync_free(self, batch_size, height, width, rays_d, bg_color, ray_indices, t_starts_, t_ends_, positions, t_dirs,
+    def _forward_sync_free(self, bhw, rays_o_flatten, rays_d_flatten, rays_d, bg_color, ray_indices, t_starts_, t_ends_, positions, t_dirs,
                            offset, count, n_dev, kwargs):
         """forward() behind the sampler with the kept count on the device (see there): same arithmetic on the first n_dev rows"""
-        n_rays = batch_size * height * width
         self._last_n = n_dev
         geo_out = self.geometry(positions, output_normal=False, n_dev=n_dev)
         rgb_fg_all = self.material(viewdirs=t_dirs, positions=positions, light_positions=None, **geo_out, **kwargs)
         comp_rgb_bg = self.background(dirs=rays_d)
-        if bg_color is None:
-            bg_color = comp_rgb_bg
-        elif bg_color.shape[:-1] == (batch_size,):
-            bg_color = bg_color.unsqueeze(1).unsqueeze(1).expand(-1, height, width, -1)
-        if bg_color.shape[:-1] == (batch_size, height, width):
-            bg_color = bg_color.reshape(n_rays, -1)
         weights_, opacity_, depth_, comp_rgb_fg, z_variance_, comp_rgb = nerfacc_api.composite(
-            geo_out["density"][..., 0], rgb_fg_all, bg_color.float(), t_starts_, t_ends_, offset, count, 0
+            geo_out["density"][..., 0], rgb_fg_all, background_colour(bg_color, comp_rgb_bg, *bhw).float(), t_starts_, t_ends_, offset, count, 0
         )
-        out = LazyOutputs({
-            "comp_rgb": comp_rgb.view(batch_size, height, width, -1),
-            "comp_rgb_fg": comp_rgb_fg.view(batch_size, height, width, -1),
-            "comp_rgb_bg": comp_rgb_bg.view(batch_size, height, width, -1),
-            "opacity": opacity_[..., None].view(batch_size, height, width, 1),
-            "depth": depth_[..., None].view(batch_size, height, width, 1),
-            "z_variance": z_variance_[..., None].view(batch_size, height, width, 1),
-        })
-        geo_keys = tuple(geo_out)
-
-        def per_sample():                       # exact-length views, made (with ONE read of the count) when first asked for
-            n = int(n_dev.item())
-            if n == 0:                          # the reference's dummy sample of an empty batch (validate_empty_rays)
-                z = t_starts_.new_zeros(1)
-                o = {"weights": z[..., None], "t_points": z[..., None], "t_intervals": z[..., None], "t_dirs": rays_d.reshape(-1, 3)[:1],
-                     "ray_indices": torch.zeros(1, dtype=torch.long, device=z.device), "points": positions[:1] * 0.0}
-                o.update({k: geo_out[k][:1] * 0.0 for k in geo_keys})
-                return o
-            t0, t1 = t_starts_[:n, None], t_ends_[:n, None]
-            o = {"weights": weights_[:n, None], "t_points": (t0 + t1) / 2.0, "t_intervals": t1 - t0, "t_dirs": t_dirs[:n],
-                 "ray_indices": ray_indices[:n], "points": positions[:n]}
-            o.update({k: geo_out[k][:n] for k in geo_keys})
-            return o
-
-        sample_keys = ("weights", "t_points", "t_intervals", "t_dirs", "ray_indices", "points") + geo_keys
-        out.defer(sample_keys, per_sample)
+        out = LazyOutputs(image_outputs(bhw, comp_rgb, comp_rgb_fg, comp_rgb_bg, opacity_, depth_, z_variance_))
+        defer_per_sample(out, n_dev, self.geometry, rays_o_flatten, rays_d_flatten, tuple(geo_out),
+                         lambda n: (t_starts_, t_ends_, weights_, t_dirs, ray_indices, positions, geo_out))
         if self.material.requires_normal:
-            def lazy_normal(geometry=self.geometry, pts=positions):
-                n = int(n_dev.item())
-                g = geometry(pts[:max(n, 1)], output_normal=True)
-                return {"normal": g["normal"], "shading_normal": g["shading_normal"]}
-            out.defer(("normal", "shading_normal"), lazy_normal)
+            defer_normals(out, self.geometry, lambda: kept_points(n_dev, lambda n: positions[:n], rays_o_flatten))
         return out
 
-    # ------------------------------------------------------------------------------------------
-    def update_step(self, epoch: int, global_step: int, on_load_weights: bool = False) -> None:
-        if self.cfg.estimator == "occgrid" and self.cfg.grid_prune:
+    def _occ_eval_fn(self, x):
+        # approximates 1 - exp(-density * step) by its first-order term (reference :436-439)
+        return self.geometry.forward_density(x) * self.render_step_size
 
-            def occ_eval_fn(x):
-                # approximates 1 - exp(-density * step) by its first-order term (reference :436-439)
-                return self.geometry.forward_density(x) * self.render_step_size
-
-            if self.training and not on_load_weights:
-                self.estimator.update_every_n_steps(step=global_step, occ_eval_fn=occ_eval_fn)
-
-    def update_step_end(self, epoch: int, global_step: int) -> None:
-        pass
-
-    def train(self, mode=True):
-        self.randomized = mode and self.cfg.randomized
-        return super().train(mode=mode)
-
-    def eval(self):
-        self.randomized = False
-        return super().eval()

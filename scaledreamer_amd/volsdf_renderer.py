@@ -31,7 +31,7 @@ import torch.nn.functional as F
 from . import nerfacc_api, ops
 from .estimators import ImportanceEstimator
 from .registry import register
-from .renderer import VolumeRenderer
+from .renderer import VolumeRenderer, background_colour, image_outputs
 from .sdf_opacity import LearnedVariance, get_alpha, kernel_color_act, volsdf_density
 
 
@@ -189,11 +189,9 @@ class GenerativeSpaceVolSDFVolumeRenderer(VolumeRenderer):
     def _outputs(self, vhw, composited, bg, samples, geo) -> Dict[str, torch.Tensor]:
         """the renderer's output dictionary (generative_space_volsdf_volume_renderer.py:395-446): the images, and while training the per-sample tensors"""
         weights, opacity, depth, fg, z_var, comp, comp_normal = composited
-        img = lambda x, c: x.reshape(*vhw, c)
-        out = {"comp_rgb": img(comp, 3), "comp_rgb_fg": img(fg, 3), "comp_rgb_bg": img(bg, 3), "opacity": img(opacity, 1),
-               "depth": img(depth, 1), "z_variance": img(z_var, 1)}
+        out = image_outputs(vhw, comp, fg, bg, opacity, depth, z_var)
         if comp_normal is not None:
-            out["comp_normal"] = img(comp_normal, 3)
+            out["comp_normal"] = comp_normal.reshape(*vhw, 3)
         if self.training:
             t_mid, t_len, t_dirs, ray_indices, positions = samples
             out.update(weights=weights[:, None], t_points=t_mid, t_intervals=t_len, t_dirs=t_dirs, ray_indices=ray_indices, points=positions, **geo)
@@ -219,11 +217,8 @@ class GenerativeSpaceVolSDFVolumeRenderer(VolumeRenderer):
         positions, t_dirs, t_mid, t_len, ray_indices = ops.volsdf_samples(ro, rd, t_edges)
         geo = _field_in_chunks(self.geometry, positions.reshape(V, -1, 3), self._chunk(), space_cache=space_cache, output_normal=True)
         bg = self._background(rays_d, text_embed)
-        blend = bg if bg_color is None else bg_color
-        if blend.dim() == 2 and blend.shape[0] == V:                      # one colour per view
-            blend = blend[:, None, None, :].expand(-1, H, W, -1)
         weights, opacity, depth, fg, z_var, comp, comp_normal = _VolSDFCompositeFn.apply(
-            geo["sdf"], geo["features"], blend.reshape(n_rays, -1).float(), p, geo.get("normal"), t_edges, self._color_act())
+            geo["sdf"], geo["features"], background_colour(bg_color, bg, V, H, W).reshape(n_rays, -1).float(), p, geo.get("normal"), t_edges, self._color_act())
         return self._outputs((V, H, W), (weights, opacity, depth, fg, z_var, comp, comp_normal), bg, (t_mid, t_len, t_dirs, ray_indices, positions), geo)
 
     # ---- one set of views with one cache entry per view -------------------------------------------------------------------------------
@@ -245,11 +240,8 @@ class GenerativeSpaceVolSDFVolumeRenderer(VolumeRenderer):
         t_light = light_positions.reshape(-1, 1, 3).expand(-1, H * W * S, -1).reshape(-1, 3)
         geo, rgb, bg = self._shade(positions, t_dirs, t_light, rays_d, space_cache, text_embed, V, extra)
         alpha = self.get_alpha(geo["sdf"], geo["normal"], t_dirs, t_len)[:, 0]
-        blend = bg if bg_color is None else bg_color
-        if blend.dim() == 2 and blend.shape[0] == V:                      # one colour per view
-            blend = blend[:, None, None, :].expand(-1, H, W, -1)
         weights, opacity, depth, fg, z_var, comp, comp_normal = self._composite(
-            alpha, rgb, blend.reshape(n_rays, -1).float(), t0f, t1f, geo.get("normal"), n_rays, S)
+            alpha, rgb, background_colour(bg_color, bg, V, H, W).reshape(n_rays, -1).float(), t0f, t1f, geo.get("normal"), n_rays, S)
         return self._outputs((V, H, W), (weights, opacity, depth, fg, z_var, comp, comp_normal), bg, (t_mid, t_len, t_dirs, ray_indices, positions), geo)
 
     def forward(self, rays_o, rays_d, light_positions, bg_color=None, noise=None, space_cache=None, text_embed=None, **kwargs):

@@ -129,6 +129,98 @@ def test_eval_mode_and_empty_rays():
     torch.testing.assert_close(out["comp_rgb"], out["comp_rgb_bg"])
 
 
+ROUTES = ("fused", "sync_free", "count")
+IMAGES = ("comp_rgb", "comp_rgb_fg", "comp_rgb_bg", "opacity", "depth", "z_variance")
+
+
+def _on_route(route, monkeypatch):
+    """the three training routes of the NeRF renderer: the fused pass (default), the composed pass with the kept count on the device (what
+    runs when the fused pass does not cover the configuration) and the pass that reads the count.  Returns the list that records how each
+    ops.compact call was made: the fused pass makes none, the device-count pass asks for zeroed ray indices, the count-reading one does not."""
+    from scaledreamer_amd import ops
+    from scaledreamer_amd.renderer import NeRFVolumeRenderer
+
+    monkeypatch.setenv("ASD_SYNC_FREE", "0" if route == "count" else "1")
+    if route == "sync_free":
+        monkeypatch.setattr(NeRFVolumeRenderer, "_fused_pass_ok", lambda self, n_rays: False)
+    compacts, real = [], ops.compact
+
+    def compact(*a, zero_ray_idx=False, **kw):
+        compacts.append(zero_ray_idx)
+        return real(*a, zero_ray_idx=zero_ray_idx, **kw)
+    monkeypatch.setattr(ops, "compact", compact)
+    return compacts
+
+
+COMPACTS = {"fused": [], "sync_free": [True], "count": [False]}
+
+
+def test_three_training_routes_agree(monkeypatch):
+    g = load_renderer_golden(RENDERER_GOLDENS[0])
+    dev = lambda k: torch.from_numpy(g[k]).cuda()
+    rays = dict(rays_o=dev("rays_o"), rays_d=dev("rays_d"), light_positions=dev("light_positions"))
+    h, w = int(g["h"]), int(g["w"])
+    colour = torch.tensor([[0.25, 0.5, 0.75]], device="cuda")
+    res = {}
+    for route in ROUTES:
+        with monkeypatch.context() as mp:
+            compacts = _on_route(route, mp)
+            geo, mat, bg, ren = build_system(g)
+            out = ren(**rays)
+            assert compacts == COMPACTS[route], route
+            loss = (out["comp_rgb"] * torch.linspace(0.5, 1.5, 3, device="cuda")).sum() + (out["opacity"] ** 2).sum() + out["z_variance"].sum()
+            loss.backward()
+            grads = {n: p.grad.detach().clone() for n, p in list(geo.named_parameters()) + [("bg." + n, p) for n, p in bg.named_parameters()]}
+            n_kept = ren.last_n_samples
+            keys = list(out.keys())
+            res[route] = (keys, {k: out[k].detach().clone() for k in keys}, grads, n_kept)
+            # one colour per view is the same image as that colour at every pixel
+            per_view = ren(**rays, bg_color=colour)
+            image = ren(**rays, bg_color=colour[:, None, None, :].expand(1, h, w, 3).contiguous())
+            assert compacts == COMPACTS[route] * 3, route
+            for k in IMAGES:
+                assert torch.equal(per_view[k], image[k]), (route, k)
+            assert not torch.equal(per_view["comp_rgb"], out["comp_rgb"])
+    keys0, out0, grads0, n0 = res["count"]
+    assert n0 == out0["weights"].shape[0]
+    for route in ("fused", "sync_free"):
+        keys1, out1, grads1, n1 = res[route]
+        assert keys1 == keys0 and n1 == n0, route
+        for k in keys0:
+            assert out0[k].shape == out1[k].shape and out0[k].dtype == out1[k].dtype, (route, k)
+            if not out0[k].dtype.is_floating_point:
+                assert torch.equal(out0[k], out1[k]), (route, k)
+            else:
+                torch.testing.assert_close(out1[k], out0[k], rtol=1e-6, atol=1e-6, msg=f"{route} {k}")
+        assert set(grads1) == set(grads0)
+        for k in grads0:
+            scale = float(grads0[k].abs().max())
+            assert float((grads1[k] - grads0[k]).abs().max()) <= 1e-4 * max(scale, 1e-12), (route, k)      # atomics: summation order only
+
+
+def test_all_miss_batch_on_every_training_route(monkeypatch):
+    """rays that miss the box entirely: the reference's one dummy sample on every route, at the origin of ray 0.  `last_n_samples` is what
+    each route stores: the dummy's row where the count is read, the device's own count (zero) where it is not."""
+    g = load_renderer_golden(RENDERER_GOLDENS[0])
+    o = torch.full((1, 4, 4, 3), 5.0, device="cuda")
+    d = torch.nn.functional.normalize(torch.ones(1, 4, 4, 3, device="cuda"), dim=-1)
+    for route in ROUTES:
+        with monkeypatch.context() as mp:
+            compacts = _on_route(route, mp)
+            geo, mat, bg, ren = build_system(g)
+            out = ren(rays_o=o, rays_d=d, light_positions=o[:, 0, 0])
+            assert compacts == COMPACTS[route], route
+            assert out["weights"].shape == (1, 1) and out["ray_indices"].tolist() == [0], route
+            assert float(out["opacity"].detach().abs().max()) == 0.0, route
+            torch.testing.assert_close(out["comp_rgb"], out["comp_rgb_bg"])
+            for k, cols in (("density", 1), ("features", 3), ("normal", 3), ("shading_normal", 3)):
+                assert out[k].shape == (1, cols), (route, k)
+            assert ren.last_n_samples == (1 if route == "count" else 0), route
+            # the dummy sits at the origin of ray 0 on every route, its normal is that of the field there: nothing comes from unwritten rows
+            assert torch.equal(out["points"], o.reshape(-1, 3)[:1]), route
+            assert torch.equal(out["normal"], geo(o.reshape(-1, 3)[:1], output_normal=True)["normal"]), route
+
+
 def test_sync_free_training_pass_equals_the_pass_that_reads_the_count(monkeypatch):
     """renderer.forward keeps the kept-sample count on the device in training (capacity-sized sample tensors, `n_dev` into the field
     kernels, per-sample dictionary entries cut to length on first access): same outputs, same gradients as the pass that reads the

@@ -108,7 +108,8 @@ def record(name, out):
     torch.cuda.synchronize()
 
 
-def compare(ref, other, noise):
+def compare(ref, other, noise, noisy=("grad/",)):
+    """`noisy`: the key prefixes judged against the run-to-run difference of REF's tree; everything else must be equal bit for bit"""
     a, b = torch.load(ref), torch.load(other)
     c = torch.load(noise) if noise else None
     bad = sorted(set(a) ^ set(b))
@@ -123,7 +124,7 @@ def compare(ref, other, noise):
             continue
         d_other = dist(a[k], b[k])
         d_noise = dist(a[k], c[k]) if c is not None and k in c else None
-        if k.startswith("grad/"):
+        if k.startswith(noisy):
             ok = d_other <= 2 * d_noise if d_noise is not None else torch.equal(a[k], b[k])
         else:
             ok = torch.equal(a[k], b[k])
