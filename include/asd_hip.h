@@ -529,7 +529,10 @@ int asd_gemm_tile_info(int32_t i, int32_t* out7);
 
 #define ASD_GN_STATS_FLOATS(batch) (64 * (batch) + 64 * (512 + (batch)))
 /* GroupNorm(32 groups) [+ SiLU] on NHWC fp16 with fp32 statistics (GroupNorm32, diffusionmodules/util.py:229-231);
- * x may be the channel-concatenation of two tensors (skip connections, openaimodel.py:797-799): x2/c2. */
+ * x may be the channel-concatenation of two tensors (skip connections, openaimodel.py:797-799): x2/c2 (x2 == NULL or c2 == 0: x1 alone;
+ * x2 is not read then).  Enforced by this entry and by asd_groupnorm_apply_f16 / _bwd_f16 / _bwd_apply_f16: channels (c1 + c2) a
+ * multiple of 32 and at most 4096 (a thread of the 256-thread passes owns at most two 8-channel slots), c1 % 8 == 0, gamma / beta
+ * 16-byte aligned; anything else is refused with ASD_ERR_ARG before a launch. */
 int asd_groupnorm_f16(const void* x1, int32_t c1, const void* x2, int32_t c2, int32_t batch, int32_t hw,
                       const void* gamma, const void* beta, float eps, int32_t silu, void* y,
                       float* stats /* ASD_GN_STATS_FLOATS(batch): [batch*32*2] sums for the backward pass + per-block partials */,
@@ -542,7 +545,9 @@ int asd_groupnorm_ordered_f16(const void* x, int32_t c, int32_t batch, int32_t h
                               int32_t silu, void* y, float* stats, void* stream);
 /* the same GroupNorm when the tensor's producer already left its statistics as `records` 64-float records per batch element
  * (asd_gemm_args.gn_partials): no statistics pass over x.  stats: ASD_GN_STATS_FLOATS(batch) floats; its first batch*64 receive the
- * per-(batch, group) sums (kept for a backward pass). */
+ * per-(batch, group) sums (kept for a backward pass).  More than 96 records per batch element are first summed in slices of 32 or more
+ * records into the 64 * (512 + batch) floats behind those sums: at most 16 slices, and no more than fit that area (batch > 34: fewer,
+ * longer slices), so no batch size writes past ASD_GN_STATS_FLOATS(batch).  c <= 4096 as above. */
 int asd_groupnorm_apply_f16(const void* x, int32_t c, int32_t batch, int32_t hw, const void* gamma, const void* beta, float eps,
                             int32_t silu, const float* partials, int32_t records, void* y, float* stats, void* stream);
 /* Input gradient of GroupNorm(+SiLU) with frozen gamma/beta (VAE encoder backward, the reference keeps the
@@ -553,10 +558,11 @@ int asd_groupnorm_bwd_f16(const void* x, const void* dy, int32_t c, int32_t batc
                                                 its other consumer (the ResnetBlock shortcut, model.py:141-148) */,
                           void* dx, float* bwd_stats /* workspace: ASD_GN_STATS_FLOATS(batch) - 64*batch floats */, void* stream);
 /* the same input gradient when the producer of dy already left the two reductions as `records` 64-float records per batch element
- * (asd_gemm_args.gn_partials with gn_bwd_x set) */
+ * (asd_gemm_args.gn_partials with gn_bwd_x set).  scratch is sized like bwd_stats above and is written only with more than 96 records:
+ * min(16, ceil(records / 32), (512 + batch) / batch) slices of 64 floats per batch element, which always fit it.  c <= 4096. */
 int asd_groupnorm_bwd_apply_f16(const void* x, const void* dy, int32_t c, int32_t batch, int32_t hw, const void* gamma, const void* beta,
                                 float eps, int32_t silu, const float* fwd_stats, const float* partials, int32_t records,
-                                const void* dx_add, void* dx, float* scratch /* (16 * batch) * 64 floats */, void* stream);
+                                const void* dx_add, void* dx, float* scratch /* ASD_GN_STATS_FLOATS(batch) - 64*batch floats */, void* stream);
 /* y[cols, rows] = x[rows, cols]^T, fp16 (operand layout changes for the attention-backward GEMMs). */
 int asd_transpose_f16(const void* x, int32_t rows, int32_t cols, int32_t ldx, void* y, int32_t ldy, void* stream);
 /* LayerNorm over the last dim (attention.py:265-267), fp16 in/out, fp32 statistics. */

@@ -18,6 +18,7 @@ __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff
 // pair per block and group).
 #define GN_UNR 4      // rows in flight per thread (16-B loads)
 #define GN_CAP_A 512  // apply blocks per launch
+#define GN_MAX_C 4096 // 256 threads x two 8-channel slots: channels from here on would be neither read nor written, so the entries refuse them
 #define GN_FOLD_RECORDS 96   // up to this many epilogue records per batch element are summed by every apply block itself (24 KB of L2
                              // reads, four loads in flight per thread); above it a reduce launch (~5 us) runs first
 
@@ -653,6 +654,16 @@ __global__ __launch_bounds__(1024) void gn_reduce_records_kernel(const float* __
     }
 }
 
+// slices the records of a batch element are summed in when there are more than GN_FOLD_RECORDS: 32 records each, at most 16, and
+// no more than fit the partials area behind the batch * 64 sums of ASD_GN_STATS_FLOATS(batch), 64 * (512 + batch) floats (with 16 slices
+// that is batch <= 34; beyond, fewer and longer slices: the area always holds one slice per batch element)
+static int gn_record_slices(int records, int batch) {
+    int slices = asd_div_up(records, 32);
+    if (slices > 16) slices = 16;
+    const int fit = (512 + batch) / batch;
+    return slices > fit ? fit : slices;
+}
+
 // apply blocks per batch element: one trip of the row loop (GN_UNR rows x the rows a block holds in flight) per block while that
 // keeps the launch under GN_CAP_A blocks — the small low-resolution tensors (8x8 ... 32x32) are latency-, not bandwidth-bound, and a
 // block that walks 16 rows of a 1280-channel tensor four at a time spends its life in four dependent memory round trips
@@ -732,6 +743,7 @@ int asd_groupnorm_f16(const void* x1, int32_t c1, const void* x2, int32_t c2, in
     const int C = c1 + (x2 ? c2 : 0);
     if (!x2) c2 = 0;
     ASD_CHECK_ARG(C % 32 == 0 && C % 8 == 0 && c1 % 8 == 0, "channels must be a multiple of 32");
+    ASD_CHECK_ARG(C <= GN_MAX_C, "at most 4096 channels (a thread owns at most two 8-channel slots)");
     ASD_CHECK_ARG(((((uintptr_t)gamma) | ((uintptr_t)beta)) & 15) == 0, "gamma / beta must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     float* partials = stats + 64 * batch;   // [batch, chunks_s, 64] per-block partial sums (plain stores: nothing to zero)
@@ -771,15 +783,15 @@ int asd_groupnorm_apply_f16(const void* x, int32_t c, int32_t batch, int32_t hw,
                             int32_t silu, const float* partials, int32_t records, void* y, float* stats /* ASD_GN_STATS_FLOATS(batch) */, void* stream) {
     ASD_CHECK_ARG(x && gamma && beta && y && stats && partials && batch > 0 && hw > 0 && records > 0, "null argument");
     ASD_CHECK_ARG(c % 32 == 0 && c % 8 == 0, "channels must be a multiple of 32");
+    ASD_CHECK_ARG(c <= GN_MAX_C, "at most 4096 channels (a thread owns at most two 8-channel slots)");
     ASD_CHECK_ARG(((((uintptr_t)gamma) | ((uintptr_t)beta)) & 15) == 0, "gamma / beta must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const int chunks_a = gn_apply_chunks(hw, c, batch);
     // every apply block sums the records of its batch element in its prologue: with many tiles, sum them once first
     const float* part = partials;
     int n = records;
-    if (records > GN_FOLD_RECORDS) {                  // slices of <= 32 records, at most 16 of them left for the apply prologue
-        int slices = asd_div_up(records, 32);
-        if (slices > 16) slices = 16;
+    if (records > GN_FOLD_RECORDS) {                  // slices of >= 32 records, at most 16 of them left for the apply prologue
+        const int slices = gn_record_slices(records, batch);
         float* tmp = stats + 64 * batch;              // the per-block partials area of ASD_GN_STATS_FLOATS(batch)
         hipLaunchKernelGGL(gn_reduce_records_kernel, dim3(batch, slices), dim3(1024), 0, s, partials, records, tmp);
         part = tmp;
@@ -795,6 +807,7 @@ int asd_groupnorm_bwd_f16(const void* x, const void* dy, int32_t c, int32_t batc
                           float* bwd_stats, void* stream) {
     ASD_CHECK_ARG(x && dy && gamma && beta && fwd_stats && dx && bwd_stats && batch > 0 && hw > 0, "null argument");
     ASD_CHECK_ARG(c % 32 == 0, "channels must be a multiple of 32");
+    ASD_CHECK_ARG(c <= GN_MAX_C, "at most 4096 channels (a thread owns at most two 8-channel slots)");
     ASD_CHECK_ARG(((((uintptr_t)gamma) | ((uintptr_t)beta)) & 15) == 0, "gamma / beta must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     int chunks = asd_div_up(hw, 16);
@@ -815,6 +828,7 @@ int asd_groupnorm_bwd_apply_f16(const void* x, const void* dy, int32_t c, int32_
                                 const void* dx_add, void* dx, float* scratch, void* stream) {
     ASD_CHECK_ARG(x && dy && gamma && beta && fwd_stats && partials && dx && scratch && batch > 0 && hw > 0 && records > 0, "null argument");
     ASD_CHECK_ARG(c % 32 == 0, "channels must be a multiple of 32");
+    ASD_CHECK_ARG(c <= GN_MAX_C, "at most 4096 channels (a thread owns at most two 8-channel slots)");
     ASD_CHECK_ARG(((((uintptr_t)gamma) | ((uintptr_t)beta)) & 15) == 0, "gamma / beta must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const int chunks = asd_div_up(hw, 16);
@@ -822,8 +836,7 @@ int asd_groupnorm_bwd_apply_f16(const void* x, const void* dy, int32_t c, int32_
     const float* part = partials;
     int n = records;
     if (records > GN_FOLD_RECORDS) {
-        int slices = asd_div_up(records, 32);
-        if (slices > 16) slices = 16;
+        const int slices = gn_record_slices(records, batch);
         hipLaunchKernelGGL(gn_reduce_records_kernel, dim3(batch, slices), dim3(1024), 0, s, partials, records, scratch);
         part = scratch;
         n = slices;
