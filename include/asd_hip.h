@@ -188,6 +188,32 @@ int asd_envmap_bwd(const asd_grid_meta* meta, const float* grid_params,
                    const float* dirs, const float* d_color, int32_t n,
                    float* d_grid_params, float* dw0, float* dw1, float* dw2, void* stream);
 
+/* `textured-background`: TexturedBackground.forward (threestudio/models/background/textured_background.py:29-54) =
+ * spherical_xyz_to_uv + F.grid_sample(texture[1,C,H,W], bilinear, reflection, align_corners = False) + the colour activation.
+ * texture [C,H,W] is the reference's parameter as it lies; C in 1..8.  u = atan2(sqrt(x^2 + y^2), z) / pi indexes the WIDTH,
+ * v = atan2(y, x) / (2 pi) + 0.5 the HEIGHT; ix = u W - 0.5, iy = v H - 0.5, both clamped to the image (u, v lie in [0, 1], so the
+ * reflection never acts and grid_sample's clip is this clamp); no wrap at the azimuth seam.  activation: 0 none, 1 sigmoid.
+ * color[n,C] (16-byte aligned when C is 4 or 8).  n = 0 is success and writes nothing. */
+int asd_bg_texture_fwd(const float* texture /*[C,H,W]*/, int32_t C, int32_t H, int32_t W, int32_t activation,
+                       const float* dirs /*[n,3]*/, int32_t n, float* color /*[n,C]*/, void* stream);
+/* Its autograd backward with respect to the texture: d_texture[C,H,W] is OVERWRITTEN (the caller zeroes nothing; texels no ray
+ * reaches are +0.0f; n = 0 gives all zeros).  No gradient with respect to the directions.  Gradient images of up to 128 KiB are summed
+ * in LDS per workgroup and then across the workgroups' slabs in a fixed order (`workspace`: asd_bg_texture_bwd_workspace() floats,
+ * 16-byte aligned, may be NULL when that is 0; then d_texture is 16-byte aligned); larger ones take global float atomics. */
+int asd_bg_texture_bwd_workspace(int32_t C, int32_t H, int32_t W, int32_t n, int64_t* n_floats);
+int asd_bg_texture_bwd(const float* texture, int32_t C, int32_t H, int32_t W, int32_t activation,
+                       const float* dirs, const float* d_color /*[n,C]*/, int32_t n,
+                       float* d_texture /*[C,H,W]*/, float* workspace, void* stream);
+
+/* `solid-color-background`: SolidColorBackground.forward (threestudio/models/background/solid_color_background.py:36-51):
+ * out[v * rays_per_view + r, :] = colors[v, :].  n_views = 1 is the configured / learned env_color (:37-39), n_views = batch the
+ * per-view colours of random_aug (:46-50).  C in 1..8. */
+int asd_bg_solid_fwd(const float* colors /*[n_views,C]*/, int32_t C, int32_t n_views, int32_t rays_per_view,
+                     float* out /*[n_views*rays_per_view,C]*/, void* stream);
+/* autograd backward of the broadcast above: d_colors[v, :] = sum over the view's rays of d_out, in a fixed order (overwritten). */
+int asd_bg_solid_bwd(const float* d_out /*[n_views*rays_per_view,C]*/, int32_t C, int32_t n_views, int32_t rays_per_view,
+                     float* d_colors /*[n_views,C]*/, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Amortized (multi-prompt) render path: importance sampling on dense [n_rays, edges] tensors, replacing the
  * nerfacc v0.5.2 calls of ImportanceEstimator.sampling (threestudio/models/estimators.py:72-74,84-88,93-94).

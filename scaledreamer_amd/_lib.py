@@ -18,6 +18,7 @@ ASD_MAX_LEVELS = 16
 ASD_BIAS_CONST, ASD_BIAS_BLOB_MAGIC3D, ASD_BIAS_BLOB_DREAMFUSION, ASD_BIAS_SPHERE = 0, 1, 2, 3
 ASD_FIELD_DENSITY, ASD_FIELD_SDF = 0, 1
 ASD_ACT_SOFTPLUS, ASD_ACT_EXP, ASD_ACT_TRUNC_EXP, ASD_ACT_NONE = 0, 1, 2, 3
+ASD_BG_ACT_NONE, ASD_BG_ACT_SIGMOID = 0, 1       # asd_bg_texture_*: the activations fused in the kernels
 
 
 class AsdError(RuntimeError):
@@ -172,6 +173,7 @@ SYMBOLS = [
     "asd_field_density", "asd_field_fwd", "asd_field_bwd_workspace", "asd_field_bwd",
     "asd_field_analytic_fwd", "asd_field_analytic_bwd_workspace", "asd_field_analytic_bwd",
     "asd_envmap_fwd", "asd_envmap_bwd",
+    "asd_bg_texture_fwd", "asd_bg_texture_bwd_workspace", "asd_bg_texture_bwd", "asd_bg_solid_fwd", "asd_bg_solid_bwd",
     "asd_importance_resample", "asd_transmittance_cdf", "asd_merge_sorted", "asd_voxel_sample_fwd", "asd_voxel_sample_bwd", "asd_voxel_sample_bwd_rows",
     "asd_triplane_sample_fwd", "asd_triplane_sample_bwd", "asd_triplane_sample_bwd_rows", "asd_relayout_f32",
     "asd_volsdf_edges", "asd_volsdf_samples", "asd_volsdf_proposal_cdf", "asd_volsdf_composite_fwd", "asd_volsdf_composite_bwd",

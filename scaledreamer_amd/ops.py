@@ -172,6 +172,54 @@ def envmap_bwd(meta, grid, w0, w1, w2, dirs, d_color):
     return dgrid, dw0, dw1, dw2
 
 
+def bg_texture_fwd(texture: torch.Tensor, dirs: torch.Tensor, activation: int = L.ASD_BG_ACT_SIGMOID) -> torch.Tensor:
+    """texture [C,H,W] (or the parameter's [1,C,H,W]), dirs [n,3] -> color [n,C]; activation: ASD_BG_ACT_*"""
+    _need_cuda(texture, dirs)
+    Cc, H, W = texture.shape[-3:]
+    dirs = _c(dirs)
+    color = torch.empty((dirs.shape[0], Cc), device=dirs.device, dtype=torch.float32)
+    k = _Keep()
+    check(lib().asd_bg_texture_fwd(k(texture), i32(Cc), i32(H), i32(W), i32(activation), ptr(dirs), i32(dirs.shape[0]), ptr(color), stream()))
+    return color
+
+
+def bg_texture_bwd(texture: torch.Tensor, dirs: torch.Tensor, d_color: torch.Tensor, activation: int = L.ASD_BG_ACT_SIGMOID) -> torch.Tensor:
+    """-> d_texture, shaped like texture (written by the pass: nothing is zeroed here)"""
+    _need_cuda(texture, dirs, d_color)
+    Cc, H, W = texture.shape[-3:]
+    dirs, d_color = _c(dirs), _c(d_color)
+    n = dirs.shape[0]
+    nf = C.c_int64(0)
+    check(lib().asd_bg_texture_bwd_workspace(i32(Cc), i32(H), i32(W), i32(n), C.byref(nf)))
+    ws = torch.empty(nf.value, device=dirs.device, dtype=torch.float32) if nf.value else None
+    d_texture = torch.empty(texture.shape, device=dirs.device, dtype=torch.float32)
+    k = _Keep()
+    check(lib().asd_bg_texture_bwd(k(texture), i32(Cc), i32(H), i32(W), i32(activation), ptr(dirs), ptr(d_color), i32(n), ptr(d_texture),
+                                   ptr(ws), stream()))
+    return d_texture
+
+
+def bg_solid_fwd(colors: torch.Tensor, rays_per_view: int) -> torch.Tensor:
+    """colors [V,C] -> out [V * rays_per_view, C]"""
+    _need_cuda(colors)
+    colors = _c(colors)
+    V, Cc = colors.shape
+    out = torch.empty((V * rays_per_view, Cc), device=colors.device, dtype=torch.float32)
+    check(lib().asd_bg_solid_fwd(ptr(colors), i32(Cc), i32(V), i32(rays_per_view), ptr(out), stream()))
+    return out
+
+
+def bg_solid_bwd(d_out: torch.Tensor, n_views: int) -> torch.Tensor:
+    """d_out [V * R, C] -> d_colors [V,C], the fixed-order sum over each view's rays"""
+    _need_cuda(d_out)
+    d_out = _c(d_out)
+    Cc = d_out.shape[-1]
+    rays = d_out.shape[0] // n_views if n_views else 0
+    d_colors = torch.empty((n_views, Cc), device=d_out.device, dtype=torch.float32)
+    check(lib().asd_bg_solid_bwd(ptr(d_out), i32(Cc), i32(n_views), i32(rays), ptr(d_colors), stream()))
+    return d_colors
+
+
 # ---- marching ---------------------------------------------------------------------------------
 def scan_i32(count: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     offset = torch.empty_like(count)
